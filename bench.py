@@ -13,14 +13,22 @@ pixel rows: strong scaling.
 Metric: Msamples/s (nominal) = W*H*spp*bounces / t / 1e6,
 ms/frame = ms_per_step.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
-                  [--no-cpu-baseline] [--cpu-threads T] [--dist] [--no-overlap]
-The CPU baseline is the library's scalar C++ fallback (rt_render_cpu) on
-every CPU of the process's affinity (or --cpu-threads), timed on rank 0 at
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--full]
+                  [--dump-outputs DIR] [--no-cpu-baseline] [--cpu-threads T]
+                  [--dist] [--no-overlap]
+A plain run at N = 1 sets up, warms up, times the K steps and prints the
+result line; everything else it can measure or check at N = 1 is behind
+--full.  --dump-outputs DIR writes what the last timed step computed (the
+frame, and at N = 1 its frameSum) as float32 DIR/<name>.npy after the timed
+steps; the inputs (scene, y*W+x seeds, step count) are a function of the
+arguments alone, so two builds can be compared output for output.
+--full: the CPU baseline is the library's scalar C++ fallback (rt_render_cpu)
+on every CPU of the process's affinity (or --cpu-threads), timed on rank 0 at
 N = 1 after the GPU steps, and checked bit-exact against the GPU; in the same
 leg the oracle (oracle/, the checker) renders the bench frame (config 4: a
 row sample; config 5: none) and the GPU's frame, frameSum and RNG state
-must equal it bit for bit ("oracle_check", "verified").
+must equal it bit for bit ("oracle_check", "verified").  --no-cpu-baseline
+leaves that leg out of a --full run (a plain run never has it).
 --dist takes the multi-rank code path (process group, gather, de-interleave,
 verify) at N = 1 too.
 N > 1: one rank per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE
@@ -66,7 +74,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(scenes.CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also time the CPU baseline and check the GPU against it and "
+                         "against the oracle (cpu_baseline, oracle_check, verified); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs as float32 DIR/<name>.npy: image "
+                         "(rows, W, 4: the RGBA8 frame), without --dist at N = 1 frame_sum (rows, W, 3), and rows (the frame rows "
+                         "written: all of them, or a fixed seeded sample when the frame exceeds 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU-baseline / oracle leg out")
     ap.add_argument("--verify", action="store_true",
                     help="also at N = 1: re-render from fresh seeds and check the frame against the CPU fallback's "
                          "rows (N > 1 always checks the gathered frame against rank 0's single-GPU render)")
@@ -179,6 +195,24 @@ def oracle_check(config, scene_key, w, h, spp, mb, gpu_renderer):
     return {"rows": st.rows, "row_stride": stride, "bit_exact": exact,
             "compared": "RGBA8, frameSum and RNG state after all frames",
             "oracle_ms": round(dt * 1e3, 1), "oracle": "oracle/oracle.c (C restatement of Main.cu:111-315, OpenMP)"}
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: every file together stays below this
+
+
+def dump_outputs(path, arrays):
+    """Write `arrays` (name -> (H, ...) array, one entry per frame row) as
+    float32 path/<name>.npy, and the rows written as path/rows.npy: every row
+    while that fits DUMP_BUDGET_BYTES, else a fixed (seed 0) sorted sample."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    h = next(iter(arrays.values())).shape[0]
+    bytes_per_row = sum(a[0].size for a in arrays.values()) * 4
+    keep = min(h, (DUMP_BUDGET_BYTES - 8 * h - 4096) // bytes_per_row)  # less rows.npy and the .npy headers
+    rows = np.arange(h) if keep == h else np.sort(np.random.default_rng(0).choice(h, keep, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a[rows], dtype=np.float32))
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
 
 
 def load_traffic(paths, workload_key):
@@ -354,6 +388,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, kern_avg_ms, issue_s = float(t[0]), float(t[1]), float(t[2])
     kernel_timing = "event pair around the timed launches on the render stream, / steps"
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left: the frame it wrote (N > 1: the
+        # gathered, de-interleaved frame) and, at N = 1, the context's frameSum
+        dump = {"image": full_img.cpu().numpy().view("uint8").reshape(H, W, 4)}
+        if not distributed:
+            dump["frame_sum"] = r.get_state(H, W)[1]
+        dump_outputs(args.dump_outputs, dump)
     if distributed:
         # the timed region's span on the render stream also holds its waits
         # for the gather stream (and, with --no-overlap, the gather itself):
@@ -488,7 +529,7 @@ def main():
                 "cycles_per_miss_line": round(L1_MISS_CYCLES_PER_LINE, 3), "model_floor_ms": round(floor_ms, 3),
                 "model_floor_frac": round(floor_ms / kern_avg_ms, 4), "counters": traffic.get("source"),
                 "micro": L1_MICRO}
-        if not distributed and not args.no_cpu_baseline:
+        if args.full and not distributed and not args.no_cpu_baseline:
             torch.cuda.synchronize(dev)
             with Renderer(dev_index, lib=lib) as check:
                 check.set_scene(scene)

@@ -114,6 +114,43 @@ def test_traffic_record_is_per_workload(bench, tmp_path):
     assert 0.95 < bench.L1_HIT_CYCLES_PER_LINE < 1.05 and bench.L1_MISS_CYCLES_PER_LINE > 2
 
 
+def test_plain_run_options(bench, monkeypatch):
+    """A plain run has neither the CPU-baseline leg nor a dump; --full and
+    --dump-outputs DIR switch them on."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_files(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float32 <name>.npy per array plus rows.npy; every row
+    while the files fit the budget, else the same sorted row sample on every
+    call, and never more bytes than the budget."""
+    import numpy as np
+    img = np.arange(40 * 8 * 4, dtype=np.uint8).reshape(40, 8, 4)
+    acc = np.linspace(0, 1, 40 * 8 * 3, dtype=np.float32).reshape(40, 8, 3)
+    bench.dump_outputs(str(tmp_path / "all"), {"image": img, "frame_sum": acc})
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("image", "frame_sum", "rows")}
+    assert got["image"].dtype == np.float32 and got["frame_sum"].dtype == np.float32
+    assert got["rows"].dtype == np.float64 and np.array_equal(got["rows"], np.arange(40))
+    assert np.array_equal(got["image"], img.astype(np.float32)) and np.array_equal(got["frame_sum"], acc)
+    # a budget that holds 10 of the 40 rows (8 * (4 + 3) * 4 = 224 bytes a row)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 40 + 4096 + 224 * 10 + 100)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"image": img, "frame_sum": acc})
+    rows = np.load(tmp_path / "s1" / "rows.npy").astype(int)
+    assert len(rows) == 10 and len(set(rows)) == 10 and list(rows) == sorted(rows) and rows.max() < 40
+    assert np.array_equal(np.load(tmp_path / "s1" / "image.npy"), img[rows].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "s1" / "frame_sum.npy"), acc[rows])
+    assert np.array_equal(np.load(tmp_path / "s2" / "rows.npy"), rows)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= bench.DUMP_BUDGET_BYTES
+    # the headline frame (1920x1080, image + frame_sum) fits whole
+    assert 1080 * 1920 * (4 + 3) * 4 + 8 * 1080 + 4096 <= 64 * 10**6
+
+
 def test_oracle_check_leg(bench, bwrt_lib):
     """The bench's oracle check (CPU-baseline leg, checker only) on config 1:
     the renderer it is handed (here the product's CPU backend, on the GPU box

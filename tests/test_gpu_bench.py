@@ -41,6 +41,40 @@ def test_bench_plain_launch_two_ranks_verified():
 
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_last_step(tmp_path, bwrt_lib):
+    """A plain `bench.py --gpus 1 --steps 2 --warmup 1` times exactly its
+    steps and carries no CPU-baseline leg; --dump-outputs writes the last
+    step's frame and frameSum, which a renderer taking the same three
+    renders from the same seeds reproduces bit for bit."""
+    import numpy as np
+    from bwrt import Renderer, scenes
+    env = {k: v for k, v in os.environ.items() if k == "BWRT_LIB" or not k.startswith("BWRT_")}
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")],
+                       env=env, cwd=REPO, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["ms_per_step"] > 0 and out["unit"] == "Msamples/s" and out["dtype"] == "f32"
+    assert abs(out["value"] - 1920 * 1080 * 8 * 4 / out["ms_per_step"] / 1e3) <= 1e-3 * out["value"]
+    assert "cpu_baseline" not in out and "oracle_check" not in out and out["verified"] is None
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("image", "frame_sum", "rows")}
+    assert got["image"].dtype == np.float32 and got["image"].shape == (1080, 1920, 4)
+    assert got["frame_sum"].dtype == np.float32 and got["frame_sum"].shape == (1080, 1920, 3)
+    assert np.array_equal(got["rows"], np.arange(1080))
+    with Renderer(0, lib=bwrt_lib) as g:
+        g.set_scene(scenes.SCENES["07"]())
+        g.init_rand(1920, 1080)
+        for _ in range(3):  # 1 warm-up + 2 timed steps, the RNG streams continuing
+            img, acc = g.render(1920, 1080, 8, 4, first_frame=1, want_accum=True)
+    assert np.array_equal(got["image"], img.astype(np.float32))
+    assert np.array_equal(got["frame_sum"], acc, equal_nan=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
 def test_bench_rccl_path_one_rank_verified():
     """The RCCL branch every N > 1 point of the headline takes (nccl process
     group with device_id, rooted gather of the row blocks on the gather

@@ -12,7 +12,7 @@ timeout -k 10 900 python -u -m pytest tests -q -m gpu -x --timeout 300 --timeout
 echo "pytest_gpu rc=$rc: $(tail -1 $OUT/pytest_gpu.log)"; [ $rc = 0 ] || { tail -30 $OUT/pytest_gpu.log; exit 1; }
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo smoke failed; cat $OUT/smoke.log; exit 1; }
 grep smoke $OUT/smoke.log
-timeout -k 10 300 python bench.py > $OUT/bench.log 2>&1 || { echo bench failed; tail -5 $OUT/bench.log; exit 1; }
+timeout -k 10 300 python bench.py --full > $OUT/bench.log 2>&1 || { echo bench failed; tail -5 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log | cut -c1-300
 for c in c3:1,2,4,6,8,16 c2:1,2,4,8; do
   BWRT_TUNING=1 timeout -k 10 200 python tools/shard_sweep.py --config ${c%:*} --strides ${c#*:} --blocks 0 --reps 20 > $OUT/shards_${c%:*}.txt 2>&1 || { echo "shards ${c%:*} failed"; exit 1; }
