@@ -83,6 +83,8 @@ RT_ERR_NO_DEVICE = -2
 RT_ERR_UNSUPPORTED = -6
 RT_MAX_BOUNCES = 32
 RT_DEFAULT_MAX_BOUNCES = 5
+RT_PRECISION_EXACT = 0
+RT_PRECISION_REFERENCE_FAST = 1
 
 _lib = None
 
@@ -106,6 +108,8 @@ def _proto(lib):
         "rt_frame_counter": (C.c_uint, [vp]),
         "rt_set_max_bounces": (C.c_int, [vp, C.c_int]),
         "rt_set_background": (C.c_int, [vp, C.c_float, C.c_float, C.c_float]),
+        "rt_set_precision": (C.c_int, [vp, C.c_int]),
+        "rt_get_precision": (C.c_int, [vp]),
         "rt_set_samples_per_pixel": (C.c_int, [vp, C.c_int]),
         "rt_get_camera": (C.c_int, [vp, P(Camera)]),
         "rt_apply_controls": (C.c_int, [P(Camera), C.c_uint, C.c_float]),

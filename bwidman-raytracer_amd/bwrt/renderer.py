@@ -87,6 +87,21 @@ class Renderer:
         """backgroundColor (Main.cu:27): radiance of misses and the depth cut-off."""
         self._check(self.lib.rt_set_background(self.ctx, r, g, b))
 
+    _PRECISIONS = {"exact": abi.RT_PRECISION_EXACT, "fast": abi.RT_PRECISION_REFERENCE_FAST}
+
+    def set_precision(self, mode: str):
+        """rt_set_precision: "exact" (the default: bit-identical to the oracle)
+        or "fast" (the reference's fast-math trade-off: hardware rcp / sqrt /
+        sin / cos and FMAs; GPU renderers only).  Takes effect at the next
+        render; accumulation, frame counter and RNG streams stay."""
+        if mode not in self._PRECISIONS:
+            raise ValueError(f"precision {mode!r}: expected 'exact' or 'fast'")
+        self._check(self.lib.rt_set_precision(self.ctx, self._PRECISIONS[mode]))
+
+    @property
+    def precision(self) -> str:
+        return "fast" if self.lib.rt_get_precision(self.ctx) == abi.RT_PRECISION_REFERENCE_FAST else "exact"
+
     def set_samples_per_pixel(self, n: int):
         """samplesPerPixel (Main.cu:27, 296-299): n paths per frame from one
         jittered camera ray, the last one kept and scaled by 1/n (default 1)."""

@@ -34,6 +34,12 @@ hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, boo
                             hipStream_t stream, int pair_req);
 hipError_t rt_launch_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride,
                                hipStream_t stream);
+// the reference-fast instantiations (rt_kernels_fast.hip, rt_kernels_bvh_fast.hip)
+namespace rt_fast {
+bool rt_render_wants_global_records(const rt_kparams& K, int num_cus);
+hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, bool simple, int block_req,
+                            hipStream_t stream, int pair_req);
+}  // namespace rt_fast
 extern thread_local long rt_order_groups_last;
 extern thread_local char rt_launched_kernel[96];
 hipError_t rt_launch_deinterleave(const unsigned* gathered, unsigned* image, int width, int height,
@@ -158,6 +164,7 @@ struct rt_context {
     int spread = -1;             // BWRT_SPREAD: 1 / 0 force the pair kernel on / off (-1 = launch policy)
     int deint_blocks = 0;        // BWRT_DEINT_BLOCKS: cap on the de-interleave grid (0 = one thread per 16 bytes)
     std::string kernel_name;     // the render kernel of the last launch (rt_last_kernel_name)
+    int precision = RT_PRECISION_EXACT;  // rt_set_precision (BWRT_PRECISION): which kernels the next render launches
     unsigned frame = 1;
     int max_bounces = RT_DEFAULT_MAX_BOUNCES;
     int spp_inner = 1;  // samplesPerPixel, Main.cu:27
@@ -864,7 +871,7 @@ struct BvhBuilder {
 
 extern "C" {
 
-const char* rt_version(void) { return "0.1.0"; }
+const char* rt_version(void) { return "0.2.0"; }
 
 rt_material rt_material_default(void) {
     rt_material m;
@@ -925,6 +932,8 @@ int rt_create(int device, rt_context** out) {
     if (const char* g = tuning_env("BWRT_SPREAD")) c->spread = std::atoi(g) ? 1 : 0;
     if (const char* g = tuning_env("BWRT_ORDER")) c->order_feedback = std::atoi(g) != 0;
     if (const char* g = tuning_env("BWRT_ORDER_PERIOD")) c->order_period = std::max(std::atoi(g), 1);
+    if (const char* g = tuning_env("BWRT_PRECISION"))
+        c->precision = std::strcmp(g, "fast") == 0 ? RT_PRECISION_REFERENCE_FAST : RT_PRECISION_EXACT;
     *out = c;
     return RT_OK;
 }
@@ -1324,6 +1333,22 @@ int rt_set_background(rt_context* c, float r, float g, float b) {
     return RT_OK;
 }
 
+// Only the choice of kernels at the next launch: the shard state (RNG
+// streams, frameSum, frame counter) is shared by both modes and stays
+int rt_set_precision(rt_context* c, int precision) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (precision != RT_PRECISION_EXACT && precision != RT_PRECISION_REFERENCE_FAST)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_set_precision: unknown precision %d", precision);
+    if (c->cpu && precision != RT_PRECISION_EXACT)
+        return fail(c, RT_ERR_UNSUPPORTED,
+                    "rt_set_precision: RT_PRECISION_REFERENCE_FAST is not supported on a CPU context "
+                    "(the CPU fallback is bit-identical to the exact kernels)");
+    c->precision = precision;
+    return RT_OK;
+}
+
+int rt_get_precision(const rt_context* c) { return c ? c->precision : RT_PRECISION_EXACT; }
+
 int rt_get_camera(const rt_context* c, rt_camera* cam) {
     if (!c || !cam) return RT_ERR_INVALID_ARGUMENT;
     *cam = c->camera;
@@ -1612,7 +1637,9 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     K.refill = c->refill > 0 ? c->refill : small ? RT_REFILL_SMALL : RT_REFILL;
     // deep paths: the sorted kernel's record stack in global memory (launch policy)
     K.rec = nullptr;
-    if (!c->simple && (c->grec == 1 || (c->grec < 0 && rt_render_wants_global_records(K, c->num_cus)))) {
+    const bool fast = c->precision == RT_PRECISION_REFERENCE_FAST;
+    if (!c->simple && (c->grec == 1 || (c->grec < 0 && (fast ? rt_fast::rt_render_wants_global_records(K, c->num_cus)
+                                                             : rt_render_wants_global_records(K, c->num_cus))))) {
         const int rc = ensure_buf(c, c->rec, rt_render_rec_floats(K) * sizeof(float));
         if (rc) return rc;
         K.rec = (float*)c->rec.p;
@@ -1664,7 +1691,8 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     // with kernel timing on, and one end event that serves both the ordering
     // of later calls (ev_render) and the timing
     if (c->ktiming) HIP_TRY(c, hipEventRecord(c->ev0, s));
-    hipError_t e = rt_launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread);
+    hipError_t e = fast ? rt_fast::rt_launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread)
+                        : rt_launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread);
     if (e == hipSuccess && rt_order_groups_last > 0) c->order_n = rt_order_groups_last;
     c->kernel_name = rt_launched_kernel;
     c->launches++;

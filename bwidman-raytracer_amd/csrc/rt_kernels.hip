@@ -28,7 +28,8 @@
 //    through scalar loads (SGPR operands of the VALU tests), not VGPRs;
 //  * every float op is one IEEE rounding in reference order (built with
 //    -ffp-contract=off; correctly rounded div/sqrt); no MFMA (branchy
-//    per-ray math, not a contraction).
+//    per-ray math, not a contraction).  The opt-in reference-fast units
+//    ("Precision modes" below) trade that for the reference's own fast-math.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -37,6 +38,30 @@
 #include "rt_diag.h"
 #include "rt_layout.h"
 #include "rt_path.h"
+
+// Precision modes.  This file is compiled four times: the exact brute-force
+// and BVH translation units (rt_kernels.hip, rt_kernels_bvh.hip: RT_TU_BVH)
+// and their reference-fast twins (rt_kernels_fast.hip,
+// rt_kernels_bvh_fast.hip: RT_FAST, built with -ffp-contract=fast; rt_path.h
+// has the arithmetic).  The render kernels are templates: the same
+// instantiation from an exact and a fast unit would be one weak symbol with
+// two bodies, and the linker would keep either.  So the fast units put
+// every render kernel and its launchers into namespace rt_fast; the exact
+// units keep them at global scope, their symbols and code unchanged.
+// RT_TU_SHARED: the float-free kernels (RNG seeding, launch order, row
+// de-interleave) and the mode-independent host helpers, defined once.
+#ifdef RT_FAST
+#define RT_MODE_BEGIN namespace rt_fast {
+#define RT_MODE_END }
+#define RT_MODE_TAG ",fast"
+#else
+#define RT_MODE_BEGIN
+#define RT_MODE_END
+#define RT_MODE_TAG ""
+#endif
+#if !defined(RT_TU_BVH) && !defined(RT_FAST)
+#define RT_TU_SHARED
+#endif
 
 namespace {
 // ---- BVH closest hit (wave-synchronous walk; rt_path.h has the pieces) ----
@@ -281,6 +306,7 @@ __device__ __forceinline__ int prim_key(const rt_kparams& K, int id) {
 #define RT_PAIR_WAVES 7
 #endif
 
+RT_MODE_BEGIN
 template <int BLOCK, bool HIT_LDS, bool BVH>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PER_EU)))
 rt_render_kernel(rt_kparams K) {
@@ -352,11 +378,11 @@ rt_render_kernel(rt_kparams K) {
                     // genMicrofacetNormal (Main.cu:170-185)
                     const float e1 = rand_range(px.rs, 1.0f);
                     const float e2 = rand_range(px.rs, 1.0f);
-                    const float theta = atan_nn(rough * sqrt_cr(e1) / sqrt_cr(1.0f - e1));
+                    const float theta = atan_nn(rt_div(rough * rt_sqrt(e1), rt_sqrt(1.0f - e1)));
                     const float phi = 2.0f * RT_PI * e2;
                     float st, ct, sp, cp;
-                    sincos_nn(theta, st, ct);
-                    sincos_nn(phi, sp, cp);
+                    rt_sincos(theta, st, ct);
+                    rt_sincos(phi, sp, cp);
                     const f3 mloc = mk(st * cp, st * sp, ct);
                     // baseAroundNormalToRegular (Main.cu:149-168)
                     f3 some = mk(1.0f, 0.0f, 0.0f);
@@ -369,7 +395,7 @@ rt_render_kernel(rt_kparams K) {
                     const f3 inc = scale(-1.0f, d);
                     const float fr = fresnel(inc, m, ior2m1);
                     const float sw = specular_weight(inc, scatter, n, m, rough2);
-                    kspec = sw * fr / RT_SPECULAR_CHANCE;  // brdf = (s*F/0.5) * {1,1,1}
+                    kspec = rt_div_spec_chance(sw * fr);  // brdf = (s*F/0.5) * {1,1,1}
                     code = ~id;
                 } else {
                     scatter = random_direction(px.rs, n);  // brdf = 4 * albedo
@@ -397,7 +423,7 @@ rt_render_kernel(rt_kparams K) {
                     continue;
                 }
                 if (K.spp_inner != 1) {  // pixel /= samplesPerPixel: (1.0f / k) * pixel
-                    const float k = 1.0f / (float)K.spp_inner;
+                    const float k = rt_div(1.0f, (float)K.spp_inner);
                     lx = k * lx;
                     ly = k * ly;
                     lz = k * lz;
@@ -422,8 +448,9 @@ rt_render_kernel(rt_kparams K) {
         }
     }
 }
+RT_MODE_END
 
-#ifndef RT_TU_BVH  // defined once, in the main translation unit
+#ifdef RT_TU_SHARED  // defined once, in the main translation unit
 // initializeRand (Main.cu:369-380): curand_init(y*W + x, 0, 0)
 // Launch-order feedback: one workgroup turns the last launch's tile-group
 // durations into the next launch's order, most expensive first (longest
@@ -504,9 +531,7 @@ __global__ void __launch_bounds__(256) rt_deinterleave_kernel(const unsigned* __
         reinterpret_cast<word*>(image)[q] = reinterpret_cast<const word*>(gathered)[((long)r * rows_per_shard + j) * wv + x];
     }
 }
-#endif  // RT_TU_BVH
-
-
+#endif  // RT_TU_SHARED
 
 enum { T_NONE = 0, T_REGEN = 1, T_DIFF = 2, T_SPEC = 3 };  // a lane's next task
 
@@ -535,6 +560,7 @@ enum { T_NONE = 0, T_REGEN = 1, T_DIFF = 2, T_SPEC = 3 };  // a lane's next task
 //      [task slots 13 x BLOCK, field-major][2 x 2 queue counters]
 // GREC: the record levels >= RT_GREC_LDS_LEVELS in global memory (deep paths
 // and full frames, launch policy).  BVH scenes take the ray-refill kernel.
+RT_MODE_BEGIN
 template <int BLOCK, bool HIT_LDS, bool GREC, bool ORDER = false, bool QUADS = true>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(GREC ? RT_GREC_WAVES : RT_WAVES_PER_EU)))
 rt_render_sorted_kernel(rt_kparams K) {
@@ -1144,6 +1170,7 @@ rt_render_pair_kernel(rt_kparams K) {
     }
     diag_group_end<true>(K);
 }
+RT_MODE_END
 
 #ifdef RT_TU_BVH
 // ---- BVH kernel with ray refill (large scenes) --------------------------------
@@ -1186,6 +1213,7 @@ __device__ __forceinline__ float h2f(unsigned bits) {
 #ifndef RT_NODE_PAIR
 #define RT_NODE_PAIR 1
 #endif
+RT_MODE_BEGIN
 template <int BLOCK, bool N16, bool ORDER = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(RT_REFILL_WAVES)))
 rt_render_bvh_refill_kernel(rt_kparams K) {
@@ -1435,6 +1463,7 @@ rt_render_bvh_refill_kernel(rt_kparams K) {
     dg.flush(K);
 #undef NODE_LIVE
 }
+RT_MODE_END
 #endif  // RT_TU_BVH
 
 // ---- launchers (host side) ------------------------------------------------
@@ -1452,7 +1481,10 @@ extern thread_local long rt_order_groups_last;
 // the render kernel the last launch on this thread took (rt_last_kernel_name)
 extern thread_local char rt_launched_kernel[96];
 hipError_t rt_launch_order_groups(const unsigned* cost, int* order, long n, hipStream_t stream);
+size_t rt_render_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool sorted);
+size_t rt_pair_lds_bytes(const rt_kparams& K);
 
+RT_MODE_BEGIN
 namespace {
 // render kernels: one path per lane (A/B reference, samplesPerPixel > 1),
 // the sorted task-queue kernel (full frames), the pair kernel (small frames
@@ -1534,10 +1566,10 @@ hipError_t launch_render(const rt_kparams& K0, size_t lds, int grid_mult, int nu
         else
             launch_kind<KIND, BLOCK, HIT_LDS, GREC, false, false>(K, grid, lds, stream);
     }
-    std::snprintf(rt_launched_kernel, sizeof rt_launched_kernel, "%s<%d%s%s%s>%s",
+    std::snprintf(rt_launched_kernel, sizeof rt_launched_kernel, "%s<%d%s%s%s%s>%s",
                   KIND == K_PAIR ? "rt_render_pair_kernel" : KIND == K_SORTED ? "rt_render_sorted_kernel" : "rt_render_kernel",
                   KIND == K_PAIR ? 128 : BLOCK, HIT_LDS ? "" : ",hit_global", GREC ? ",grec" : "", BVH ? ",bvh" : "",
-                  feedback ? "+order" : "");
+                  RT_MODE_TAG, feedback ? "+order" : "");
     hipError_t e = hipGetLastError();
     // the sort runs when asked, and always for a grid without an order yet
     if (e == hipSuccess && feedback && (K0.order_sort || K0.order_n != grid)) {
@@ -1586,8 +1618,8 @@ hipError_t rt_launch_render_bvh_refill(const rt_kparams& K0, int num_cus, hipStr
         hipLaunchKernelGGL((rt_render_bvh_refill_kernel<BLOCK, true>), dim3((unsigned)grid), dim3(BLOCK), lds, s, K);
     else
         hipLaunchKernelGGL((rt_render_bvh_refill_kernel<BLOCK, false>), dim3((unsigned)grid), dim3(BLOCK), lds, s, K);
-    std::snprintf(rt_launched_kernel, sizeof rt_launched_kernel, "rt_render_bvh_refill_kernel<64%s>%s",
-                  n16 ? ",n16" : "", feedback ? "+order" : "");
+    std::snprintf(rt_launched_kernel, sizeof rt_launched_kernel, "rt_render_bvh_refill_kernel<64%s%s>%s",
+                  n16 ? ",n16" : "", RT_MODE_TAG, feedback ? "+order" : "");
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && feedback && (K0.order_sort || K0.order_n != grid)) {
         e = rt_launch_order_groups(K0.group_cost, K0.group_order, grid, s);
@@ -1603,18 +1635,11 @@ hipError_t rt_launch_render_bvh_simple(const rt_kparams& K, int block, size_t ld
     return block == 64 ? launch_render<K_SIMPLE, 64, false, true>(K, lds, grid_mult, num_cus, s)
                        : launch_render<K_SIMPLE, 256, false, true>(K, lds, grid_mult, num_cus, s);
 }
+RT_MODE_END
 #else
 hipError_t rt_launch_render_bvh_simple(const rt_kparams& K, int block, size_t lds, int grid_mult, int num_cus,
                                        hipStream_t s);
 hipError_t rt_launch_render_bvh_refill(const rt_kparams& K, int num_cus, hipStream_t s);
-
-size_t rt_render_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool sorted);
-// LDS bytes of one pair-kernel group (hit table in LDS)
-size_t rt_pair_lds_bytes(const rt_kparams& K) {
-    const int n_prim = K.n_sph + K.n_pln + K.n_tri + K.n_quad;
-    return (size_t)((n_prim * RT_HIT_FLOATS + 3) & ~3) * sizeof(float) +
-           (size_t)(3 * (K.max_bounces > 0 ? K.max_bounces : 0) + RT_PAIR_FIELDS) * 64 * sizeof(float) + 4 * sizeof(int);
-}
 
 namespace {
 template <int BLOCK, int KIND>
@@ -1670,6 +1695,15 @@ bool rt_render_wants_global_records(const rt_kparams& K, int num_cus) {
     const double gens = (double)((long)K.rows * K.width) / (256.0 * occ_g * (num_cus > 0 ? num_cus : 1));
     return gens >= RT_GREC_MIN_GEN;
 }
+RT_MODE_END
+
+#ifdef RT_TU_SHARED
+// LDS bytes of one pair-kernel group (hit table in LDS)
+size_t rt_pair_lds_bytes(const rt_kparams& K) {
+    const int n_prim = K.n_sph + K.n_pln + K.n_tri + K.n_quad;
+    return (size_t)((n_prim * RT_HIT_FLOATS + 3) & ~3) * sizeof(float) +
+           (size_t)(3 * (K.max_bounces > 0 ? K.max_bounces : 0) + RT_PAIR_FIELDS) * 64 * sizeof(float) + 4 * sizeof(int);
+}
 
 // Floats of a global-memory record stack for one launch: 3 dwords per level
 // kept in global memory (levels RT_GREC_LDS_LEVELS .. max_bounces-1; the
@@ -1695,6 +1729,7 @@ size_t rt_render_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool so
     if (sorted) b += (size_t)13 * block * sizeof(float) + 8 * sizeof(int);  // + queue counters
     return b;
 }
+#endif  // RT_TU_SHARED
 
 // Host-side launch policy: BVH scenes take the ray-refill kernel; otherwise
 // 256-lane workgroups (64 when the record stack of very deep paths would not
@@ -1714,6 +1749,7 @@ size_t rt_render_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool so
 #ifndef RT_PAIR_MIN_CHAIN
 #define RT_PAIR_MIN_CHAIN 8
 #endif
+RT_MODE_BEGIN
 hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, bool simple, int block_req,
                             hipStream_t stream, int pair_req) {
     // samplesPerPixel > 1 (the reference's in-frame loop, off by default):
@@ -1775,7 +1811,9 @@ hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, boo
     }
     return launch_block<RT_SORTED_BLOCK, K_SORTED>(K, hit_lds, lds_s, grid_mult, num_cus, stream);
 }
+RT_MODE_END
 
+#ifdef RT_TU_SHARED
 thread_local long rt_order_groups_last = 0;
 thread_local char rt_launched_kernel[96] = "";
 
@@ -1808,4 +1846,5 @@ hipError_t rt_launch_deinterleave(const unsigned* gathered, unsigned* image, int
                            width, height, shards, rows_per_shard);
     return hipGetLastError();
 }
+#endif  // RT_TU_SHARED
 #endif  // RT_TU_BVH

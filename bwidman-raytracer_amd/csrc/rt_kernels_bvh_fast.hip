@@ -1,0 +1,6 @@
+// rt_kernels_bvh_fast.hip — the reference-fast BVH instantiations
+// (rt_fast::rt_launch_render_bvh_*): rt_kernels_bvh.hip's flags plus
+// -ffp-contract=fast (see rt_kernels_fast.hip).
+#define RT_FAST
+#define RT_TU_BVH
+#include "rt_kernels.hip"

@@ -25,6 +25,17 @@
 //   rt_xor3  a ^ b ^ c: one gfx950 v_bitop3_b32 on the device;
 // plus the address space of wave-uniform scene reads (scalar loads through
 // the constant address space on the device, plain pointers on the host).
+//
+// Reference-fast precision mode (RT_FAST translation units, device pass
+// only, built with -ffp-contract=fast): what the reference's own
+// --use_fast_math build computes.  rt_sqrt / rt_rcp / rt_inv_len are one
+// v_sqrt_f32 / v_rcp_f32 / v_rsq_f32, every division of the per-ray path is
+// rt_div(x, y) = x * rcp(y), rt_sincos is v_sin_f32 / v_cos_f32, and the
+// compiler may contract a * b + c.  Kept as in the exact mode: the isnan
+// guard of specular_weight, fminf / fmaxf, NaN -> 0 in to_u8, atan_nn's
+// polynomial, the integer RNG and the denormal mode.  The host pass and the
+// exact translation units compile exactly what they did before the mode
+// existed (rt_div is a plain division there).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,11 +46,19 @@
 
 #define RT_HD __host__ __device__ __forceinline__
 
+#if defined(RT_FAST) && defined(__HIP_DEVICE_COMPILE__)
+#define RT_FAST_DEVICE 1
+#else
+#define RT_FAST_DEVICE 0
+#endif
+
 namespace {
 
 // ---- target primitives ----------------------------------------------------
 RT_HD float rt_sqrt(float x) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if RT_FAST_DEVICE
+    return sqrt_hw(x);
+#elif defined(__HIP_DEVICE_COMPILE__)
     return sqrt_cr(x);
 #else
     return sqrtf(x);
@@ -47,7 +66,9 @@ RT_HD float rt_sqrt(float x) {
 }
 
 RT_HD float rt_rcp(float x) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if RT_FAST_DEVICE
+    return rcp_hw(x);
+#elif defined(__HIP_DEVICE_COMPILE__)
     return rcp_cr(x);
 #else
     return 1.0f / x;
@@ -56,10 +77,30 @@ RT_HD float rt_rcp(float x) {
 
 // 1 / length as the reference's normalize computes it: RN(1 / RN(sqrt(s)))
 RT_HD float rt_inv_len(float s) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if RT_FAST_DEVICE
+    return inv_length_hw(s);
+#elif defined(__HIP_DEVICE_COMPILE__)
     return inv_length_cr(s);
 #else
     return 1.0f / sqrtf(s);
+#endif
+}
+
+// x / y: the correctly rounded quotient; reference-fast: x * rcp(y)
+RT_HD float rt_div(float x, float y) {
+#if RT_FAST_DEVICE
+    return x * rcp_hw(y);
+#else
+    return x / y;
+#endif
+}
+
+// x / specularChance (Main.cu:255); reference-fast: a constant multiply
+RT_HD float rt_div_spec_chance(float x) {
+#if RT_FAST_DEVICE
+    return x * (1.0f / RT_SPECULAR_CHANCE);
+#else
+    return x / RT_SPECULAR_CHANCE;
 #endif
 }
 
@@ -251,6 +292,17 @@ RT_HD void sincos_nn(float x, float& s, float& c) {
     c = cneg ? -cv : cv;
 }
 
+// sin and cos of a BRDF angle (theta, phi: both in [0, 2 pi))
+RT_HD void rt_sincos(float x, float& s, float& c) {
+#if RT_FAST_DEVICE
+    sincos_hw(x, s, c);
+#else
+    sincos_nn(x, s, c);
+#endif
+}
+
+// (reference-fast keeps the polynomial: the reference's fast-math has no
+// fast atanf; only the division and the contraction change)
 RT_HD float atan_nn(float x) {  // orc_atanf
     const bool xneg = x < 0.0f;
     if (xneg) x = -x;
@@ -260,7 +312,7 @@ RT_HD float atan_nn(float x) {  // orc_atanf
         x = -rt_rcp(x);
     } else if (x > 0.4142135623730950f) {
         y = 0.7853981633974483f;
-        x = (x - 1.0f) / (x + 1.0f);
+        x = rt_div(x - 1.0f, x + 1.0f);
     } else {
         y = 0.0f;
     }
@@ -284,7 +336,7 @@ RT_HD float atan_nn(float x) {  // orc_atanf
 RT_HD float shadowing_masking(f3 dir, f3 n, f3 m, float rough2) {
     float vdn = dot(dir, n);
     float tan_theta = fmaxf(rt_rcp(vdn * vdn) - 1.0f, 0.0f);
-    return chi(dot(dir, m) / vdn) * 2.0f / (1.0f + rt_sqrt(1.0f + rough2 * tan_theta * tan_theta));
+    return rt_div(chi(rt_div(dot(dir, m), vdn)) * 2.0f, 1.0f + rt_sqrt(1.0f + rough2 * tan_theta * tan_theta));
 }
 
 // fresnel(i, m, 1, ior) with ior2m1 = ior*ior/(1*1) - 1 precomputed
@@ -293,7 +345,8 @@ RT_HD float fresnel(f3 incident, f3 normal, float ior2m1) {
     float g_root = ior2m1 + c * c;
     if (g_root < 0.0f) return 1.0f;
     float g = rt_sqrt(g_root);
-    return 0.5f * square(g - c) / square(g + c) * (1.0f + square(c * (g + c) - 1.0f) / square(c * (g - c) + 1.0f));
+    return rt_div(0.5f * square(g - c), square(g + c)) *
+           (1.0f + rt_div(square(c * (g + c) - 1.0f), square(c * (g - c) + 1.0f)));
 }
 
 RT_HD float specular_weight(f3 i, f3 o, f3 n, f3 m, float rough2) {
@@ -301,7 +354,7 @@ RT_HD float specular_weight(f3 i, f3 o, f3 n, f3 m, float rough2) {
     if (isnan(g)) return 1.0f;
     float den = fabsf(dot(i, n) * dot(m, n));
     if (den == 0.0f) den = RT_NEAR_ZERO;
-    return fabsf(dot(i, m)) * g / den;
+    return rt_div(fabsf(dot(i, m)) * g, den);
 }
 
 // genRandomDirection (Main.cu:193-206): rejection-sampled ball point,
@@ -331,11 +384,11 @@ RT_HD f3 random_direction(Xorwow& s, f3 normal, int* iters = nullptr) {
 RT_HD f3 specular_scatter(Xorwow& rs, f3 d, f3 n, float rough, float rough2, float ior2m1, float& kspec) {
     const float e1 = rand_range(rs, 1.0f);
     const float e2 = rand_range(rs, 1.0f);
-    const float theta = atan_nn(rough * rt_sqrt(e1) / rt_sqrt(1.0f - e1));
+    const float theta = atan_nn(rt_div(rough * rt_sqrt(e1), rt_sqrt(1.0f - e1)));
     const float phi = 2.0f * RT_PI * e2;
     float st, ct, sp, cp;
-    sincos_nn(theta, st, ct);
-    sincos_nn(phi, sp, cp);
+    rt_sincos(theta, st, ct);
+    rt_sincos(phi, sp, cp);
     const f3 mloc = mk(st * cp, st * sp, ct);
     f3 some = mk(1.0f, 0.0f, 0.0f);
     if (fabsf(dot(n, some)) < 1.0f - RT_NEAR_ZERO) some = mk(0.0f, 1.0f, 0.0f);
@@ -346,7 +399,7 @@ RT_HD f3 specular_scatter(Xorwow& rs, f3 d, f3 n, float rough, float rough2, flo
     const f3 inc = scale(-1.0f, d);
     const float fr = fresnel(inc, m, ior2m1);
     const float sw = specular_weight(inc, scatter, n, m, rough2);
-    kspec = sw * fr / RT_SPECULAR_CHANCE;
+    kspec = rt_div_spec_chance(sw * fr);
     return scatter;
 }
 
@@ -405,7 +458,7 @@ RT_HD void polygon_test(const rt_kparams& K, cfloat_ptr q, int nv, f3 o, f3 d, i
     float nx = q[0], ny = q[1], nz = q[2], dd = q[3];
     float nd = nx * d.x + ny * d.y + nz * d.z;
     if (!(fabsf(nd) < RT_NEAR_ZERO)) {
-        float t = -((nx * o.x + ny * o.y + nz * o.z) + dd) / nd;
+        float t = rt_div(-((nx * o.x + ny * o.y + nz * o.z) + dd), nd);
         // plane part (fresh planeInfo, distance = INFINITY), then the
         // polygon's own distance test (Intersection.cuh:118-122)
         bool plane_hit = !(t <= RT_NEAR_ZERO || t > INFINITY);
@@ -458,7 +511,7 @@ RT_HD void closest_hit_brute(const rt_kparams& K, f3 o, f3 d, float& best_t, int
             // i.e. t <= 0 <= nearZero, rejected by the reference as well
             if (!(disc < 0.0f) && !(b >= 0.0f && disc == disc && a2 > 0.0f)) {
                 RT_BRANCH_COUNT(K, 0);
-                float t = (-b - rt_sqrt(disc)) / a2;
+                float t = rt_div(-b - rt_sqrt(disc), a2);
                 if (!(t <= RT_NEAR_ZERO || t > best_t)) {
                     best_t = t;
                     best_id = i;
@@ -470,7 +523,7 @@ RT_HD void closest_hit_brute(const rt_kparams& K, f3 o, f3 d, float& best_t, int
             float nx = q[0], ny = q[1], nz = q[2], dd = q[3];
             float nd = nx * d.x + ny * d.y + nz * d.z;
             if (!(fabsf(nd) < RT_NEAR_ZERO)) {
-                float t = -((nx * o.x + ny * o.y + nz * o.z) + dd) / nd;
+                float t = rt_div(-((nx * o.x + ny * o.y + nz * o.z) + dd), nd);
                 if (!(t <= RT_NEAR_ZERO || t > best_t)) {
                     best_t = t;
                     best_id = pln_base + i;
@@ -539,7 +592,7 @@ RT_HD void planes_first(const rt_kparams& K, f3 o, f3 d, float& best_t, int& bes
         const cfloat_ptr q = as_const(K.pln) + RT_PLN_FLOATS * i;
         const float nd = q[0] * d.x + q[1] * d.y + q[2] * d.z;
         if (!(fabsf(nd) < RT_NEAR_ZERO)) {
-            const float t = -((q[0] * o.x + q[1] * o.y + q[2] * o.z) + q[3]) / nd;
+            const float t = rt_div(-((q[0] * o.x + q[1] * o.y + q[2] * o.z) + q[3]), nd);
             const int key = RT_KEY(1, i);
             if (key_accept(t, key, best_t, best_key)) {
                 best_t = t;
@@ -622,7 +675,7 @@ RT_HD void leaf_test(const rt_kparams& K, const float* r, f3 o, f3 d, float a2, 
         const float c = dot(xp, xp) - c1.x;
         const float disc = b * b - a4 * c;
         if (!(disc < 0.0f) && !(b >= 0.0f)) {
-            const float t = (-b - rt_sqrt(disc)) / a2;
+            const float t = rt_div(-b - rt_sqrt(disc), a2);
             if (key_accept(t, key, best_t, best_key)) {
                 best_t = t;
                 best_id = idx;
@@ -639,7 +692,7 @@ RT_HD void leaf_test(const rt_kparams& K, const float* r, f3 o, f3 d, float a2, 
         const float dd = -dot(n, v0);
         const float nd = n.x * d.x + n.y * d.y + n.z * d.z;
         if (fabsf(nd) < RT_NEAR_ZERO) return;
-        const float t = -((n.x * o.x + n.y * o.y + n.z * o.z) + dd) / nd;
+        const float t = rt_div(-((n.x * o.x + n.y * o.y + n.z * o.z) + dd), nd);
         if (!key_accept(t, key, best_t, best_key)) return;
         const f3 P = add(o, scale(t, d));
         // (the edges formed again where they are needed: fewer live registers)
@@ -660,7 +713,7 @@ RT_HD void leaf_test(const rt_kparams& K, const float* r, f3 o, f3 d, float a2, 
     }
     const float nd = c0.y * d.x + c0.z * d.y + c0.w * d.z;
     if (fabsf(nd) < RT_NEAR_ZERO) return;
-    const float t = -((c0.y * o.x + c0.z * o.y + c0.w * o.z) + c1.x) / nd;
+    const float t = rt_div(-((c0.y * o.x + c0.z * o.y + c0.w * o.z) + c1.x), nd);
     if (!key_accept(t, key, best_t, best_key)) return;
     const f3 P = add(o, scale(t, d));
     if (dot(mk(c2.x, c2.y, c2.z), sub(P, mk(c1.y, c1.z, c1.w))) < 0.0f) return;
@@ -724,7 +777,7 @@ RT_HD unsigned to_u8(float v) {
 // Main.cu:305-312: frameSum / n -> ACES (Math.cuh:253-262) -> gamma
 // (Math.cuh:249-251) -> *255 -> round -> uchar4(r, g, b, 255)
 RT_HD unsigned tone_map(float ax, float ay, float az, unsigned n) {
-    const float inv = 1.0f / (float)n;
+    const float inv = rt_div(1.0f, (float)n);
     float v[3] = {inv * ax, inv * ay, inv * az};
     unsigned px = 0xff000000u;
 #pragma unroll
@@ -732,7 +785,7 @@ RT_HD unsigned tone_map(float ax, float ay, float az, unsigned n) {
         float cc = 0.6f * v[ch];  // color *= 0.6
         float num = cc * (2.51f * cc + 0.03f);
         float den = cc * (2.43f * cc + 0.59f) + 0.14f;
-        float tm = fminf(num / den, 1.0f);  // clamp(color, 1.0f): upper only
+        float tm = fminf(rt_div(num, den), 1.0f);  // clamp(color, 1.0f): upper only
         float g = rt_sqrt(tm) * 255.0f;
         px |= to_u8(g) << (8 * ch);
     }

@@ -67,3 +67,19 @@ __device__ __forceinline__ float inv_length_cr(float s) {
     return 1.0f / sqrtf(s);
 }
 #endif
+
+// Reference-fast precision mode (RT_FAST translation units only): what the
+// reference's own --use_fast_math build computes — one hardware instruction
+// each (v_sqrt_f32, v_rcp_f32, v_rsq_f32: 1 ulp, denormals as zero), and
+// v_sin_f32 / v_cos_f32 on the angle in revolutions (|x| <= 256 turns; the
+// BRDF's angles lie in [0, 2 pi)).
+#ifdef RT_FAST
+__device__ __forceinline__ float sqrt_hw(float x) { return __builtin_amdgcn_sqrtf(x); }
+__device__ __forceinline__ float rcp_hw(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float inv_length_hw(float s) { return __builtin_amdgcn_rsqf(s); }
+__device__ __forceinline__ void sincos_hw(float x, float& s, float& c) {
+    const float turns = x * 0.15915494309189535f;  // 1 / (2 pi)
+    s = __builtin_amdgcn_sinf(turns);
+    c = __builtin_amdgcn_cosf(turns);
+}
+#endif

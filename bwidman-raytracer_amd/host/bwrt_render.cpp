@@ -9,8 +9,8 @@
 //   bwrt_render [--scene 07|01|04|04_box | --scene-file FILE] [--save-scene FILE]
 //               [--width 1920] [--height 1080] [--frames 8] [--frames-per-call 1]
 //               [--max-bounces 5] [--background r,g,b] [--spp 1] [--device 0] [--gpus 1]
-//               [--cpu [THREADS]] [--keys "W*10,W+LEFT*5,*3"] [--dt SECONDS]
-//               [--out image.png|image.ppm] [--dump-scene file.bin]
+//               [--cpu [THREADS]] [--precision exact|fast] [--keys "W*10,W+LEFT*5,*3"]
+//               [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]
 //
 // --keys: comma-separated steps KEY[+KEY...]*FRAMES (keys W A S D SPACE
 // LEFT_SHIFT LEFT RIGHT UP DOWN ESCAPE; an empty key list holds nothing);
@@ -21,7 +21,9 @@
 // host threads, 0 or omitted = all; BASELINE config 1's "scalar C++ CPU
 // path").  --spp sets samplesPerPixel (Main.cu:27; the in-frame loop keeps
 // the last of n paths, Main.cu:296-299), and "Samples:" prints
-// accumulatedFrames * samplesPerPixel like Main.cu:491.
+// accumulatedFrames * samplesPerPixel like Main.cu:491.  --precision fast
+// renders with the reference's fast-math trade-off (rt_set_precision: GPU
+// only; the default, exact, is bit-identical to the CPU fallback).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -43,8 +45,8 @@ static const char* kUsage =
     "usage: bwrt_render [--scene 07|01|04|04_box | --scene-file FILE] [--save-scene FILE]\n"
     "                   [--width 1920] [--height 1080] [--frames 8] [--frames-per-call 1]\n"
     "                   [--max-bounces 5] [--background r,g,b] [--spp 1] [--device 0] [--gpus 1]\n"
-    "                   [--cpu [THREADS]] [--keys \"W*10,W+LEFT*5,*3\"] [--dt SECONDS]\n"
-    "                   [--out image.png|image.ppm] [--dump-scene file.bin]\n";
+    "                   [--cpu [THREADS]] [--precision exact|fast] [--keys \"W*10,W+LEFT*5,*3\"]\n"
+    "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n";
 
 struct KeyStep {
     unsigned keys;
@@ -100,6 +102,7 @@ int main(int argc, char** argv) {
     std::string scene_name = "07", scene_file, save, out, dump, keys_spec;
     int width = 1920, height = 1080, frames = 8, per_call = 1, max_bounces = RT_DEFAULT_MAX_BOUNCES, device = 0;
     int gpus = 1, spp = 1, cpu_threads = -1;  // -1: GPU
+    int precision = RT_PRECISION_EXACT;
     float bg[3] = {0.0f, 0.0f, 0.0f};
     double fixed_dt = -1.0;
     for (int i = 1; i < argc; i++) {
@@ -126,6 +129,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--cpu")) {
             cpu_threads = 0;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') cpu_threads = std::atoi(argv[++i]);
+        }
+        else if (!std::strcmp(argv[i], "--precision")) {
+            const char* v = next();
+            if (!std::strcmp(v, "exact")) precision = RT_PRECISION_EXACT;
+            else if (!std::strcmp(v, "fast")) precision = RT_PRECISION_REFERENCE_FAST;
+            else {
+                std::fprintf(stderr, "unknown --precision '%s'\n%s", v, kUsage);
+                return 2;
+            }
         }
         else if (!std::strcmp(argv[i], "--keys")) keys_spec = next();
         else if (!std::strcmp(argv[i], "--dt")) fixed_dt = std::atof(next());
@@ -185,6 +197,7 @@ int main(int argc, char** argv) {
         } else if ((rc = rt_create((device + g) % ndev, &ctxs[g]))) {
             return die(ctxs[g], rc, "rt_create");
         }
+        if ((rc = rt_set_precision(ctxs[g], precision))) return die(ctxs[g], rc, "rt_set_precision");
         if ((rc = rt_set_samples_per_pixel(ctxs[g], spp))) return die(ctxs[g], rc, "rt_set_samples_per_pixel");
         if ((rc = rt_set_scene(ctxs[g], &view))) return die(ctxs[g], rc, "rt_set_scene");
         if ((rc = rt_set_max_bounces(ctxs[g], max_bounces))) return die(ctxs[g], rc, "rt_set_max_bounces");

@@ -36,12 +36,14 @@
  *  - Launch-policy overrides for tuning and diagnostics are environment
  *    variables read ONLY when the process sets BWRT_TUNING=1 (otherwise a
  *    context always takes the measured launch policy); none changes a
- *    result, only kernel choice and speed:
+ *    result, only kernel choice and speed (BWRT_PRECISION excepted: it sets
+ *    the context's initial rt_set_precision mode):
  *      at rt_create:    BWRT_KERNEL=simple, BWRT_BLOCK, BWRT_TILE, BWRT_TILE_SQ,
  *                       BWRT_GREC, BWRT_GRID_MULT, BWRT_LEAF_BATCH, BWRT_REFILL,
  *                       BWRT_SPREAD, BWRT_ORDER, BWRT_ORDER_PERIOD,
  *                       BWRT_STREAM_PRIO=0 (the context's stream at normal
- *                       instead of the highest priority), BWRT_DEINT_BLOCKS
+ *                       instead of the highest priority), BWRT_DEINT_BLOCKS,
+ *                       BWRT_PRECISION=fast|exact
  *      at rt_set_scene: BWRT_BVH_MIN, BWRT_BVH_LEAF, BWRT_BVH_CT, BWRT_BVH_SBVH,
  *                       BWRT_BVH_REFS, BWRT_BVH_ALPHA, BWRT_BVH_ORDER_MASK,
  *                       BWRT_BVH_N16, BWRT_NO_CULL, BWRT_BVH_STATS (report)
@@ -232,6 +234,25 @@ RT_API int rt_set_max_bounces(rt_context* ctx, int max_bounces);
  * effect at the next render; does not reset accumulation. */
 RT_API int rt_set_background(rt_context* ctx, float r, float g, float b);
 
+/* Arithmetic of the GPU render kernels.
+ * RT_PRECISION_EXACT (the default): every float operation is one IEEE
+ * rounding in the reference's source order; results are bit-identical to the
+ * CPU fallback and the oracle.
+ * RT_PRECISION_REFERENCE_FAST: the trade-off of the reference's own
+ * --use_fast_math build: contracted FMAs, hardware reciprocal / square root /
+ * reciprocal square root (1 ulp) with every per-ray division as x * rcp(y),
+ * and hardware sine / cosine.  Images agree with the exact mode within 1 LSB
+ * per channel on at least 99.5 % of the pixels (mean |delta| <= 0.25 LSB);
+ * the rare pixel whose path takes another branch differs arbitrarily.
+ * Per context; takes effect at the next render; resets neither the
+ * accumulation, nor the frame counter, nor the RNG streams.  An unknown value
+ * returns RT_ERR_INVALID_ARGUMENT.  A CPU context accepts EXACT only
+ * (REFERENCE_FAST: RT_ERR_UNSUPPORTED): the CPU fallback exists to be
+ * bit-identical to the exact kernels. */
+typedef enum rt_precision { RT_PRECISION_EXACT = 0, RT_PRECISION_REFERENCE_FAST = 1 } rt_precision;
+RT_API int rt_set_precision(rt_context* ctx, int precision);
+RT_API int rt_get_precision(const rt_context* ctx);
+
 /* samplesPerPixel (Main.cu:27, a compile-time constant 1 there): each
  * progressive frame traces n paths from the frame's one jittered camera ray
  * and, like the reference's loop (Main.cu:296-299, `pixel = tracePath(...)`
@@ -345,7 +366,9 @@ RT_API float rt_last_kernel_ms(rt_context* ctx);
 /* Name of the render kernel the context's last GPU render launched, with
  * its workgroup lanes and variant, e.g. "rt_render_sorted_kernel<256,grec>+order"
  * (full frames), "rt_render_pair_kernel<128>+order" (small frames and
- * shards), "rt_render_bvh_refill_kernel<64,n16>" (BVH scenes); "" before
+ * shards), "rt_render_bvh_refill_kernel<64,n16>" (BVH scenes); a
+ * RT_PRECISION_REFERENCE_FAST launch carries ",fast" inside the angle
+ * brackets, e.g. "rt_render_pair_kernel<128,fast>+order"; "" before
  * the first render and on a CPU context.  A diagnostic of the launch
  * policy (tests assert which kernel a workload runs); valid until the next
  * render on the context.  The reference launches one kernel, Main.cu:342. */
