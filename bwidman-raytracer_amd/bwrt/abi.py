@@ -77,10 +77,18 @@ class RenderParams(C.Structure):
                 ("row_offset", C.c_int), ("row_stride", C.c_int)]
 
 
+class DenoiseParams(C.Structure):
+    """rt_denoise_params: a-trous levels and the three edge-stopping sigmas."""
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_plane", C.c_float)]
+
+
 RT_OK = 0
 RT_ERR_INVALID_ARGUMENT = -1
 RT_ERR_NO_DEVICE = -2
+RT_ERR_NO_SCENE = -5
 RT_ERR_UNSUPPORTED = -6
+RT_DENOISE_MAX_ITERATIONS = 6
 RT_MAX_BOUNCES = 32
 RT_DEFAULT_MAX_BOUNCES = 5
 RT_PRECISION_EXACT = 0
@@ -128,6 +136,11 @@ def _proto(lib):
                                                   C.c_int, vp]),
         "rt_get_state": (C.c_int, [vp, vp, vp]),
         "rt_set_state": (C.c_int, [vp, vp, vp, C.c_uint]),
+        "rt_render_aov": (C.c_int, [vp, P(RenderParams), vp, vp, vp, vp]),
+        "rt_denoise_params_default": (DenoiseParams, []),
+        "rt_denoise": (C.c_int, [vp, P(DenoiseParams), vp, vp]),
+        "rt_denoise_device": (C.c_int, [vp, P(DenoiseParams), vp, vp]),
+        "rt_last_denoise_ms": (C.c_float, [vp]),
         "rt_error_string": (C.c_char_p, [C.c_int]),
         "rt_last_error": (C.c_char_p, [vp]),
         "rt_last_kernel_name": (C.c_char_p, [vp]),

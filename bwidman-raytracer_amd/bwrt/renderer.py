@@ -189,6 +189,51 @@ class Renderer:
                                                          height, shards, rows_per_shard,
                                                          stream_ptr))
 
+    # -- first-hit features and the denoiser --------------------------------
+    def render_aov(self, width, height, row_offset=0, row_stride=1):
+        """rt_render_aov: the first-hit feature buffers of a shard as a dict of
+        arrays: "albedo", "normal" (rows, width, 3) float32, "depth" (rows,
+        width) float32 (+inf on a miss), "prim" (rows, width) int32 (-1)."""
+        rows = self.lib.rt_shard_rows(height, row_offset, row_stride)
+        out = {"albedo": np.empty((rows, width, 3), np.float32), "normal": np.empty((rows, width, 3), np.float32),
+               "depth": np.empty((rows, width), np.float32), "prim": np.empty((rows, width), np.int32)}
+        p = self.params(width, height, 1, 0, 0, row_offset, row_stride)
+        self._check(self.lib.rt_render_aov(self.ctx, C.byref(p), out["albedo"].ctypes.data,
+                                           out["normal"].ctypes.data, out["depth"].ctypes.data,
+                                           out["prim"].ctypes.data))
+        return out
+
+    def denoise_params(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None):
+        """rt_denoise_params_default() with the given fields replaced."""
+        d = self.lib.rt_denoise_params_default()
+        for name, v in (("iterations", iterations), ("sigma_color", sigma_color),
+                        ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane)):
+            if v is not None:
+                setattr(d, name, v)
+        return d
+
+    def denoise(self, width, height, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None,
+                want_color=False):
+        """rt_denoise: the a-trous filter over the accumulated full frame
+        (width x height: the shape of the last render).  Returns the RGBA8
+        image, with want_color also the filtered linear colour (H, W, 3)."""
+        d = self.denoise_params(iterations, sigma_color, sigma_normal, sigma_plane)
+        out = np.empty((height, width, 4), np.uint8)
+        col = np.empty((height, width, 3), np.float32) if want_color else None
+        self._check(self.lib.rt_denoise(self.ctx, C.byref(d), out.ctypes.data,
+                                        col.ctypes.data if col is not None else None))
+        return (out, col) if want_color else out
+
+    def denoise_device(self, rgba_ptr: int, stream_ptr: int | None = None, iterations=None, sigma_color=None,
+                       sigma_normal=None, sigma_plane=None):
+        """rt_denoise_device: the filtered RGBA8 into device memory on a stream
+        (asynchronous; ordered after the last render on the device)."""
+        d = self.denoise_params(iterations, sigma_color, sigma_normal, sigma_plane)
+        self._check(self.lib.rt_denoise_device(self.ctx, C.byref(d), rgba_ptr, stream_ptr))
+
+    def last_denoise_ms(self) -> float:
+        return self.lib.rt_last_denoise_ms(self.ctx)
+
     # -- checkpoint / resume -----------------------------------------------
     def get_state(self, rows, width):
         rng = np.empty((6, rows, width), dtype=np.uint32)

@@ -48,6 +48,13 @@ hipError_t rt_launch_deinterleave(const unsigned* gathered, unsigned* image, int
 int rt_cpu_render(const rt_kparams& K, int threads);
 void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride);
 bool rt_cpu_supported();
+void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb);
+void rt_cpu_denoise_level(const rt_dn_level& L, int threads);
+// first-hit feature kernel (rt_kernels.hip; the BVH walk in rt_kernels_bvh.hip) and the
+// a-trous filter (rt_denoise.hip)
+hipError_t rt_launch_aov(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream);
+hipError_t rt_launch_aov_bvh(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream);
+hipError_t rt_launch_denoise_level(const rt_dn_level& L, bool tiled, hipStream_t stream);
 
 static_assert(sizeof(rt_vec3) == 12, "vec3d layout (Math.cuh:35-39)");
 static_assert(sizeof(rt_material) == 24, "material layout (WorldTypes.cuh:15-20)");
@@ -168,6 +175,22 @@ struct rt_context {
     unsigned frame = 1;
     int max_bounces = RT_DEFAULT_MAX_BOUNCES;
     int spp_inner = 1;  // samplesPerPixel, Main.cu:27
+
+    // denoiser (rt_denoise): the first-hit guides of the current full frame
+    // {n.xyz, prim} / {P.xyz, depth}, valid until the scene, the camera or the
+    // frame shape changes, and two ping-pong colour buffers
+    DevBuf guide_a, guide_b, dn_col[2], dn_rgba;
+    DevBuf aov_a, aov_b, aov_alb;  // rt_render_aov scratch (any shard)
+    std::vector<float4> guide_a_h, guide_b_h, dn_col_h[2];
+    bool guides_valid = false;
+    // start / end of the last rt_denoise's levels on dn_stream: timing, and the
+    // next render or state write is ordered after the end (the filter reads frameSum)
+    hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;
+    hipStream_t dn_stream = nullptr;
+    bool dn_recorded = false;
+    float dn_cpu_ms = -1.0f;
+    bool dn_timed = false;
+    int dn_kernel = -1;  // BWRT_DENOISE_KERNEL: 0 direct, 1 tiled, -1 = the measured per-level policy
 };
 
 namespace {
@@ -241,6 +264,7 @@ void free_buf(DevBuf& b) {
 int quiesce(rt_context* c) {
     if (c->cpu) return RT_OK;
     HIP_TRY(c, flush_render(c));
+    if (c->dn_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_dn1));  // a denoise still reading frameSum
     if (!c->render_recorded) return RT_OK;
     HIP_TRY(c, hipEventSynchronize(c->ev_render));
     return RT_OK;
@@ -270,19 +294,19 @@ void put_material(float* h, const rt_material& m) {
     h[4] = m.emittance * m.albedo.x;
     h[5] = m.emittance * m.albedo.y;
     h[6] = m.emittance * m.albedo.z;
-    h[7] = 0.0f;
+    h[7] = m.albedo.x;  // slots 7, 11, 15: the raw albedo (aov_shade; no render kernel reads these lanes)
     h[8] = m.roughness;
     // fresnel(): square(ior)/square(1.0f) - 1.0f (Main.cu:125)
     h[9] = (m.refractive_index * m.refractive_index) / (1.0f * 1.0f) - 1.0f;
     h[10] = m.roughness * m.roughness;  // Main.cu:119 evaluates roughness*roughness first
-    h[11] = 0.0f;
+    h[11] = m.albedo.y;
     // diffuse brdf = 2 / (1 - specularChance) * albedo (Main.cu:259): the
     // double constant narrows to 4.0f; scaling by 4 is exact
     const float dk = (float)(2.0 / (1 - 0.5f));
     h[12] = dk * m.albedo.x;
     h[13] = dk * m.albedo.y;
     h[14] = dk * m.albedo.z;
-    h[15] = 0.0f;
+    h[15] = m.albedo.z;
 }
 
 // Triangle / quad record: {n, d, v0, in0, v1, in1, ...}; Intersection.cuh:109-127
@@ -871,7 +895,7 @@ struct BvhBuilder {
 
 extern "C" {
 
-const char* rt_version(void) { return "0.2.0"; }
+const char* rt_version(void) { return "0.3.0"; }
 
 rt_material rt_material_default(void) {
     rt_material m;
@@ -910,7 +934,8 @@ int rt_create(int device, rt_context** out) {
         (high ? hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi)
               : hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev_render) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_aux, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&c->ev_aux, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreate(&c->ev_dn0) != hipSuccess || hipEventCreate(&c->ev_dn1) != hipSuccess) {
         rt_destroy(c);
         return RT_ERR_HIP;
     }
@@ -932,6 +957,8 @@ int rt_create(int device, rt_context** out) {
     if (const char* g = tuning_env("BWRT_SPREAD")) c->spread = std::atoi(g) ? 1 : 0;
     if (const char* g = tuning_env("BWRT_ORDER")) c->order_feedback = std::atoi(g) != 0;
     if (const char* g = tuning_env("BWRT_ORDER_PERIOD")) c->order_period = std::max(std::atoi(g), 1);
+    if (const char* g = tuning_env("BWRT_DENOISE_KERNEL"))
+        c->dn_kernel = std::strcmp(g, "tiled") == 0 ? 1 : std::strcmp(g, "direct") == 0 ? 0 : -1;
     if (const char* g = tuning_env("BWRT_PRECISION"))
         c->precision = std::strcmp(g, "fast") == 0 ? RT_PRECISION_REFERENCE_FAST : RT_PRECISION_EXACT;
     *out = c;
@@ -986,6 +1013,12 @@ void rt_destroy(rt_context* c) {
     c->render_pending = false;  // its launch is done: the stream is synchronised
     if (c->render_recorded) (void)hipEventSynchronize(c->ev_render);
     if (c->aux_recorded) (void)hipEventSynchronize(c->ev_aux);
+    if (c->dn_recorded) (void)hipEventSynchronize(c->ev_dn1);
+    for (DevBuf* b : {&c->guide_a, &c->guide_b, &c->dn_col[0], &c->dn_col[1], &c->dn_rgba, &c->aov_a, &c->aov_b,
+                      &c->aov_alb})
+        free_buf(*b);
+    if (c->ev_dn0) (void)hipEventDestroy(c->ev_dn0);
+    if (c->ev_dn1) (void)hipEventDestroy(c->ev_dn1);
     free_buf(c->scene_buf);
     free_buf(c->rng);
     free_buf(c->accum);
@@ -1314,6 +1347,7 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
     c->has_scene = true;
     c->frame = 1;
     c->order_stale = true;
+    c->guides_valid = false;
     return RT_OK;
 }
 
@@ -1322,6 +1356,7 @@ int rt_set_camera(rt_context* c, const rt_camera* cam) {
     c->camera = *cam;
     c->frame = 1;  // Controls.cuh: any movement sets accumulatedFrames = 1
     c->order_stale = true;
+    c->guides_valid = false;
     return RT_OK;
 }
 
@@ -1428,6 +1463,7 @@ int rt_controls(rt_context* c, unsigned keys, float dt) {
     if (flags > 0 && (flags & RT_CONTROLS_MOVED)) {
         c->frame = 1;  // accumulatedFrames = 1
         c->order_stale = true;
+        c->guides_valid = false;
     }
     return flags;
 }
@@ -1488,6 +1524,7 @@ int rt_init_rand(rt_context* c, int width, int height, int row_offset, int row_s
         }
         rt_cpu_init_rand(c->rng_h.data(), width, rows, row_offset, row_stride);
     }
+    c->guides_valid = false;  // the guides are those of one frame shape
     if (c->cpu) {
         c->width = width;
         c->height = height;
@@ -1515,6 +1552,8 @@ int rt_init_rand(rt_context* c, int width, int height, int row_offset, int row_s
     return RT_OK;
 }
 
+static void fill_view(rt_context* c, int width, int height, int row_offset, int stride, int rows, rt_kparams& K);
+
 static int prepare(rt_context* c, const rt_render_params* p, rt_kparams& K, unsigned& first) {
     const HostFpEnv fp;
     if (!c || !p) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
@@ -1537,21 +1576,30 @@ static int prepare(rt_context* c, const rt_render_params* p, rt_kparams& K, unsi
         return fail(c, RT_ERR_INVALID_ARGUMENT, "frame counter overflow");
     if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
 
-    std::memset(&K, 0, sizeof K);
-    K.width = p->width;
-    K.height = p->height;
-    K.row_offset = p->row_offset;
-    K.row_stride = stride;
-    K.rows = c->rows;
+    fill_view(c, p->width, p->height, p->row_offset, stride, c->rows, K);
     K.samples = p->samples;
     K.max_bounces = p->max_bounces;
     K.first_frame = first;
+    K.rng = c->cpu ? c->rng_h.data() : (unsigned*)c->rng.p;
+    K.accum = c->cpu ? c->accum_h.data() : (float*)c->accum.p;
+    return RT_OK;
+}
+
+// Camera prelude and compiled scene of a width x height view (shard
+// row_offset, stride, rows) into K; every other field 0
+static void fill_view(rt_context* c, int width, int height, int row_offset, int stride, int rows, rt_kparams& K) {
+    std::memset(&K, 0, sizeof K);
+    K.width = width;
+    K.height = height;
+    K.row_offset = row_offset;
+    K.row_stride = stride;
+    K.rows = rows;
     // host prelude, Main.cu:336-338
     const rt_camera& cam = c->camera;
     K.cam_pos[0] = cam.position.x;
     K.cam_pos[1] = cam.position.y;
     K.cam_pos[2] = cam.position.z;
-    K.screen_z = -(float)(p->width / 2) / tanf(cam.fov / 2.0f);
+    K.screen_z = -(float)(width / 2) / tanf(cam.fov / 2.0f);
     {
         const float cy = cosf(cam.angle[0]), sy = sinf(cam.angle[0]);  // rotationMatrix3DY
         const float cx = cosf(cam.angle[1]), sx = sinf(cam.angle[1]);  // rotationMatrix3DX
@@ -1561,7 +1609,7 @@ static int prepare(rt_context* c, const rt_render_params* p, rt_kparams& K, unsi
             for (int j = 0; j < 3; j++)  // dot(a.row(i), b.col(j)), Math.cuh:191-199
                 K.rot[3 * i + j] = L[i][0] * U[0][j] + L[i][1] * U[1][j] + L[i][2] * U[2][j];
     }
-    K.jitter = (float)(0.001 * (p->width / 1000));  // Main.cu:291
+    K.jitter = (float)(0.001 * (width / 1000));  // Main.cu:291
     K.bg[0] = c->background[0];
     K.bg[1] = c->background[1];
     K.bg[2] = c->background[2];
@@ -1593,9 +1641,6 @@ static int prepare(rt_context* c, const rt_render_params* p, rt_kparams& K, unsi
     K.ovf_im = c->ovf_im;
     K.cull_dmax = c->cull_dmax;
     K.spp_inner = c->spp_inner;
-    K.rng = c->cpu ? c->rng_h.data() : (unsigned*)c->rng.p;
-    K.accum = c->cpu ? c->accum_h.data() : (float*)c->accum.p;
-    return RT_OK;
 }
 
 // The CPU backend's render: rt_cpu.cpp over the host state, synchronous
@@ -1684,6 +1729,8 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
         HIP_TRY(c, flush_render(c));
         HIP_TRY(c, hipStreamWaitEvent(s, c->ev_render, 0));
     }
+    // ... and after a denoise of the frame on another stream (it reads frameSum)
+    if (c->dn_recorded && c->dn_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_dn1, 0));
     rt_order_groups_last = 0;
     rt_launched_kernel[0] = 0;
     // every event recorded here is a marker packet the GPU drains between two
@@ -1863,6 +1910,7 @@ int rt_synchronize(rt_context* c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->render_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_render));
     if (c->aux_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_aux));
+    if (c->dn_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_dn1));
     return RT_OK;
 }
 
@@ -1974,5 +2022,255 @@ int rt_render_cpu(rt_context* c, const rt_render_params* p, int threads, uint8_t
 }
 
 int rt_context_threads(const rt_context* c) { return c && c->cpu ? c->threads : 0; }
+
+// ---- first-hit feature buffers and the a-trous denoiser ---------------------
+// Neither reads or writes the RNG state, frameSum or the frame counter; both
+// always run the exact arithmetic (rt_set_precision selects render kernels only).
+
+int rt_render_aov(rt_context* c, const rt_render_params* p, float* albedo, float* normal, float* depth,
+                  int32_t* prim) {
+    const HostFpEnv fp;
+    if (!c || !p) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    const int stride = p->row_stride == 0 ? 1 : p->row_stride;
+    if (p->width <= 0 || p->height <= 0 || p->row_offset < 0 || stride < 0 || p->row_offset >= p->height)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "bad shard %dx%d offset %d stride %d", p->width, p->height,
+                    p->row_offset, stride);
+    if ((long long)p->width * p->height > (1ll << 31))
+        return fail(c, RT_ERR_UNSUPPORTED, "image larger than 2^31 pixels");
+    const int rows = shard_rows(p->height, p->row_offset, stride);
+    const size_t npix = (size_t)rows * p->width;
+    rt_kparams K;
+    fill_view(c, p->width, p->height, p->row_offset, stride, rows, K);
+    std::vector<float4> a, b, al;
+    try {
+        a.resize(npix);
+        b.resize(npix);
+        if (albedo) al.resize(npix);
+    } catch (...) {
+        return fail(c, RT_ERR_OUT_OF_MEMORY, "host buffers for %zu pixels", npix);
+    }
+    if (c->cpu) {
+        rt_cpu_aov(K, c->threads, a.data(), b.data(), albedo ? al.data() : nullptr);
+    } else {
+        HIP_TRY(c, hipSetDevice(c->device));
+        int rc = ensure_buf(c, c->aov_a, npix * sizeof(float4));
+        if (!rc) rc = ensure_buf(c, c->aov_b, npix * sizeof(float4));
+        if (!rc && albedo) rc = ensure_buf(c, c->aov_alb, npix * sizeof(float4));
+        if (rc) return rc;
+        float4* dal = albedo ? (float4*)c->aov_alb.p : nullptr;
+        HIP_TRY(c, K.bvh_nodes ? rt_launch_aov_bvh(K, (float4*)c->aov_a.p, (float4*)c->aov_b.p, dal, c->stream)
+                               : rt_launch_aov(K, (float4*)c->aov_a.p, (float4*)c->aov_b.p, dal, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(a.data(), c->aov_a.p, npix * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(b.data(), c->aov_b.p, npix * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        if (albedo)
+            HIP_TRY(c, hipMemcpyAsync(al.data(), dal, npix * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    for (size_t i = 0; i < npix; i++) {
+        if (albedo) {
+            albedo[3 * i + 0] = al[i].x;
+            albedo[3 * i + 1] = al[i].y;
+            albedo[3 * i + 2] = al[i].z;
+        }
+        if (normal) {
+            normal[3 * i + 0] = a[i].x;
+            normal[3 * i + 1] = a[i].y;
+            normal[3 * i + 2] = a[i].z;
+        }
+        if (depth) depth[i] = b[i].w;
+        if (prim) std::memcpy(&prim[i], &a[i].w, sizeof(int32_t));
+    }
+    return RT_OK;
+}
+
+rt_denoise_params rt_denoise_params_default(void) {
+    rt_denoise_params d;
+    d.iterations = 5;
+    // tools/denoise_sigma_sweep.py (DESIGN.md "Denoiser")
+    d.sigma_color = 16.0f;
+    d.sigma_normal = 0.5f;
+    d.sigma_plane = 0.1f;
+    return d;
+}
+
+// The guides of the context's current full frame, recomputed when stale (on
+// stream s for a GPU context: part of the denoise call that needs them)
+static int ensure_guides(rt_context* c, hipStream_t s) {
+    if (c->guides_valid) return RT_OK;
+    rt_kparams K;
+    fill_view(c, c->width, c->height, 0, 1, c->height, K);
+    const size_t npix = (size_t)c->height * c->width;
+    if (c->cpu) {
+        try {
+            c->guide_a_h.resize(npix);
+            c->guide_b_h.resize(npix);
+        } catch (...) {
+            return fail(c, RT_ERR_OUT_OF_MEMORY, "host guides for %zu pixels", npix);
+        }
+        rt_cpu_aov(K, c->threads, c->guide_a_h.data(), c->guide_b_h.data(), nullptr);
+    } else {
+        int rc = ensure_buf(c, c->guide_a, npix * sizeof(float4));
+        if (!rc) rc = ensure_buf(c, c->guide_b, npix * sizeof(float4));
+        if (rc) return rc;
+        HIP_TRY(c, K.bvh_nodes ? rt_launch_aov_bvh(K, (float4*)c->guide_a.p, (float4*)c->guide_b.p, nullptr, s)
+                               : rt_launch_aov(K, (float4*)c->guide_a.p, (float4*)c->guide_b.p, nullptr, s));
+    }
+    c->guides_valid = true;
+    return RT_OK;
+}
+
+// Every level of one denoise call; the final colour ends in dn_col[*final_buf]
+// and, tone-mapped, in rgba (device pointer on a GPU context; may be null)
+static int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_t s, unsigned* rgba, int* final_buf) {
+    const HostFpEnv fp;
+    if (!c || !dp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (dp->iterations < 0 || dp->iterations > RT_DENOISE_MAX_ITERATIONS)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "iterations %d outside 0..%d", dp->iterations,
+                    RT_DENOISE_MAX_ITERATIONS);
+    if (!(dp->sigma_color > 0.0f) || !(dp->sigma_normal > 0.0f) || !(dp->sigma_plane > 0.0f))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "sigmas must be > 0 (colour %g, normal %g, plane %g)",
+                    (double)dp->sigma_color, (double)dp->sigma_normal, (double)dp->sigma_plane);
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    if (c->frame < 2u || (c->cpu ? c->accum_h.empty() : !c->accum.p))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "no frame accumulated yet (render first)");
+    if (c->row_offset != 0 || c->row_stride > 1)
+        return fail(c, RT_ERR_UNSUPPORTED,
+                    "the context holds a row shard (offset %d, stride %d): the denoiser needs a full frame",
+                    c->row_offset, c->row_stride);
+    const size_t npix = (size_t)c->height * c->width;
+    if (!c->cpu) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        int rc = ensure_buf(c, c->dn_col[0], npix * sizeof(float4));
+        if (!rc) rc = ensure_buf(c, c->dn_col[1], npix * sizeof(float4));
+        if (rc) return rc;
+        // after the render that made the frame, and after a previous denoise
+        // (shared colour buffers and guides), whatever streams they ran on
+        if (c->render_stream && c->render_stream != s) {
+            HIP_TRY(c, flush_render(c));
+            HIP_TRY(c, hipStreamWaitEvent(s, c->ev_render, 0));
+        }
+        if (c->dn_recorded && c->dn_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_dn1, 0));
+    } else {
+        try {
+            c->dn_col_h[0].resize(npix);
+            c->dn_col_h[1].resize(npix);
+        } catch (...) {
+            return fail(c, RT_ERR_OUT_OF_MEMORY, "host colour buffers for %zu pixels", npix);
+        }
+    }
+    int rc = ensure_guides(c, s);
+    if (rc) return rc;
+    rt_dn_level L;
+    std::memset(&L, 0, sizeof L);
+    L.width = c->width;
+    L.height = c->height;
+    L.inv = 1.0f / (float)(c->frame - 1u);
+    L.in = 1.0f / (dp->sigma_normal * dp->sigma_normal);
+    L.ip = 1.0f / (dp->sigma_plane * dp->sigma_plane);
+    L.accum = c->cpu ? c->accum_h.data() : (const float*)c->accum.p;
+    L.ga = c->cpu ? c->guide_a_h.data() : (const float4*)c->guide_a.p;
+    L.gb = c->cpu ? c->guide_b_h.data() : (const float4*)c->guide_b.p;
+    float4* col[2] = {c->cpu ? c->dn_col_h[0].data() : (float4*)c->dn_col[0].p,
+                      c->cpu ? c->dn_col_h[1].data() : (float4*)c->dn_col[1].p};
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!c->cpu) HIP_TRY(c, hipEventRecord(c->ev_dn0, s));
+    const int levels = dp->iterations;
+    for (int i = 0; i < (levels > 0 ? levels : 1); i++) {
+        L.step = levels > 0 ? 1 << i : 0;  // step 0: the conversion pass of iterations == 0
+        const float sc = dp->sigma_color * std::ldexp(1.0f, -i);
+        L.ic = 1.0f / (sc * sc);
+        L.first = i == 0;
+        L.last = i >= levels - 1;
+        L.src = i > 0 ? col[(i - 1) & 1] : nullptr;
+        L.dst = col[i & 1];
+        L.rgba = L.last ? rgba : nullptr;
+        if (c->cpu) {
+            rt_cpu_denoise_level(L, c->threads);
+        } else {
+            // BWRT_DENOISE_KERNEL forces a variant; the policy is the per-level
+            // winner of tools/time_denoise.py at 1920x1080 (profiles/denoise/,
+            // DESIGN.md section 9): the LDS-tiled kernel up to step 16 (0.084-0.139
+            // against 0.17-0.19 ms), the direct one at step 32 (0.24 against 0.31
+            // ms: the tile's 108 KiB leave one workgroup per CU)
+            const bool tiled = c->dn_kernel >= 0 ? c->dn_kernel == 1 : L.step <= 16;
+            HIP_TRY(c, rt_launch_denoise_level(L, tiled, s));
+        }
+    }
+    *final_buf = levels > 0 ? (levels - 1) & 1 : 0;
+    if (c->cpu) {
+        c->dn_cpu_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    } else {
+        HIP_TRY(c, hipEventRecord(c->ev_dn1, s));
+        c->dn_stream = s;
+        c->dn_recorded = true;
+    }
+    c->dn_timed = true;
+    return RT_OK;
+}
+
+int rt_denoise(rt_context* c, const rt_denoise_params* dp, uint8_t* rgba_out, float* color_out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    const size_t npix = (size_t)c->height * c->width;
+    int fb = 0;
+    if (c->cpu) {
+        std::vector<unsigned> rgba;
+        if (rgba_out) {
+            try {
+                rgba.resize(npix);
+            } catch (...) {
+                return fail(c, RT_ERR_OUT_OF_MEMORY, "host RGBA for %zu pixels", npix);
+            }
+        }
+        const int rc = denoise_levels(c, dp, nullptr, rgba_out ? rgba.data() : nullptr, &fb);
+        if (rc) return rc;
+        if (rgba_out) std::memcpy(rgba_out, rgba.data(), npix * 4);
+        if (color_out)
+            for (size_t i = 0; i < npix; i++) {
+                color_out[3 * i + 0] = c->dn_col_h[fb][i].x;
+                color_out[3 * i + 1] = c->dn_col_h[fb][i].y;
+                color_out[3 * i + 2] = c->dn_col_h[fb][i].z;
+            }
+        return RT_OK;
+    }
+    if (rgba_out) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        const int rc = ensure_buf(c, c->dn_rgba, npix * 4);
+        if (rc) return rc;
+    }
+    const int rc = denoise_levels(c, dp, c->stream, rgba_out ? (unsigned*)c->dn_rgba.p : nullptr, &fb);
+    if (rc) return rc;
+    if (rgba_out) HIP_TRY(c, hipMemcpyAsync(rgba_out, c->dn_rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    if (color_out) {
+        std::vector<float4> col(npix);
+        HIP_TRY(c, hipMemcpyAsync(col.data(), c->dn_col[fb].p, npix * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < npix; i++) {
+            color_out[3 * i + 0] = col[i].x;
+            color_out[3 * i + 1] = col[i].y;
+            color_out[3 * i + 2] = col[i].z;
+        }
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
+int rt_denoise_device(rt_context* c, const rt_denoise_params* dp, void* rgba_device, void* stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_denoise_device: CPU context");
+    if (rgba_device && ((uintptr_t)rgba_device & 3u))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
+    int fb = 0;
+    return denoise_levels(c, dp, stream ? (hipStream_t)stream : c->stream, (unsigned*)rgba_device, &fb);
+}
+
+float rt_last_denoise_ms(rt_context* c) {
+    if (!c || !c->dn_timed) return -1.0f;
+    if (c->cpu) return c->dn_cpu_ms;
+    if (hipEventSynchronize(c->ev_dn1) != hipSuccess) return -1.0f;
+    float ms = -1.0f;
+    if (hipEventElapsedTime(&ms, c->ev_dn0, c->ev_dn1) != hipSuccess) return -1.0f;
+    return ms;
+}
 
 }  // extern "C"

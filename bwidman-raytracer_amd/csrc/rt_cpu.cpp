@@ -224,3 +224,85 @@ int rt_cpu_render(const rt_kparams& K, int threads) {
     for (std::thread& t : pool) t.join();
     return (int)pool.size() + 1;
 }
+
+// ---- first-hit features and the a-trous filter on the host -------------------
+#include "rt_denoise.h"
+
+namespace {
+
+// fn(p) for p = 0 .. n-1 in 256-item chunks on `threads` threads (the calling
+// thread works too), under the render's IEEE float state; returns when all are
+// done (the barrier between two filter levels).  Every item writes only its own
+// outputs, so the result does not depend on the thread count.
+template <class Fn>
+void parallel_items(long n, int threads, const Fn& fn) {
+    constexpr long kChunk = 256;
+    const long chunks = (n + kChunk - 1) / kChunk;
+    if (threads < 1) threads = 1;
+    if ((long)threads > chunks) threads = (int)(chunks > 0 ? chunks : 1);
+    std::atomic<long> next(0);
+    auto work = [&]() {
+        const unsigned saved = _mm_getcsr();
+        _mm_setcsr((saved & ~(_MM_ROUND_MASK | _MM_FLUSH_ZERO_MASK | 0x0040u)) | _MM_ROUND_NEAREST);  // 0x40 = DAZ
+        for (long c = next.fetch_add(1); c < chunks; c = next.fetch_add(1)) {
+            const long end = (c + 1) * kChunk < n ? (c + 1) * kChunk : n;
+            for (long p = c * kChunk; p < end; p++) fn(p);
+        }
+        _mm_setcsr(saved);
+    };
+    std::vector<std::thread> pool;
+    pool.reserve((size_t)threads - 1);
+    for (int t = 1; t < threads; t++) {
+        try {
+            pool.emplace_back(work);
+        } catch (...) {
+            break;
+        }
+    }
+    work();
+    for (std::thread& t : pool) t.join();
+}
+
+}  // namespace
+
+// The feature buffers of the shard in K (rt_kernels.hip rt_aov_kernel): ga, gb
+// and alb as the kernel packs them (alb may be null)
+void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb) {
+    parallel_items((long)K.rows * K.width, threads, [&](long p) {
+        const int j = (int)(p / K.width);
+        const int x = (int)(p - (long)j * K.width);
+        const int y = K.row_offset + j * K.row_stride;
+        const f3 o = mk(K.cam_pos[0], K.cam_pos[1], K.cam_pos[2]);
+        const f3 d = primary_dir(K, x, y);
+        float t;
+        int id;
+        if (K.bvh_nodes)
+            closest_hit_bvh_cpu(K, o, d, t, id);
+        else
+            closest_hit_brute(K, o, d, t, id);
+        const AovHit a = aov_shade(K, o, d, t, id);
+        ga[p] = make_float4(a.n.x, a.n.y, a.n.z, rt_i2f(a.prim));
+        gb[p] = make_float4(a.P.x, a.P.y, a.P.z, a.depth);
+        if (alb) alb[p] = make_float4(a.albedo.x, a.albedo.y, a.albedo.z, 0.0f);
+    });
+}
+
+// One filter level (L.step >= 1) or, with L.step == 0, the conversion pass
+void rt_cpu_denoise_level(const rt_dn_level& L, int threads) {
+    const long npix = (long)L.width * L.height;
+    if (L.step == 0) {
+        parallel_items(npix, threads, [&](long p) { dn_store(L, p, dn_color<true>(L, p)); });
+        return;
+    }
+    parallel_items(npix, threads, [&](long p) {
+        const int y = (int)(p / L.width);
+        const int x = (int)(p - (long)y * L.width);
+        if (L.first) {
+            const DnGlobalFetch<true> fetch{L};
+            dn_store(L, p, dn_pixel(L, x, y, fetch));
+        } else {
+            const DnGlobalFetch<false> fetch{L};
+            dn_store(L, p, dn_pixel(L, x, y, fetch));
+        }
+    });
+}

@@ -1848,3 +1848,51 @@ hipError_t rt_launch_deinterleave(const unsigned* gathered, unsigned* image, int
 }
 #endif  // RT_TU_SHARED
 #endif  // RT_TU_BVH
+
+// ---- first-hit feature buffers (rt_render_aov, the denoiser's guides) -------
+// One lane per shard pixel: the closest hit of the un-jittered primary ray
+// (no RNG draw) through the renders' own routines, shaded by aov_shade
+// (rt_path.h), stored packed so that a filter tap is two 16-byte loads:
+// ga = {n.xyz, prim as bits}, gb = {P.xyz, depth}; alb = {albedo, 0} (may be
+// null).  Always the exact arithmetic: defined at global scope (outside the
+// precision-mode namespace) and instantiated once, the brute-force loop in the
+// main unit, the BVH walk in the exact BVH unit (-O3).
+// closest_hit_bvh is wave-synchronous (__all / __any): a lane past the end of
+// the shard stays in the call with a clamped pixel and only skips the stores.
+template <bool BVH>
+__global__ void __launch_bounds__(256) rt_aov_kernel(const rt_kparams K, float4* __restrict__ ga,
+                                                     float4* __restrict__ gb, float4* __restrict__ alb) {
+    const long npix = (long)K.rows * K.width;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = i < npix;
+    const long p = valid ? i : npix - 1;
+    const int j = (int)(p / K.width);
+    const int x = (int)(p - (long)j * K.width);
+    const int y = K.row_offset + j * K.row_stride;
+    const f3 o = mk(K.cam_pos[0], K.cam_pos[1], K.cam_pos[2]);
+    const f3 d = primary_dir(K, x, y);
+    float t;
+    int id;
+    closest_hit<BVH>(K, o, d, t, id);
+    const AovHit a = aov_shade(K, o, d, t, id);
+    if (valid) {
+        ga[p] = make_float4(a.n.x, a.n.y, a.n.z, __int_as_float(a.prim));
+        gb[p] = make_float4(a.P.x, a.P.y, a.P.z, a.depth);
+        if (alb) alb[p] = make_float4(a.albedo.x, a.albedo.y, a.albedo.z, 0.0f);
+    }
+}
+
+#if defined(RT_TU_SHARED) || (defined(RT_TU_BVH) && !defined(RT_FAST))
+#ifdef RT_TU_SHARED
+hipError_t rt_launch_aov(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream) {
+    constexpr bool kBvh = false;
+#else
+hipError_t rt_launch_aov_bvh(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream) {
+    constexpr bool kBvh = true;
+#endif
+    const long npix = (long)K.rows * K.width;
+    if (npix <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rt_aov_kernel<kBvh>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, K, ga, gb, alb);
+    return hipGetLastError();
+}
+#endif

@@ -16,9 +16,11 @@
 //                                    cull sphere {cx,cy,cz,Rc^2}}
 //   quads     : n_quad x 32 floats  {nx,ny,nz,d, v0[3],in0[3], .. v3[3],in3[3], cull {.., Rc^2 = inf}}
 //   hit table : n_prim x 16 floats  {n_or_centre[3], is_sphere,
-//                                    emittance*albedo[3], 0,
-//                                    roughness, ior^2-1, roughness^2, 0,
-//                                    4*albedo[3], 0}
+//                                    emittance*albedo[3], albedo.x,
+//                                    roughness, ior^2-1, roughness^2, albedo.y,
+//                                    4*albedo[3], albedo.z}
+//                                   (the raw albedo for the feature buffers, in
+//                                    lanes no render kernel uses)
 //   primitive id = index within its kind + kind offset, kinds ordered
 //   spheres, planes, triangles, quads.
 //
@@ -161,3 +163,20 @@ struct rt_kparams {
 // quad i, then i+1): a primitive's key; among equal distances the reference
 // keeps the LAST tested primitive, i.e. the largest key.
 #define RT_KEY(kind, i) ((i) * 4 + (kind))
+
+// One level of the denoiser (rt_denoise.h) over a full width x height frame
+// (float4: every includer has <hip/hip_runtime.h> first).
+struct rt_dn_level {
+    int width, height;
+    int step;            // 1 << level
+    int first;           // colour in = inv * frameSum (tone_map's first step), else src
+    int last;            // also write tone_map(c, 1) to rgba (when non-null)
+    float ic, in, ip;    // 1 / sigma^2 of the colour (this level's), normal and plane terms
+    float inv;           // rt_div(1, n), n = frame counter - 1
+    const float* accum;  // frameSum, 3 planes of width * height
+    const float4* src;   // colour of the previous level
+    float4* dst;         // colour of this level {r, g, b, 0}
+    unsigned* rgba;
+    const float4* ga;    // guides {n.xyz, prim as bits}
+    const float4* gb;    //        {P.xyz, depth}
+};

@@ -12,6 +12,8 @@
 //   camera ray            Main.cu:287-290          -> primary_dir
 //   shading combine       Main.cu:262-268          -> fold_level
 //   tone map / quantise   Math.cuh:245-262, Main.cu:305-312 -> tone_map
+// Not from the reference: exp_nn (the denoiser's tap weight, rt_denoise.h) and
+// aov_shade (first-hit feature buffers).
 //
 // Every function is __host__ __device__ and written once: the GPU kernels and
 // the CPU fallback run the same float operations in the same order (both
@@ -330,8 +332,36 @@ RT_HD float atan_nn(float x) {  // orc_atanf
     return xneg ? -y : y;
 }
 
+// e^x for x <= 0 (the denoiser's tap weight, rt_denoise.h): 0 below -87, else
+// the Cephes single-precision sequence in plain float operations —
+// n = floor(x log2(e) + 0.5), two-constant Cody-Waite reduction, degree-5
+// polynomial, n added to the exponent bits.  At x >= -87 n >= -126 with a
+// polynomial value above 1 (r = x - n ln 2 > 0.33 there), so the result stays
+// normal.  Not for NaN.
+RT_HD float exp_nn(float x) {
+    if (x < -87.0f) return 0.0f;
+    const float fn = floorf(x * 1.44269504088896341f + 0.5f);
+    float r = x - fn * 0.693359375f;
+    r = r - fn * -2.12194440e-4f;
+    const float z = r * r;
+    float p = 1.9875691500e-4f * r;
+    p = p + 1.3981999507e-3f;
+    p = p * r;
+    p = p + 8.3334519073e-3f;
+    p = p * r;
+    p = p + 4.1665795894e-2f;
+    p = p * r;
+    p = p + 1.6666665459e-1f;
+    p = p * r;
+    p = p + 5.0000001201e-1f;
+    p = p * z;
+    p = p + r;
+    p = p + 1.0f;
+    return rt_i2f(rt_f2i(p) + (int)((unsigned)(int)fn << 23));
+}
+
 // ---- BRDF helpers (Main.cu:111-206) ---------------------------------------
-// rough2 = roughness * roughness (precomputed: the reference evaluates
+// rough2 =roughness * roughness (precomputed: the reference evaluates
 // roughness * roughness * tanTheta * tanTheta left to right, Main.cu:119)
 RT_HD float shadowing_masking(f3 dir, f3 n, f3 m, float rough2) {
     float vdn = dot(dir, n);
@@ -747,6 +777,38 @@ RT_HD f3 primary_dir(const rt_kparams& K, int x, int y) {
                      K.rot[3] * pix.x + K.rot[4] * pix.y + K.rot[5] * pix.z,
                      K.rot[6] * pix.x + K.rot[7] * pix.y + K.rot[8] * pix.z);
     return normalize3(pr);
+}
+
+// First-hit features of the un-jittered primary ray (rt_render_aov, the
+// denoiser's guides) from its closest hit (t, id): the hit point and the
+// shading normal as the path tracer forms them (normalised; no flip towards
+// the camera, the reference has none), the material's raw albedo (hit table
+// slots 7, 11, 15).  A miss: prim -1, depth +inf, normal and P 0, albedo =
+// the background colour.
+struct AovHit {
+    f3 albedo, n, P;
+    float depth;
+    int prim;
+};
+
+RT_HD AovHit aov_shade(const rt_kparams& K, f3 o, f3 d, float t, int id) {
+    AovHit a;
+    if (id < 0) {
+        a.albedo = mk(K.bg[0], K.bg[1], K.bg[2]);
+        a.n = mk(0.0f, 0.0f, 0.0f);
+        a.P = mk(0.0f, 0.0f, 0.0f);
+        a.depth = INFINITY;
+        a.prim = -1;
+        return a;
+    }
+    const float* h = K.hit + RT_HIT_FLOATS * id;
+    a.P = add(o, scale(t, d));
+    const f3 n = mk(h[0], h[1], h[2]);
+    a.n = normalize3(h[3] != 0.0f ? sub(a.P, n) : n);  // sphere: centre -> normal
+    a.albedo = mk(h[7], h[11], h[15]);
+    a.depth = t;
+    a.prim = id;
+    return a;
 }
 
 // Fold of the recursion innermost-first (Main.cu:262-268):

@@ -11,6 +11,8 @@
 //               [--max-bounces 5] [--background r,g,b] [--spp 1] [--device 0] [--gpus 1]
 //               [--cpu [THREADS]] [--precision exact|fast] [--keys "W*10,W+LEFT*5,*3"]
 //               [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]
+//               [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]
+//               [--aov PREFIX]
 //
 // --keys: comma-separated steps KEY[+KEY...]*FRAMES (keys W A S D SPACE
 // LEFT_SHIFT LEFT RIGHT UP DOWN ESCAPE; an empty key list holds nothing);
@@ -24,6 +26,12 @@
 // accumulatedFrames * samplesPerPixel like Main.cu:491.  --precision fast
 // renders with the reference's fast-math trade-off (rt_set_precision: GPU
 // only; the default, exact, is bit-identical to the CPU fallback).
+// --denoise [N] filters the final frame with rt_denoise (N a-trous levels,
+// default rt_denoise_params_default(); the --sigma-* flags replace its
+// sigmas): the file from --out is then the denoised frame (one context only).
+// --aov PREFIX writes the first-hit feature buffers (rt_render_aov) as
+// PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5) and PREFIX_depth (1 / (1 +
+// depth), a miss black) images in --out's format (PNG without --out).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -46,7 +54,9 @@ static const char* kUsage =
     "                   [--width 1920] [--height 1080] [--frames 8] [--frames-per-call 1]\n"
     "                   [--max-bounces 5] [--background r,g,b] [--spp 1] [--device 0] [--gpus 1]\n"
     "                   [--cpu [THREADS]] [--precision exact|fast] [--keys \"W*10,W+LEFT*5,*3\"]\n"
-    "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n";
+    "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n"
+    "                   [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]\n"
+    "                   [--aov PREFIX]\n";
 
 struct KeyStep {
     unsigned keys;
@@ -105,6 +115,9 @@ int main(int argc, char** argv) {
     int precision = RT_PRECISION_EXACT;
     float bg[3] = {0.0f, 0.0f, 0.0f};
     double fixed_dt = -1.0;
+    bool denoise = false;
+    rt_denoise_params dn = rt_denoise_params_default();
+    std::string aov;
     for (int i = 1; i < argc; i++) {
         auto next = [&](void) -> const char* { return i + 1 < argc ? argv[++i] : ""; };
         if (!std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h")) {
@@ -143,6 +156,14 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--dt")) fixed_dt = std::atof(next());
         else if (!std::strcmp(argv[i], "--out")) out = next();
         else if (!std::strcmp(argv[i], "--dump-scene")) dump = next();
+        else if (!std::strcmp(argv[i], "--denoise")) {
+            denoise = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn.iterations = std::atoi(argv[++i]);
+        }
+        else if (!std::strcmp(argv[i], "--sigma-color")) dn.sigma_color = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--sigma-normal")) dn.sigma_normal = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--sigma-plane")) dn.sigma_plane = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--aov")) aov = next();
         else {
             std::fprintf(stderr, "unknown option %s\n%s", argv[i], kUsage);
             return 2;
@@ -242,6 +263,41 @@ int main(int argc, char** argv) {
             frame_count = 0;
         }
         if (quit) break;
+    }
+    if (denoise) {
+        if (gpus != 1) {
+            std::fprintf(stderr, "--denoise needs one context (a frame gathered from several GPUs is not denoised)\n");
+            return 2;
+        }
+        if ((rc = rt_denoise(ctx, &dn, rgba.data(), nullptr))) return die(ctx, rc, "rt_denoise");
+        std::printf("denoise: %d levels, %.3f ms\n", dn.iterations, rt_last_denoise_ms(ctx));
+    }
+    if (!aov.empty()) {
+        const size_t npix = (size_t)width * height;
+        std::vector<float> albedo(npix * 3), normal(npix * 3), depth(npix);
+        rt_render_params ap{};
+        ap.width = width;
+        ap.height = height;
+        ap.row_stride = 1;
+        if ((rc = rt_render_aov(ctx, &ap, albedo.data(), normal.data(), depth.data(), nullptr)))
+            return die(ctx, rc, "rt_render_aov");
+        const bool ppm = out.size() > 4 && out.compare(out.size() - 4, 4, ".ppm") == 0;
+        auto u8 = [](float v) { return (uint8_t)(v >= 1.0f ? 255 : v > 0.0f ? (int)(v * 255.0f + 0.5f) : 0); };
+        std::vector<uint8_t> img(npix * 4);
+        for (int k = 0; k < 3; k++) {
+            for (size_t i = 0; i < npix; i++) {
+                for (int ch = 0; ch < 3; ch++)
+                    img[4 * i + ch] = k == 0   ? u8(albedo[3 * i + ch])
+                                      : k == 1 ? u8(normal[3 * i + ch] * 0.5f + 0.5f)
+                                               : u8(1.0f / (1.0f + depth[i]));
+                img[4 * i + 3] = 255;
+            }
+            const std::string name = aov + (k == 0 ? "_albedo" : k == 1 ? "_normal" : "_depth") + (ppm ? ".ppm" : ".png");
+            if (!(ppm ? bwrt::write_ppm(name, width, height, img.data()) : bwrt::write_png(name, width, height, img.data()))) {
+                std::fprintf(stderr, "cannot write %s\n", name.c_str());
+                return 1;
+            }
+        }
     }
     if (!out.empty()) {
         const bool png = out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0;

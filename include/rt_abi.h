@@ -24,7 +24,8 @@
  *    cross the ABI.  rt_last_error() gives a human-readable message.
  *  - One context = one GPU (HIP device) and one pixel-row shard.  A context
  *    must be used by one host thread at a time.  All calls except
- *    rt_render_device()/rt_deinterleave_rows_device() are synchronous.
+ *    rt_render_device()/rt_denoise_device()/rt_deinterleave_rows_device()
+ *    are synchronous.
  *  - Output RGBA8 buffers are row-major, row 0 = BOTTOM of the screen
  *    (the reference draws texcoord (0,0) at the bottom-left, Main.cu:358).
  *  - Semantics of one "sample" (progressive frame) follow the reference
@@ -43,7 +44,8 @@
  *                       BWRT_SPREAD, BWRT_ORDER, BWRT_ORDER_PERIOD,
  *                       BWRT_STREAM_PRIO=0 (the context's stream at normal
  *                       instead of the highest priority), BWRT_DEINT_BLOCKS,
- *                       BWRT_PRECISION=fast|exact
+ *                       BWRT_PRECISION=fast|exact,
+ *                       BWRT_DENOISE_KERNEL=direct|tiled (filter kernel variant)
  *      at rt_set_scene: BWRT_BVH_MIN, BWRT_BVH_LEAF, BWRT_BVH_CT, BWRT_BVH_SBVH,
  *                       BWRT_BVH_REFS, BWRT_BVH_ALPHA, BWRT_BVH_ORDER_MASK,
  *                       BWRT_BVH_N16, BWRT_NO_CULL, BWRT_BVH_STATS (report)
@@ -185,10 +187,10 @@ RT_API void rt_destroy(rt_context* ctx);
  * for the host), bit-identical results, one pixel per loop iteration on a
  * pool of `threads` host threads (256-pixel chunks).  It is an explicit
  * backend, never chosen implicitly: only a context made by rt_create_cpu()
- * renders on the CPU, and every entry point above behaves on it as on a GPU
+ * renders on the CPU, and every entry point behaves on it as on a GPU
  * context (rt_set_scene, rt_init_rand, rt_render, rt_render_ex, rt_controls,
  * rt_get_state / rt_set_state, ...; rt_last_kernel_ms gives the last render's
- * wall time) except rt_render_device, rt_render_multi and
+ * wall time) except rt_render_device, rt_denoise_device, rt_render_multi and
  * rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no device memory).
  * Replaces the reference's config-1 CPU path and is the CPU baseline of
  * bench.py (SURVEY §8(b) rt_render_cpu, §8(d)). */
@@ -402,6 +404,54 @@ RT_API int rt_deinterleave_rows_device(rt_context* ctx, const void* gathered,
 RT_API int rt_get_state(rt_context* ctx, uint32_t* rng, float* accum);
 RT_API int rt_set_state(rt_context* ctx, const uint32_t* rng,
                         const float* accum, unsigned frame_counter);
+
+/* ---- first-hit feature buffers (AOVs) and the denoiser -----------------------
+ * Neither reads or writes the RNG state, frameSum or the frame counter: a
+ * render that continues after them is bit-identical to one never interrupted.
+ * Both always use the exact arithmetic, whatever rt_set_precision says, and
+ * give bit-identical results on GPU and CPU contexts. */
+
+/* First-hit feature buffers of the shard (p->width, height, row_offset,
+ * row_stride; the other fields of p are ignored), from the un-jittered primary
+ * ray of each pixel (no RNG draw): the material's raw albedo, the path
+ * tracer's shading normal (unit length, not flipped towards the camera), the
+ * hit distance and the primitive id (spheres, planes, triangles, quads in
+ * turn).  A miss gives the background colour, normal 0, depth +inf, prim -1.
+ * Rows as rt_render_ex; any output pointer may be NULL. */
+RT_API int rt_render_aov(rt_context* ctx, const rt_render_params* p,
+                         float* albedo /*rows*w*3*/, float* normal /*rows*w*3*/,
+                         float* depth /*rows*w*/, int32_t* prim /*rows*w*/);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010; a plane-distance
+ * term for their position term) over frameSum / n, guided by the first-hit
+ * normal, hit point and hit / miss class; DESIGN.md has the exact definition. */
+#define RT_DENOISE_MAX_ITERATIONS 6
+typedef struct rt_denoise_params {
+    int iterations;      /* 0..RT_DENOISE_MAX_ITERATIONS; level i has tap step 1<<i */
+    float sigma_color;   /* > 0, +inf allowed (term off); level i uses sigma_color * 2^-i */
+    float sigma_normal;  /* > 0, +inf allowed */
+    float sigma_plane;   /* > 0, +inf allowed; world units */
+} rt_denoise_params;
+RT_API rt_denoise_params rt_denoise_params_default(void);
+
+/* Filter the context's accumulated full frame.  rgba_out: w*h*4 bytes or NULL;
+ * color_out: w*h*3 linear floats (the filtered frameSum / n) or NULL.  With
+ * iterations == 0 the RGBA equals the last render's.  RT_ERR_INVALID_ARGUMENT:
+ * iterations out of range, a sigma <= 0 or NaN, or no frame accumulated yet
+ * (frame counter < 2); RT_ERR_NO_SCENE; RT_ERR_UNSUPPORTED: the context's
+ * pixel state is a row shard (row_offset != 0 or row_stride > 1: the
+ * neighbours of its rows live on other contexts). */
+RT_API int rt_denoise(rt_context* ctx, const rt_denoise_params* params,
+                      uint8_t* rgba_out, float* color_out);
+/* As above into DEVICE memory (w*h*4 bytes, 4-byte aligned, or NULL) on HIP
+ * stream `stream`, with rt_render_device's ordering rules: returns after the
+ * launches; ordered after the context's last render and before its next one
+ * on the device, whatever streams they use.  CPU context: RT_ERR_UNSUPPORTED. */
+RT_API int rt_denoise_device(rt_context* ctx, const rt_denoise_params* params,
+                             void* rgba_device, void* stream);
+/* Duration (ms) of all levels of the last denoise call (HIP events on its
+ * stream; wall time on a CPU context); -1 when unavailable. */
+RT_API float rt_last_denoise_ms(rt_context* ctx);
 
 RT_API const char* rt_error_string(int status);
 RT_API const char* rt_last_error(const rt_context* ctx);
