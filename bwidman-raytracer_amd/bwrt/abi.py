@@ -83,6 +83,11 @@ class DenoiseParams(C.Structure):
                 ("sigma_plane", C.c_float)]
 
 
+class TemporalParams(C.Structure):
+    """rt_temporal_params: the history cap and the two tap-rejection thresholds."""
+    _fields_ = [("max_history", C.c_float), ("normal_cos_min", C.c_float), ("plane_tol", C.c_float)]
+
+
 RT_OK = 0
 RT_ERR_INVALID_ARGUMENT = -1
 RT_ERR_NO_DEVICE = -2
@@ -141,6 +146,11 @@ def _proto(lib):
         "rt_denoise": (C.c_int, [vp, P(DenoiseParams), vp, vp]),
         "rt_denoise_device": (C.c_int, [vp, P(DenoiseParams), vp, vp]),
         "rt_last_denoise_ms": (C.c_float, [vp]),
+        "rt_temporal_params_default": (TemporalParams, []),
+        "rt_temporal": (C.c_int, [vp, P(TemporalParams), P(DenoiseParams), vp, vp, vp]),
+        "rt_temporal_device": (C.c_int, [vp, P(TemporalParams), P(DenoiseParams), vp, vp]),
+        "rt_temporal_reset": (C.c_int, [vp]),
+        "rt_last_temporal_ms": (C.c_float, [vp]),
         "rt_error_string": (C.c_char_p, [C.c_int]),
         "rt_last_error": (C.c_char_p, [vp]),
         "rt_last_kernel_name": (C.c_char_p, [vp]),

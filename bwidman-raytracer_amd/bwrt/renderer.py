@@ -234,6 +234,52 @@ class Renderer:
     def last_denoise_ms(self) -> float:
         return self.lib.rt_last_denoise_ms(self.ctx)
 
+    # -- temporal reprojection ------------------------------------------------
+    def temporal_params(self, max_history=None, normal_cos_min=None, plane_tol=None):
+        """rt_temporal_params_default() with the given fields replaced."""
+        t = self.lib.rt_temporal_params_default()
+        for name, v in (("max_history", max_history), ("normal_cos_min", normal_cos_min), ("plane_tol", plane_tol)):
+            if v is not None:
+                setattr(t, name, v)
+        return t
+
+    def _dn(self, denoise):
+        """None, or a dict of denoise_params() fields -> a pointer argument."""
+        return None if denoise is None else C.byref(self.denoise_params(**denoise))
+
+    def temporal(self, width, height, max_history=None, normal_cos_min=None, plane_tol=None, denoise=None,
+                 want_color=False, want_length=False):
+        """rt_temporal: reproject the previous view's accumulated colour into
+        the accumulated full frame (width x height: the shape of the last
+        render) and blend; `denoise` (a dict of denoise_params() fields, {} =
+        the defaults) runs the a-trous filter over the result.  Returns the
+        RGBA8 image, with want_color / want_length also the linear colour (H,
+        W, 3) and the effective sample count (H, W), in that order."""
+        t = self.temporal_params(max_history, normal_cos_min, plane_tol)
+        out = np.empty((height, width, 4), np.uint8)
+        col = np.empty((height, width, 3), np.float32) if want_color else None
+        ln = np.empty((height, width), np.float32) if want_length else None
+        self._check(self.lib.rt_temporal(self.ctx, C.byref(t), self._dn(denoise), out.ctypes.data,
+                                         col.ctypes.data if col is not None else None,
+                                         ln.ctypes.data if ln is not None else None))
+        res = (out,) + ((col,) if want_color else ()) + ((ln,) if want_length else ())
+        return res if len(res) > 1 else out
+
+    def temporal_device(self, rgba_ptr: int, stream_ptr: int | None = None, max_history=None, normal_cos_min=None,
+                        plane_tol=None, denoise=None):
+        """rt_temporal_device: the temporal (and, with `denoise`, filtered)
+        RGBA8 into device memory on a stream (asynchronous; ordered after the
+        last render, denoise and temporal call on the device)."""
+        t = self.temporal_params(max_history, normal_cos_min, plane_tol)
+        self._check(self.lib.rt_temporal_device(self.ctx, C.byref(t), self._dn(denoise), rgba_ptr, stream_ptr))
+
+    def temporal_reset(self):
+        """rt_temporal_reset: drop the history and the pending result."""
+        self._check(self.lib.rt_temporal_reset(self.ctx))
+
+    def last_temporal_ms(self) -> float:
+        return self.lib.rt_last_temporal_ms(self.ctx)
+
     # -- checkpoint / resume -----------------------------------------------
     def get_state(self, rows, width):
         rng = np.empty((6, rows, width), dtype=np.uint32)

@@ -50,11 +50,14 @@ void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int ro
 bool rt_cpu_supported();
 void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb);
 void rt_cpu_denoise_level(const rt_dn_level& L, int threads);
+void rt_cpu_temporal(const rt_tp_args& T, int threads);
 // first-hit feature kernel (rt_kernels.hip; the BVH walk in rt_kernels_bvh.hip) and the
 // a-trous filter (rt_denoise.hip)
 hipError_t rt_launch_aov(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream);
 hipError_t rt_launch_aov_bvh(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream);
 hipError_t rt_launch_denoise_level(const rt_dn_level& L, bool tiled, hipStream_t stream);
+// temporal reprojection (rt_temporal.hip)
+hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream);
 
 static_assert(sizeof(rt_vec3) == 12, "vec3d layout (Math.cuh:35-39)");
 static_assert(sizeof(rt_material) == 24, "material layout (WorldTypes.cuh:15-20)");
@@ -191,6 +194,31 @@ struct rt_context {
     float dn_cpu_ms = -1.0f;
     bool dn_timed = false;
     int dn_kernel = -1;  // BWRT_DENOISE_KERNEL: 0 direct, 1 tiled, -1 = the measured per-level policy
+
+    // temporal reprojection (rt_temporal).  `view` counts views: it goes up
+    // wherever guides_valid is cleared.  Two buffer sets {colour + length,
+    // guide copy, camera}: tp[tp_hist] is the history, tp[tp_hist ^ 1] the
+    // pending result of view tp_pending_view; the first call in a later view
+    // swaps them (tp_hist ^= 1).  Nothing is allocated (events included)
+    // before the first call.
+    struct TpSet {
+        DevBuf col, ga, gb;
+        std::vector<float4> col_h, ga_h, gb_h;
+        float cam_pos[3] = {}, rot[9] = {}, screen_z = 0.0f;
+    };
+    unsigned long long view = 1;
+    TpSet tp[2];
+    int tp_hist = 0;
+    bool tp_has_hist = false, tp_has_pending = false;
+    unsigned long long tp_pending_view = 0;
+    int tp_w = 0, tp_h = 0;  // frame shape of both sets
+    // start / end of the last reprojection pass on tp_stream: timing, and the
+    // next render, denoise, temporal call or state write is ordered after the end
+    hipEvent_t ev_tp0 = nullptr, ev_tp1 = nullptr;
+    hipStream_t tp_stream = nullptr;
+    bool tp_recorded = false;
+    float tp_cpu_ms = -1.0f;
+    bool tp_timed = false;
 };
 
 namespace {
@@ -265,6 +293,7 @@ int quiesce(rt_context* c) {
     if (c->cpu) return RT_OK;
     HIP_TRY(c, flush_render(c));
     if (c->dn_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_dn1));  // a denoise still reading frameSum
+    if (c->tp_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_tp1));  // a reprojection pass likewise
     if (!c->render_recorded) return RT_OK;
     HIP_TRY(c, hipEventSynchronize(c->ev_render));
     return RT_OK;
@@ -1014,9 +1043,13 @@ void rt_destroy(rt_context* c) {
     if (c->render_recorded) (void)hipEventSynchronize(c->ev_render);
     if (c->aux_recorded) (void)hipEventSynchronize(c->ev_aux);
     if (c->dn_recorded) (void)hipEventSynchronize(c->ev_dn1);
+    if (c->tp_recorded) (void)hipEventSynchronize(c->ev_tp1);
     for (DevBuf* b : {&c->guide_a, &c->guide_b, &c->dn_col[0], &c->dn_col[1], &c->dn_rgba, &c->aov_a, &c->aov_b,
-                      &c->aov_alb})
+                      &c->aov_alb, &c->tp[0].col, &c->tp[0].ga, &c->tp[0].gb, &c->tp[1].col, &c->tp[1].ga,
+                      &c->tp[1].gb})
         free_buf(*b);
+    if (c->ev_tp0) (void)hipEventDestroy(c->ev_tp0);
+    if (c->ev_tp1) (void)hipEventDestroy(c->ev_tp1);
     if (c->ev_dn0) (void)hipEventDestroy(c->ev_dn0);
     if (c->ev_dn1) (void)hipEventDestroy(c->ev_dn1);
     free_buf(c->scene_buf);
@@ -1348,6 +1381,8 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
     c->frame = 1;
     c->order_stale = true;
     c->guides_valid = false;
+    c->view++;
+    c->tp_has_hist = c->tp_has_pending = false;  // primitive ids change meaning
     return RT_OK;
 }
 
@@ -1357,6 +1392,7 @@ int rt_set_camera(rt_context* c, const rt_camera* cam) {
     c->frame = 1;  // Controls.cuh: any movement sets accumulatedFrames = 1
     c->order_stale = true;
     c->guides_valid = false;
+    c->view++;
     return RT_OK;
 }
 
@@ -1464,6 +1500,7 @@ int rt_controls(rt_context* c, unsigned keys, float dt) {
         c->frame = 1;  // accumulatedFrames = 1
         c->order_stale = true;
         c->guides_valid = false;
+        c->view++;
     }
     return flags;
 }
@@ -1525,6 +1562,8 @@ int rt_init_rand(rt_context* c, int width, int height, int row_offset, int row_s
         rt_cpu_init_rand(c->rng_h.data(), width, rows, row_offset, row_stride);
     }
     c->guides_valid = false;  // the guides are those of one frame shape
+    c->view++;
+    if (width != c->tp_w || height != c->tp_h) c->tp_has_hist = c->tp_has_pending = false;
     if (c->cpu) {
         c->width = width;
         c->height = height;
@@ -1731,6 +1770,7 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     }
     // ... and after a denoise of the frame on another stream (it reads frameSum)
     if (c->dn_recorded && c->dn_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_dn1, 0));
+    if (c->tp_recorded && c->tp_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_tp1, 0));  // a reprojection pass too
     rt_order_groups_last = 0;
     rt_launched_kernel[0] = 0;
     // every event recorded here is a marker packet the GPU drains between two
@@ -1911,6 +1951,7 @@ int rt_synchronize(rt_context* c) {
     if (c->render_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_render));
     if (c->aux_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_aux));
     if (c->dn_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_dn1));
+    if (c->tp_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_tp1));
     return RT_OK;
 }
 
@@ -2120,10 +2161,21 @@ static int ensure_guides(rt_context* c, hipStream_t s) {
     return RT_OK;
 }
 
-// Every level of one denoise call; the final colour ends in dn_col[*final_buf]
-// and, tone-mapped, in rgba (device pointer on a GPU context; may be null)
-static int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_t s, unsigned* rgba, int* final_buf) {
-    const HostFpEnv fp;
+// A scene, an accumulated frame and a full-frame pixel state: what the
+// denoiser and the temporal reprojection (`who`) need besides their parameters
+static int full_frame_check(rt_context* c, const char* who) {
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    if (c->frame < 2u || (c->cpu ? c->accum_h.empty() : !c->accum.p))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "no frame accumulated yet (render first)");
+    if (c->row_offset != 0 || c->row_stride > 1)
+        return fail(c, RT_ERR_UNSUPPORTED,
+                    "the context holds a row shard (offset %d, stride %d): %s needs a full frame", c->row_offset,
+                    c->row_stride, who);
+    return RT_OK;
+}
+
+// The conditions of a denoise call (and of the filter part of a temporal one)
+static int denoise_check(rt_context* c, const rt_denoise_params* dp) {
     if (!c || !dp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
     if (dp->iterations < 0 || dp->iterations > RT_DENOISE_MAX_ITERATIONS)
         return fail(c, RT_ERR_INVALID_ARGUMENT, "iterations %d outside 0..%d", dp->iterations,
@@ -2131,17 +2183,22 @@ static int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_
     if (!(dp->sigma_color > 0.0f) || !(dp->sigma_normal > 0.0f) || !(dp->sigma_plane > 0.0f))
         return fail(c, RT_ERR_INVALID_ARGUMENT, "sigmas must be > 0 (colour %g, normal %g, plane %g)",
                     (double)dp->sigma_color, (double)dp->sigma_normal, (double)dp->sigma_plane);
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
-    if (c->frame < 2u || (c->cpu ? c->accum_h.empty() : !c->accum.p))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "no frame accumulated yet (render first)");
-    if (c->row_offset != 0 || c->row_stride > 1)
-        return fail(c, RT_ERR_UNSUPPORTED,
-                    "the context holds a row shard (offset %d, stride %d): the denoiser needs a full frame",
-                    c->row_offset, c->row_stride);
+    return full_frame_check(c, "the denoiser");
+}
+
+// Every level of one denoise call; the final colour ends in dn_col[*final_buf]
+// and, tone-mapped, in rgba (device pointer on a GPU context; may be null).
+// src0 non-null (rt_temporal; iterations >= 1): level 0 filters that colour
+// buffer instead of inv * frameSum.
+static int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_t s, unsigned* rgba, int* final_buf,
+                          const float4* src0 = nullptr) {
+    const HostFpEnv fp;
+    int rc = denoise_check(c, dp);
+    if (rc) return rc;
     const size_t npix = (size_t)c->height * c->width;
     if (!c->cpu) {
         HIP_TRY(c, hipSetDevice(c->device));
-        int rc = ensure_buf(c, c->dn_col[0], npix * sizeof(float4));
+        rc = ensure_buf(c, c->dn_col[0], npix * sizeof(float4));
         if (!rc) rc = ensure_buf(c, c->dn_col[1], npix * sizeof(float4));
         if (rc) return rc;
         // after the render that made the frame, and after a previous denoise
@@ -2151,6 +2208,8 @@ static int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_
             HIP_TRY(c, hipStreamWaitEvent(s, c->ev_render, 0));
         }
         if (c->dn_recorded && c->dn_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_dn1, 0));
+        // and after a reprojection pass (it reads the guides; its filter writes the colour buffers)
+        if (c->tp_recorded && c->tp_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_tp1, 0));
     } else {
         try {
             c->dn_col_h[0].resize(npix);
@@ -2159,7 +2218,7 @@ static int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_
             return fail(c, RT_ERR_OUT_OF_MEMORY, "host colour buffers for %zu pixels", npix);
         }
     }
-    int rc = ensure_guides(c, s);
+    rc = ensure_guides(c, s);
     if (rc) return rc;
     rt_dn_level L;
     std::memset(&L, 0, sizeof L);
@@ -2180,9 +2239,9 @@ static int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_
         L.step = levels > 0 ? 1 << i : 0;  // step 0: the conversion pass of iterations == 0
         const float sc = dp->sigma_color * std::ldexp(1.0f, -i);
         L.ic = 1.0f / (sc * sc);
-        L.first = i == 0;
+        L.first = i == 0 && !src0;
         L.last = i >= levels - 1;
-        L.src = i > 0 ? col[(i - 1) & 1] : nullptr;
+        L.src = i > 0 ? col[(i - 1) & 1] : src0;
         L.dst = col[i & 1];
         L.rgba = L.last ? rgba : nullptr;
         if (c->cpu) {
@@ -2270,6 +2329,230 @@ float rt_last_denoise_ms(rt_context* c) {
     if (hipEventSynchronize(c->ev_dn1) != hipSuccess) return -1.0f;
     float ms = -1.0f;
     if (hipEventElapsedTime(&ms, c->ev_dn0, c->ev_dn1) != hipSuccess) return -1.0f;
+    return ms;
+}
+
+
+// ---- temporal reprojection ----------------------------------------------------
+// (csrc/rt_temporal.h has the arithmetic)
+
+rt_temporal_params rt_temporal_params_default(void) {
+    rt_temporal_params t;
+    // tools/temporal_sweep.py
+    t.max_history = 32.0f;
+    t.normal_cos_min = 0.9f;
+    t.plane_tol = 0.02f;
+    return t;
+}
+
+static int temporal_check(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn) {
+    if (!c || !tp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!(tp->max_history > 0.0f) || !(tp->plane_tol > 0.0f) ||
+        !(tp->normal_cos_min >= -1.0f && tp->normal_cos_min <= 1.0f))
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "max_history and plane_tol must be > 0, normal_cos_min in -1..1 (%g, %g, %g)",
+                    (double)tp->max_history, (double)tp->plane_tol, (double)tp->normal_cos_min);
+    if (dn) {
+        const int rc = denoise_check(c, dn);
+        if (rc) return rc;
+    }
+    return full_frame_check(c, "reprojection");
+}
+
+// One temporal call on stream s: promote, reproject, store the pending result
+// of the current view in tp[*set]; with a filter (dn, iterations >= 1) its
+// levels follow and *filtered_buf is the dn_col buffer of the final colour
+// (else -1: the final colour is the pending one).  rgba: device pointer on a
+// GPU context; may be null.
+static int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn, hipStream_t s,
+                         unsigned* rgba, int* set, int* filtered_buf) {
+    const HostFpEnv fp;
+    int rc = temporal_check(c, tp, dn);
+    if (rc) return rc;
+    const bool filter = dn && dn->iterations > 0;
+    const size_t npix = (size_t)c->height * c->width;
+    if (c->tp_w != c->width || c->tp_h != c->height) {  // (rt_init_rand dropped them already)
+        c->tp_has_hist = c->tp_has_pending = false;
+        c->tp_w = c->width;
+        c->tp_h = c->height;
+    }
+    if (!c->cpu) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (!c->ev_tp0) HIP_TRY(c, hipEventCreate(&c->ev_tp0));
+        if (!c->ev_tp1) HIP_TRY(c, hipEventCreate(&c->ev_tp1));
+        for (rt_context::TpSet& t : c->tp)
+            for (DevBuf* b : {&t.col, &t.ga, &t.gb})
+                if ((rc = ensure_buf(c, *b, npix * sizeof(float4)))) return rc;
+        // after the render that made the frame, a previous denoise (the guides;
+        // its levels may still read a pending colour) and a previous temporal
+        // call (it reads the set this one writes), whatever streams they ran on
+        if (c->render_stream && c->render_stream != s) {
+            HIP_TRY(c, flush_render(c));
+            HIP_TRY(c, hipStreamWaitEvent(s, c->ev_render, 0));
+        }
+        if (c->dn_recorded && c->dn_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_dn1, 0));
+        if (c->tp_recorded && c->tp_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_tp1, 0));
+    } else {
+        try {
+            for (rt_context::TpSet& t : c->tp) {
+                t.col_h.resize(npix);
+                t.ga_h.resize(npix);
+                t.gb_h.resize(npix);
+            }
+        } catch (...) {
+            return fail(c, RT_ERR_OUT_OF_MEMORY, "host history buffers for %zu pixels", npix);
+        }
+    }
+    rc = ensure_guides(c, s);
+    if (rc) return rc;
+    // the first call of a later view: the pending result becomes the history.
+    // The swap is of host-side roles only; the stream waits above order this
+    // call's kernel after every earlier reader of the set it now writes.
+    if (c->tp_has_pending && c->tp_pending_view != c->view) {
+        c->tp_hist ^= 1;
+        c->tp_has_hist = true;
+        c->tp_has_pending = false;
+    }
+    const rt_context::TpSet& H = c->tp[c->tp_hist];
+    rt_context::TpSet& P = c->tp[c->tp_hist ^ 1];
+    rt_kparams K;
+    fill_view(c, c->width, c->height, 0, 1, c->height, K);
+    rt_tp_args T;
+    std::memset(&T, 0, sizeof T);
+    T.width = c->width;
+    T.height = c->height;
+    T.has_history = c->tp_has_hist ? 1 : 0;
+    T.n = (float)(c->frame - 1u);
+    T.inv = 1.0f / (float)(c->frame - 1u);
+    T.max_history = tp->max_history;
+    T.normal_cos_min = tp->normal_cos_min;
+    T.plane_tol = tp->plane_tol;
+    std::memcpy(T.h_cam, H.cam_pos, sizeof T.h_cam);
+    std::memcpy(T.h_rot, H.rot, sizeof T.h_rot);
+    T.h_screen_z = H.screen_z;
+    T.accum = c->cpu ? c->accum_h.data() : (const float*)c->accum.p;
+    T.ga = c->cpu ? c->guide_a_h.data() : (const float4*)c->guide_a.p;
+    T.gb = c->cpu ? c->guide_b_h.data() : (const float4*)c->guide_b.p;
+    T.h_col = c->cpu ? H.col_h.data() : (const float4*)H.col.p;
+    T.h_ga = c->cpu ? H.ga_h.data() : (const float4*)H.ga.p;
+    T.h_gb = c->cpu ? H.gb_h.data() : (const float4*)H.gb.p;
+    T.p_col = c->cpu ? P.col_h.data() : (float4*)P.col.p;
+    T.p_ga = c->cpu ? P.ga_h.data() : (float4*)P.ga.p;
+    T.p_gb = c->cpu ? P.gb_h.data() : (float4*)P.gb.p;
+    T.rgba = filter ? nullptr : rgba;  // the filter's last level writes it otherwise
+    if (c->cpu) {
+        const auto t0 = std::chrono::steady_clock::now();
+        rt_cpu_temporal(T, c->threads);
+        c->tp_cpu_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    } else {
+        HIP_TRY(c, hipEventRecord(c->ev_tp0, s));
+        HIP_TRY(c, rt_launch_temporal(T, s));
+        HIP_TRY(c, hipEventRecord(c->ev_tp1, s));
+        c->tp_stream = s;
+        c->tp_recorded = true;
+    }
+    c->tp_timed = true;
+    std::memcpy(P.cam_pos, K.cam_pos, sizeof P.cam_pos);
+    std::memcpy(P.rot, K.rot, sizeof P.rot);
+    P.screen_z = K.screen_z;
+    c->tp_has_pending = true;
+    c->tp_pending_view = c->view;
+    *set = c->tp_hist ^ 1;
+    *filtered_buf = -1;
+    if (filter) {
+        int fb = 0;
+        rc = denoise_levels(c, dn, s, rgba, &fb, T.p_col);
+        if (rc) return rc;
+        *filtered_buf = fb;
+    }
+    return RT_OK;
+}
+
+int rt_temporal(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn, uint8_t* rgba_out,
+                float* color_out, float* length_out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    const size_t npix = (size_t)c->height * c->width;
+    int set = 0, fb = -1;
+    std::vector<float4> col, len;
+    if (c->cpu) {
+        std::vector<unsigned> rgba;
+        try {
+            if (rgba_out) rgba.resize(npix);
+        } catch (...) {
+            return fail(c, RT_ERR_OUT_OF_MEMORY, "host RGBA for %zu pixels", npix);
+        }
+        const int rc = temporal_pass(c, tp, dn, nullptr, rgba_out ? rgba.data() : nullptr, &set, &fb);
+        if (rc) return rc;
+        if (rgba_out) std::memcpy(rgba_out, rgba.data(), npix * 4);
+        const float4* pc = c->tp[set].col_h.data();
+        const float4* fc = fb >= 0 ? c->dn_col_h[fb].data() : pc;
+        for (size_t i = 0; i < npix; i++) {
+            if (color_out) {
+                color_out[3 * i + 0] = fc[i].x;
+                color_out[3 * i + 1] = fc[i].y;
+                color_out[3 * i + 2] = fc[i].z;
+            }
+            if (length_out) length_out[i] = pc[i].w;
+        }
+        return RT_OK;
+    }
+    if (rgba_out) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        const int rc = ensure_buf(c, c->dn_rgba, npix * 4);
+        if (rc) return rc;
+    }
+    const int rc = temporal_pass(c, tp, dn, c->stream, rgba_out ? (unsigned*)c->dn_rgba.p : nullptr, &set, &fb);
+    if (rc) return rc;
+    try {
+        if (color_out || (length_out && fb < 0)) col.resize(npix);
+        if (length_out && fb >= 0) len.resize(npix);
+    } catch (...) {
+        (void)hipStreamSynchronize(c->stream);
+        return fail(c, RT_ERR_OUT_OF_MEMORY, "host colour for %zu pixels", npix);
+    }
+    if (rgba_out) HIP_TRY(c, hipMemcpyAsync(rgba_out, c->dn_rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!col.empty())
+        HIP_TRY(c, hipMemcpyAsync(col.data(), fb >= 0 ? c->dn_col[fb].p : c->tp[set].col.p, npix * sizeof(float4),
+                                  hipMemcpyDeviceToHost, c->stream));
+    if (!len.empty())
+        HIP_TRY(c, hipMemcpyAsync(len.data(), c->tp[set].col.p, npix * sizeof(float4), hipMemcpyDeviceToHost,
+                                  c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const std::vector<float4>& lsrc = len.empty() ? col : len;
+    for (size_t i = 0; i < npix; i++) {
+        if (color_out) {
+            color_out[3 * i + 0] = col[i].x;
+            color_out[3 * i + 1] = col[i].y;
+            color_out[3 * i + 2] = col[i].z;
+        }
+        if (length_out) length_out[i] = lsrc[i].w;
+    }
+    return RT_OK;
+}
+
+int rt_temporal_device(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn, void* rgba_device,
+                       void* stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_temporal_device: CPU context");
+    if (rgba_device && ((uintptr_t)rgba_device & 3u))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
+    int set = 0, fb = -1;
+    return temporal_pass(c, tp, dn, stream ? (hipStream_t)stream : c->stream, (unsigned*)rgba_device, &set, &fb);
+}
+
+int rt_temporal_reset(rt_context* c) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    // roles only: work still queued on the buffers is ordered by the next call's stream waits
+    c->tp_has_hist = c->tp_has_pending = false;
+    return RT_OK;
+}
+
+float rt_last_temporal_ms(rt_context* c) {
+    if (!c || !c->tp_timed) return -1.0f;
+    if (c->cpu) return c->tp_cpu_ms;
+    if (hipEventSynchronize(c->ev_tp1) != hipSuccess) return -1.0f;
+    float ms = -1.0f;
+    if (hipEventElapsedTime(&ms, c->ev_tp0, c->ev_tp1) != hipSuccess) return -1.0f;
     return ms;
 }
 

@@ -227,6 +227,7 @@ int rt_cpu_render(const rt_kparams& K, int threads) {
 
 // ---- first-hit features and the a-trous filter on the host -------------------
 #include "rt_denoise.h"
+#include "rt_temporal.h"
 
 namespace {
 
@@ -304,5 +305,13 @@ void rt_cpu_denoise_level(const rt_dn_level& L, int threads) {
             const DnGlobalFetch<false> fetch{L};
             dn_store(L, p, dn_pixel(L, x, y, fetch));
         }
+    });
+}
+
+// The temporal reprojection pass (rt_temporal.h), on the same pool
+void rt_cpu_temporal(const rt_tp_args& T, int threads) {
+    parallel_items((long)T.width * T.height, threads, [&](long p) {
+        const int y = (int)(p / T.width);
+        tp_run_pixel(T, (int)(p - (long)y * T.width), y);
     });
 }

@@ -180,3 +180,27 @@ struct rt_dn_level {
     const float4* ga;    // guides {n.xyz, prim as bits}
     const float4* gb;    //        {P.xyz, depth}
 };
+
+// One temporal reprojection pass (rt_temporal.h) over a full width x height
+// frame: the current view's frameSum and guides, the history view's colour,
+// guides and camera, and the pending buffers of the current view.
+struct rt_tp_args {
+    int width, height;
+    int has_history;     // 0: every pixel takes the no-history path (h_* are not read)
+    float n;             // (float)(frame counter - 1)
+    float inv;           // 1 / n, formed as rt_dn_level::inv
+    float max_history, normal_cos_min, plane_tol;
+    float h_cam[3];      // the history view's rt_kparams::cam_pos, rot, screen_z
+    float h_rot[9];
+    float h_screen_z;
+    const float* accum;  // frameSum, 3 planes of width * height
+    const float4* ga;    // current guides {n.xyz, prim as bits}
+    const float4* gb;    //                {P.xyz, depth}
+    const float4* h_col; // history {r, g, b, len}
+    const float4* h_ga;
+    const float4* h_gb;
+    float4* p_col;       // pending {out.rgb, len_out}
+    float4* p_ga;        // pending copy of the current guides
+    float4* p_gb;
+    unsigned* rgba;      // tone_map(out, 1) when non-null
+};

@@ -12,6 +12,7 @@
 //               [--cpu [THREADS]] [--precision exact|fast] [--keys "W*10,W+LEFT*5,*3"]
 //               [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]
 //               [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]
+//               [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]
 //               [--aov PREFIX]
 //
 // --keys: comma-separated steps KEY[+KEY...]*FRAMES (keys W A S D SPACE
@@ -29,6 +30,12 @@
 // --denoise [N] filters the final frame with rt_denoise (N a-trous levels,
 // default rt_denoise_params_default(); the --sigma-* flags replace its
 // sigmas): the file from --out is then the denoised frame (one context only).
+// --temporal calls rt_temporal after every render call, before controls(): a
+// view's accumulated colour is kept when the keys move the camera and is
+// reprojected into the next view (--max-history, --normal-cos and --plane-tol
+// replace the fields of rt_temporal_params_default()).  The file from --out is
+// then the temporal frame of the last render call, filtered when --denoise is
+// also given (one context only).
 // --aov PREFIX writes the first-hit feature buffers (rt_render_aov) as
 // PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5) and PREFIX_depth (1 / (1 +
 // depth), a miss black) images in --out's format (PNG without --out).
@@ -56,6 +63,7 @@ static const char* kUsage =
     "                   [--cpu [THREADS]] [--precision exact|fast] [--keys \"W*10,W+LEFT*5,*3\"]\n"
     "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n"
     "                   [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]\n"
+    "                   [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]\n"
     "                   [--aov PREFIX]\n";
 
 struct KeyStep {
@@ -117,6 +125,8 @@ int main(int argc, char** argv) {
     double fixed_dt = -1.0;
     bool denoise = false;
     rt_denoise_params dn = rt_denoise_params_default();
+    bool temporal = false;
+    rt_temporal_params tp = rt_temporal_params_default();
     std::string aov;
     for (int i = 1; i < argc; i++) {
         auto next = [&](void) -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -163,6 +173,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--sigma-color")) dn.sigma_color = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--sigma-normal")) dn.sigma_normal = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--sigma-plane")) dn.sigma_plane = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--temporal")) temporal = true;
+        else if (!std::strcmp(argv[i], "--max-history")) tp.max_history = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--normal-cos")) tp.normal_cos_min = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--plane-tol")) tp.plane_tol = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--aov")) aov = next();
         else {
             std::fprintf(stderr, "unknown option %s\n%s", argv[i], kUsage);
@@ -207,6 +221,10 @@ int main(int argc, char** argv) {
     if (!dump.empty() || (!save.empty() && frames <= 0)) return 0;
 
     if (gpus < 1 || cpu_threads >= 0) gpus = 1;
+    if (temporal && gpus != 1) {
+        std::fprintf(stderr, "--temporal needs one context (a frame gathered from several GPUs is not reprojected)\n");
+        return 2;
+    }
     const int ndev = cpu_threads >= 0 ? 1 : rt_device_count() > 0 ? rt_device_count() : 1;
     std::vector<rt_context*> ctxs(gpus, nullptr);
     int rc = 0;
@@ -239,6 +257,17 @@ int main(int argc, char** argv) {
         if (rc) return die(ctx, rc, "rt_render");
         done += n;
         const double frame_s = std::chrono::duration<double>(clk::now() - t0).count();
+        if (temporal) {
+            // before controls() restarts the accumulation.  The call after the
+            // last render gives the frame that is written (filtered with --denoise)
+            const bool last = done == frames || (!steps.empty() && (steps[step].keys & RT_KEY_ESCAPE));
+            rc = rt_temporal(ctx, &tp, last && denoise ? &dn : nullptr, last ? rgba.data() : nullptr, nullptr, nullptr);
+            if (rc) return die(ctx, rc, "rt_temporal");
+            if (last) {
+                std::printf("temporal: %.3f ms\n", rt_last_temporal_ms(ctx));
+                if (denoise) std::printf("denoise: %d levels, %.3f ms\n", dn.iterations, rt_last_denoise_ms(ctx));
+            }
+        }
         bool quit = false;
         if (!steps.empty()) {  // controls(window, camera, deltaTime, accumulatedFrames)
             const unsigned keys = steps[step].keys;
@@ -264,7 +293,7 @@ int main(int argc, char** argv) {
         }
         if (quit) break;
     }
-    if (denoise) {
+    if (denoise && !temporal) {
         if (gpus != 1) {
             std::fprintf(stderr, "--denoise needs one context (a frame gathered from several GPUs is not denoised)\n");
             return 2;

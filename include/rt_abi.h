@@ -24,8 +24,8 @@
  *    cross the ABI.  rt_last_error() gives a human-readable message.
  *  - One context = one GPU (HIP device) and one pixel-row shard.  A context
  *    must be used by one host thread at a time.  All calls except
- *    rt_render_device()/rt_denoise_device()/rt_deinterleave_rows_device()
- *    are synchronous.
+ *    rt_render_device()/rt_denoise_device()/rt_temporal_device()/
+ *    rt_deinterleave_rows_device() are synchronous.
  *  - Output RGBA8 buffers are row-major, row 0 = BOTTOM of the screen
  *    (the reference draws texcoord (0,0) at the bottom-left, Main.cu:358).
  *  - Semantics of one "sample" (progressive frame) follow the reference
@@ -190,8 +190,9 @@ RT_API void rt_destroy(rt_context* ctx);
  * renders on the CPU, and every entry point behaves on it as on a GPU
  * context (rt_set_scene, rt_init_rand, rt_render, rt_render_ex, rt_controls,
  * rt_get_state / rt_set_state, ...; rt_last_kernel_ms gives the last render's
- * wall time) except rt_render_device, rt_denoise_device, rt_render_multi and
- * rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no device memory).
+ * wall time) except rt_render_device, rt_denoise_device, rt_temporal_device,
+ * rt_render_multi and rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no
+ * device memory).
  * Replaces the reference's config-1 CPU path and is the CPU baseline of
  * bench.py (SURVEY §8(b) rt_render_cpu, §8(d)). */
 
@@ -452,6 +453,57 @@ RT_API int rt_denoise_device(rt_context* ctx, const rt_denoise_params* params,
 /* Duration (ms) of all levels of the last denoise call (HIP events on its
  * stream; wall time on a CPU context); -1 when unavailable. */
 RT_API float rt_last_denoise_ms(rt_context* ctx);
+
+/* ---- temporal reprojection across camera moves ---------------------------------
+ * A camera change restarts the accumulation (frameSum is reset by the next
+ * render).  rt_temporal() keeps what the previous view had accumulated: it
+ * reprojects that view's colour into the current one through the first-hit
+ * geometry (the temporal stage of SVGF, Schied et al. 2017) and blends it with
+ * frameSum / n by effective sample counts; DESIGN.md section 10 has the exact
+ * definition.  Like the denoiser it reads neither the RNG state nor writes
+ * frameSum or the frame counter, always uses the exact arithmetic, and gives
+ * bit-identical results on GPU and CPU contexts.
+ *
+ * The context counts views: a new one starts at rt_set_scene, rt_set_camera, a
+ * moving rt_controls and a change of the frame shape.  A call writes the
+ * *pending* result of the current view {colour, effective sample count, the
+ * view's first-hit guides and camera}; the first call in a later view promotes
+ * the pending result to the *history* (a buffer swap) and reprojects from it.
+ * Repeated calls in one view leave the history alone and overwrite the pending
+ * result.  rt_set_scene (primitive ids change meaning), a change of width or
+ * height and rt_temporal_reset drop both.  The scene is static between
+ * rt_set_scene calls: equal primitive ids are the occlusion test.  Nothing is
+ * allocated before the first call. */
+typedef struct rt_temporal_params {
+    float max_history;     /* > 0: cap on the reprojected effective sample count */
+    float normal_cos_min;  /* -1..1: least cosine between the normals of a pixel and a history tap */
+    float plane_tol;       /* > 0: largest distance of a tap's hit point from the pixel's tangent
+                              plane, relative to the pixel's hit distance */
+} rt_temporal_params;
+RT_API rt_temporal_params rt_temporal_params_default(void);
+
+/* Reproject into the context's accumulated full frame.  dn == NULL: no spatial
+ * filter; else the a-trous levels of rt_denoise run over the temporal colour
+ * instead of frameSum / n (dn->iterations == 0: as NULL), and rgba_out /
+ * color_out are the filtered result; the stored history is always the
+ * unfiltered colour.  rgba_out: w*h*4 bytes or NULL; color_out: w*h*3 linear
+ * floats or NULL; length_out: w*h effective sample counts or NULL (n where
+ * nothing was reprojected).  Errors as rt_denoise: RT_ERR_INVALID_ARGUMENT (a
+ * parameter out of range or NaN, no frame accumulated yet), RT_ERR_NO_SCENE,
+ * RT_ERR_UNSUPPORTED (a row shard). */
+RT_API int rt_temporal(rt_context* ctx, const rt_temporal_params* params, const rt_denoise_params* dn,
+                       uint8_t* rgba_out, float* color_out, float* length_out);
+/* As above into DEVICE memory (w*h*4 bytes, 4-byte aligned, or NULL) on HIP
+ * stream `stream` (NULL = the context's), with rt_denoise_device's ordering
+ * rules: after the context's last render, denoise and temporal call, before
+ * its next ones, whatever streams they use.  CPU context: RT_ERR_UNSUPPORTED. */
+RT_API int rt_temporal_device(rt_context* ctx, const rt_temporal_params* params, const rt_denoise_params* dn,
+                              void* rgba_device, void* stream);
+/* Drop the history and the pending result (the buffers stay allocated). */
+RT_API int rt_temporal_reset(rt_context* ctx);
+/* Duration (ms) of the reprojection pass alone of the last temporal call (HIP
+ * events on its stream; wall time on a CPU context); -1 when unavailable. */
+RT_API float rt_last_temporal_ms(rt_context* ctx);
 
 RT_API const char* rt_error_string(int status);
 RT_API const char* rt_last_error(const rt_context* ctx);
