@@ -1,0 +1,324 @@
+// rt_context.h — what the host units of the C ABI (include/rt_abi.h) share:
+// struct rt_context with its buffer and pass types, the error helpers, and
+// the kernel launchers.  Private to csrc/.
+//
+//   rt_context.cpp  create / destroy, setters, controls, state, errors
+//   rt_render.cpp   prepare, fill_view, launch, rt_render*, multi-GPU, de-interleave
+//   rt_post.cpp     first-hit features, denoiser, temporal reprojection
+//   rt_scene.cpp    the scene compiler (rt_scene.h; no HIP, no context)
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include <xmmintrin.h>
+
+#include "../../include/rt_abi.h"
+#include "rt_layout.h"
+#include "rt_scene.h"
+
+// ---- kernel launchers ---------------------------------------------------------
+size_t rt_render_rec_floats(const rt_kparams& K);
+bool rt_render_wants_global_records(const rt_kparams& K, int num_cus);
+hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, bool simple, int block_req,
+                            hipStream_t stream, int pair_req);
+hipError_t rt_launch_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride,
+                               hipStream_t stream);
+// the reference-fast instantiations (rt_kernels_fast.hip, rt_kernels_bvh_fast.hip)
+namespace rt_fast {
+bool rt_render_wants_global_records(const rt_kparams& K, int num_cus);
+hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, bool simple, int block_req,
+                            hipStream_t stream, int pair_req);
+}  // namespace rt_fast
+extern thread_local long rt_order_groups_last;
+extern thread_local char rt_launched_kernel[96];
+hipError_t rt_launch_deinterleave(const unsigned* gathered, unsigned* image, int width, int height,
+                                  int shards, int rows_per_shard, int max_blocks, hipStream_t stream);
+// scalar C++ CPU fallback (rt_cpu.cpp)
+int rt_cpu_render(const rt_kparams& K, int threads);
+void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride);
+bool rt_cpu_supported();
+void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb);
+void rt_cpu_denoise_level(const rt_dn_level& L, int threads);
+void rt_cpu_temporal(const rt_tp_args& T, int threads);
+// first-hit feature kernel (rt_kernels.hip; the BVH walk in rt_kernels_bvh.hip) and the
+// a-trous filter (rt_denoise.hip)
+hipError_t rt_launch_aov(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream);
+hipError_t rt_launch_aov_bvh(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream);
+hipError_t rt_launch_denoise_level(const rt_dn_level& L, bool tiled, hipStream_t stream);
+// temporal reprojection (rt_temporal.hip)
+hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream);
+
+// ---- buffers -------------------------------------------------------------------
+// Device memory on a GPU context, host memory on a CPU context (ensure_buf);
+// frees itself with the context.
+struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    bool host = false;
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { release(); }
+    void release() {
+        if (p) host ? std::free(p) : (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <class T>
+    T* as() const {
+        return static_cast<T*>(p);
+    }
+};
+
+// ---- passes --------------------------------------------------------------------
+// One kind of work the context puts on a stream (render, de-interleave,
+// denoise, reprojection): where the last one ran, the event that marks its
+// end — later work on another stream and host-side state writes are ordered
+// after it; events, not stream handles, so a caller may destroy its streams —
+// and its duration.  A CPU context (`host`) has no events: a pass is over
+// when it returns, and is timed by the wall clock.
+struct Pass {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // start marker (timed passes) and end
+    hipStream_t stream = nullptr;             // of the last one
+    // the context's own stream, for the render pass alone: a pass there
+    // without a start marker leaves its end event `pending` (see end)
+    hipStream_t home = nullptr;
+    bool host = false;
+    bool recorded = false;  // ev1 was recorded at least once
+    bool pending = false;   // the last one ran on `home` and ev1 is not recorded for it yet
+    bool timed = false;     // ev0 .. ev1 bracket the last one
+    bool marked = false;    // begin() recorded the start marker
+    float cpu_ms = -1.0f;
+    std::chrono::steady_clock::time_point t0;
+
+    // the events; `timing`: a start marker too and default flags, else an
+    // end event without timing.  Idempotent (the temporal pass creates its
+    // events on first use: nothing is allocated before the first call).
+    hipError_t create(bool timing) {
+        hipError_t e = hipSuccess;
+        if (timing && !ev0) e = hipEventCreate(&ev0);
+        if (e == hipSuccess && !ev1) e = timing ? hipEventCreate(&ev1) : hipEventCreateWithFlags(&ev1, hipEventDisableTiming);
+        return e;
+    }
+    hipError_t begin(hipStream_t s, bool with_marker) {
+        marked = with_marker;
+        if (host) t0 = std::chrono::steady_clock::now();
+        return !host && with_marker ? hipEventRecord(ev0, s) : hipSuccess;
+    }
+    // Every recorded event is a marker packet the GPU drains between two
+    // kernels (~5 us each on MI355X, tools/ev_ab.sh).  On `home`, which lives
+    // as long as the context, an unmarked pass therefore records nothing:
+    // flush() records the end event when a later call needs it, and
+    // back-to-back renders carry no packet between them.
+    hipError_t end(hipStream_t s) {
+        stream = s;
+        if (host) {
+            cpu_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        } else if (home && s == home && !marked) {
+            pending = true;
+        } else {
+            pending = false;
+            const hipError_t e = hipEventRecord(ev1, s);
+            if (e != hipSuccess) return e;
+            recorded = true;
+        }
+        timed = marked;
+        return hipSuccess;
+    }
+    hipError_t flush() {
+        if (!pending) return hipSuccess;
+        pending = false;
+        const hipError_t e = hipEventRecord(ev1, home);
+        if (e == hipSuccess) recorded = true;
+        return e;
+    }
+    // order stream s after the last pass (nothing to do on its own stream)
+    hipError_t wait_on(hipStream_t s) {
+        if (!(recorded || pending) || stream == s) return hipSuccess;
+        const hipError_t e = flush();
+        return e != hipSuccess ? e : hipStreamWaitEvent(s, ev1, 0);
+    }
+    hipError_t sync() { return recorded ? hipEventSynchronize(ev1) : hipSuccess; }  // host-side wait (flush first)
+    float elapsed_ms() {
+        if (host) return cpu_ms;
+        float ms = -1.0f;
+        if (!timed || hipEventSynchronize(ev1) != hipSuccess || hipEventElapsedTime(&ms, ev0, ev1) != hipSuccess)
+            return -1.0f;
+        return ms;
+    }
+    void destroy() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        ev0 = ev1 = nullptr;
+    }
+};
+
+struct rt_context {
+    int device = 0;
+    int num_cus = 256;
+    bool simple = false;  // BWRT_KERNEL=simple: one-path-per-lane kernel (A/B reference)
+    int grid_mult = 0;  // persistent grid = grid_mult x resident workgroups per CU x CUs
+    hipStream_t stream = nullptr;
+    // render: the kernels read and write the shard state, so a launch on
+    // another stream and host-side state writes wait for the last one.
+    // aux: the last de-interleave (rt_synchronize waits for it; it touches no
+    // state).  denoise: its levels read frameSum and share the guides and
+    // colour buffers.  temporal: the reprojection pass, likewise; its events
+    // are created by the first temporal call.
+    Pass render, aux, denoise, temporal;
+    // CPU backend (rt_create_cpu): host buffers, and the scalar fallback of
+    // rt_cpu.cpp instead of the kernels
+    bool cpu = false;
+    int threads = 1;
+    bool ktiming = true;  // start marker before each render launch (rt_set_kernel_timing)
+    std::string err;
+
+    bool has_scene = false;
+    rt_camera camera{};
+    float background[3] = {0.0f, 0.0f, 0.0f};  // backgroundColor, Main.cu:27
+    rt_compiled_scene scene;  // of scene_buf (its `data` is dropped once scene_buf holds it)
+    Buf scene_buf;
+
+    // shard state
+    int width = 0, height = 0, row_offset = 0, row_stride = 1, rows = 0;
+    Buf rng, accum, rgba;
+    Buf rec;  // sorted kernel's record stack in global memory (deep paths)
+    // launch-order feedback (rt_layout.h): tile-group costs of the last
+    // launch and the order sorted from them, valid for a grid of order_n groups
+    Buf gcost, gorder;
+    long order_n = 0;
+    // re-sort the launch order every order_period-th launch (BWRT_ORDER_PERIOD;
+    // a grid without an order is always sorted): the per-group costs follow
+    // the image, so a kept order is as good as a fresh one, and the sort
+    // kernel plus its launch gap cost ~8 us per launch.  Config 3 bench kernel
+    // average, three alternating runs: every launch 0.7567 / 0.7543 / 0.7535,
+    // every 4th 0.7479 / 0.7461 / 0.7476, every 16th 0.7462 / 0.7430 / 0.7469,
+    // never again 0.7451 / 0.7458 / 0.7484 ms (profiles/r03f/order_period_ab.txt);
+    // config 2 0.1503 / 0.1515 vs 0.1555 / 0.1565, config 4 5.50 vs 5.52 ms
+    int order_period = 16;
+    // the kept order was measured on another image (new scene, camera or
+    // shard): the next launch re-sorts its costs whatever the period
+    bool order_stale = true;
+    unsigned long long launches = 0;
+    bool order_feedback = true;  // BWRT_ORDER=0: blockIdx order
+    int grec = -1;  // BWRT_GREC: 1 / 0 force global / LDS records; -1 = launch policy
+    void* host_rgba = nullptr;  // pinned staging for rt_render_multi
+    size_t host_rgba_bytes = 0;
+    int block = 0;               // BWRT_BLOCK: sorted-kernel workgroup lanes (0 = launch policy)
+    int tile_w = -1;             // BWRT_TILE: wave tile width (0 = linear order; -1 = launch policy)
+    int tile_sq = 0;             // BWRT_TILE_SQ: a 4-wave group's tiles as 2 x 2 (experiment)
+    int leaf_batch = -1;         // BWRT_LEAF_BATCH: BVH refill kernel leaf-batch threshold (-1 = launch policy)
+    int refill = -1;             // BWRT_REFILL: BVH refill kernel refill threshold (-1 = launch policy)
+    int spread = -1;             // BWRT_SPREAD: 1 / 0 force the pair kernel on / off (-1 = launch policy)
+    int deint_blocks = 0;        // BWRT_DEINT_BLOCKS: cap on the de-interleave grid (0 = one thread per 16 bytes)
+    std::string kernel_name;     // the render kernel of the last launch (rt_last_kernel_name)
+    int precision = RT_PRECISION_EXACT;  // rt_set_precision (BWRT_PRECISION): which kernels the next render launches
+    unsigned frame = 1;
+    int max_bounces = RT_DEFAULT_MAX_BOUNCES;
+    int spp_inner = 1;  // samplesPerPixel, Main.cu:27
+
+    // denoiser (rt_denoise): the first-hit guides of the current full frame
+    // {n.xyz, prim} / {P.xyz, depth}, valid until the scene, the camera or the
+    // frame shape changes, and two ping-pong colour buffers
+    Buf guide_a, guide_b, dn_col[2], dn_rgba;
+    Buf aov_a, aov_b, aov_alb;  // rt_render_aov scratch (any shard; GPU contexts)
+    bool guides_valid = false;
+    int dn_kernel = -1;  // BWRT_DENOISE_KERNEL: 0 direct, 1 tiled, -1 = the measured per-level policy
+
+    // temporal reprojection (rt_temporal).  `view` counts views: it goes up
+    // wherever guides_valid is cleared.  Two buffer sets {colour + length,
+    // guide copy, camera}: tp[tp_hist] is the history, tp[tp_hist ^ 1] the
+    // pending result of view tp_pending_view; the first call in a later view
+    // swaps them (tp_hist ^= 1).  Nothing is allocated (events included)
+    // before the first call.
+    struct TpSet {
+        Buf col, ga, gb;
+        float cam_pos[3] = {}, rot[9] = {}, screen_z = 0.0f;
+    };
+    unsigned long long view = 1;
+    TpSet tp[2];
+    int tp_hist = 0;
+    bool tp_has_hist = false, tp_has_pending = false;
+    unsigned long long tp_pending_view = 0;
+    int tp_w = 0, tp_h = 0;  // frame shape of both sets
+
+    // a new view (scene, camera, frame shape): the guides are stale
+    void new_view() {
+        guides_valid = false;
+        view++;
+    }
+};
+
+// ---- helpers shared by the units (rt_context.cpp) -----------------------------
+// IEEE float state for the library's host-side float work (scene compile,
+// camera set-up, controls): round to nearest, no FTZ / DAZ, whatever the
+// calling thread holds (a -ffast-math library or torch.set_flush_denormal
+// may have set them), restored on return — the GPU keeps f32 denormals and
+// the compiled scene must not depend on the caller
+struct HostFpEnv {
+    unsigned saved;
+    HostFpEnv() : saved(_mm_getcsr()) {
+        _mm_setcsr((saved & ~(_MM_ROUND_MASK | _MM_FLUSH_ZERO_MASK | 0x0040u)) | _MM_ROUND_NEAREST);  // 0x40 = DAZ
+    }
+    ~HostFpEnv() { _mm_setcsr(saved); }
+};
+
+// Tuning and diagnostic knobs (BWRT_BLOCK, BWRT_TILE, BWRT_GREC, BWRT_SPREAD,
+// BWRT_ORDER*, BWRT_BVH_*, BWRT_STAMPS, ...; listed in rt_abi.h) are read
+// only when the process sets BWRT_TUNING=1: a default context always takes
+// the measured launch policy, whatever else the environment holds.
+const char* tuning_env(const char* name);
+
+int fail(rt_context* c, int code, const char* fmt, ...);
+int hip_fail(rt_context* c, hipError_t e, const char* what);
+
+#define HIP_TRY(ctx, expr)                                  \
+    do {                                                    \
+        hipError_t _e = (expr);                             \
+        if (_e != hipSuccess) return hip_fail(ctx, _e, #expr); \
+    } while (0)
+
+// Host-side wait for every pass that uses the shard state (render, denoise,
+// temporal), on whatever streams they ran; no-op on a CPU context
+int quiesce(rt_context* c);
+// Order stream s after the same three passes (no host sync)
+int order_after_all(rt_context* c, hipStream_t s);
+// At least `bytes` in b (never shrinks).  A CPU context allocates host
+// memory; its failure is RT_ERR_OUT_OF_MEMORY with the message host_oom
+// (a format taking n).  A buffer that may be in use is freed only after
+// quiesce() and a sync of the context's stream.
+int ensure_buf(rt_context* c, Buf& b, size_t bytes, const char* host_oom = "host buffer (%zu)", size_t n = 0);
+int shard_rows(int height, int row_offset, int row_stride);
+int shard_check(rt_context* c, int width, int height, int row_offset, int row_stride);  // RT_OK or the failure
+// Camera prelude and compiled scene of a width x height view (shard
+// row_offset, stride, rows) into K; every other field 0 (rt_render.cpp)
+void fill_view(rt_context* c, int width, int height, int row_offset, int stride, int rows, rt_kparams& K);
+
+// ---- layouts of the ABI's host arrays -----------------------------------------
+// frameSum: 3 planes of npix on the device, interleaved RGB at the ABI
+inline void planes_to_rgb(const float* planes, size_t npix, float* out) {
+    for (size_t i = 0; i < npix; i++)
+        for (int ch = 0; ch < 3; ch++) out[3 * i + ch] = planes[ch * npix + i];
+}
+inline void rgb_to_planes(const float* rgb, size_t npix, float* planes) {
+    for (size_t i = 0; i < npix; i++)
+        for (int ch = 0; ch < 3; ch++) planes[ch * npix + i] = rgb[3 * i + ch];
+}
+// float4 images: .xyz as RGB triplets, .w as one plane
+inline void xyz_of(const float4* v, size_t npix, float* out) {
+    for (size_t i = 0; i < npix; i++) {
+        out[3 * i + 0] = v[i].x;
+        out[3 * i + 1] = v[i].y;
+        out[3 * i + 2] = v[i].z;
+    }
+}
+inline void w_of(const float4* v, size_t npix, void* out) {  // float or int32 bits
+    for (size_t i = 0; i < npix; i++) std::memcpy(static_cast<char*>(out) + 4 * i, &v[i].w, 4);
+}

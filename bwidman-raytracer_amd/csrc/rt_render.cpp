@@ -1,0 +1,358 @@
+// rt_render.cpp — the render calls of the C ABI (include/rt_abi.h): kernel
+// parameters of a view, the launch policy, rt_render*, single-process
+// multi-GPU rendering and the row de-interleave.
+//
+// Compiled with -ffp-contract=off: the camera prelude (Main.cu:336-338) uses
+// the reference's float operations in the reference's order.
+#include <cmath>
+
+#include "rt_context.h"
+
+static int prepare(rt_context* c, const rt_render_params* p, rt_kparams& K, unsigned& first) {
+    const HostFpEnv fp;
+    if (!c || !p) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    const int stride = p->row_stride == 0 ? 1 : p->row_stride;
+    if (p->width <= 0 || p->height <= 0 || p->samples <= 0 || p->row_offset < 0 || stride < 0 ||
+        p->row_offset >= p->height)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "bad render params %dx%d samples %d shard %d/%d", p->width,
+                    p->height, p->samples, p->row_offset, stride);
+    if (p->max_bounces < 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "max_bounces < 0");
+    if (p->max_bounces > RT_MAX_BOUNCES)
+        return fail(c, RT_ERR_UNSUPPORTED, "max_bounces %d > %d", p->max_bounces, RT_MAX_BOUNCES);
+    if (c->width != p->width || c->height != p->height || c->row_offset != p->row_offset ||
+        c->row_stride != stride || !c->rng.p) {
+        int rc = rt_init_rand(c, p->width, p->height, p->row_offset, stride);
+        if (rc) return rc;
+    }
+    first = p->first_frame ? p->first_frame : c->frame;
+    if ((unsigned long long)first + (unsigned)p->samples > 0xffffffffull)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "frame counter overflow");
+    if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
+
+    fill_view(c, p->width, p->height, p->row_offset, stride, c->rows, K);
+    K.samples = p->samples;
+    K.max_bounces = p->max_bounces;
+    K.first_frame = first;
+    K.rng = c->rng.as<unsigned>();
+    K.accum = c->accum.as<float>();
+    return RT_OK;
+}
+
+void fill_view(rt_context* c, int width, int height, int row_offset, int stride, int rows, rt_kparams& K) {
+    std::memset(&K, 0, sizeof K);
+    K.width = width;
+    K.height = height;
+    K.row_offset = row_offset;
+    K.row_stride = stride;
+    K.rows = rows;
+    // host prelude, Main.cu:336-338
+    const rt_camera& cam = c->camera;
+    K.cam_pos[0] = cam.position.x;
+    K.cam_pos[1] = cam.position.y;
+    K.cam_pos[2] = cam.position.z;
+    K.screen_z = -(float)(width / 2) / tanf(cam.fov / 2.0f);
+    {
+        const float cy = cosf(cam.angle[0]), sy = sinf(cam.angle[0]);  // rotationMatrix3DY
+        const float cx = cosf(cam.angle[1]), sx = sinf(cam.angle[1]);  // rotationMatrix3DX
+        const float L[3][3] = {{cy, 0, sy}, {0, 1, 0}, {-sy, 0, cy}};
+        const float U[3][3] = {{1, 0, 0}, {0, cx, -sx}, {0, sx, cx}};
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)  // dot(a.row(i), b.col(j)), Math.cuh:191-199
+                K.rot[3 * i + j] = L[i][0] * U[0][j] + L[i][1] * U[1][j] + L[i][2] * U[2][j];
+    }
+    K.jitter = (float)(0.001 * (width / 1000));  // Main.cu:291
+    K.bg[0] = c->background[0];
+    K.bg[1] = c->background[1];
+    K.bg[2] = c->background[2];
+    const rt_compiled_scene& sc = c->scene;
+    K.n_sph = sc.n_sph;
+    K.n_pln = sc.n_pln;
+    K.n_tri = sc.n_tri;
+    K.n_quad = sc.n_quad;
+    K.cull_omax = sc.cull_omax;
+    K.bvh_order_stride = sc.bvh_nodes_per_order * 8;
+    K.bvh_order_mask = sc.bvh_order_mask;
+    int nmax = sc.n_sph;  // Main.cu:217
+    if (sc.n_pln > nmax) nmax = sc.n_pln;
+    if (sc.n_tri > nmax) nmax = sc.n_tri;
+    if (sc.n_quad > nmax) nmax = sc.n_quad;
+    K.n_max = nmax;
+    const float* base = c->scene_buf.as<const float>();
+    K.sph = base;
+    K.pln = base + sc.off_pln;
+    K.tri = base + sc.off_tri;
+    K.quad = base + sc.off_quad;
+    K.hit = base + sc.off_hit;
+    K.bvh_nodes = sc.off_bvh ? base + sc.off_bvh : nullptr;
+    K.bvh_leafrec = sc.off_bvh ? base + sc.off_bvh_prims : nullptr;
+    K.bvh_leafvtx = sc.off_bvh ? base + sc.off_bvh_vtx : nullptr;
+    K.bvh_nodes16 = sc.off_bvh && sc.off_bvh16 ? reinterpret_cast<const unsigned*>(base + sc.off_bvh16) : nullptr;
+    K.bvh_n_nodes = sc.bvh_nodes_per_order;
+    K.ovf_sc = sc.ovf_sc;
+    K.ovf_nm = sc.ovf_nm;
+    K.ovf_im = sc.ovf_im;
+    K.cull_dmax = sc.cull_dmax;
+    K.spp_inner = c->spp_inner;
+}
+
+// The CPU backend's render: rt_cpu.cpp over the host state, synchronous
+static int cpu_render(rt_context* c, const rt_render_params* p, int threads, uint8_t* rgba_out, float* accum_out) {
+    rt_kparams K;
+    unsigned first = 0;
+    int rc = prepare(c, p, K, first);
+    if (rc) return rc;
+    const size_t npix = (size_t)c->rows * c->width;
+    K.rgba = c->rgba.as<unsigned>();
+    (void)c->render.begin(nullptr, true);
+    rt_cpu_render(K, threads > 0 ? threads : c->threads);
+    (void)c->render.end(nullptr);
+    c->frame = first + (unsigned)p->samples;  // Main.cu:480 accumulatedFrames++
+    if (rgba_out) std::memcpy(rgba_out, c->rgba.p, npix * 4);
+    if (accum_out) planes_to_rgb(c->accum.as<float>(), npix, accum_out);
+    return RT_OK;
+}
+
+static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, int samples) {
+    // wave tiles: 8 x 8 pixels; on small shards (one rank of a multi-GPU
+    // frame, below 1024 pixels per CU) 32 x 2 (config 3 at 1/8: 0.249 ->
+    // 0.244 ms); BVH scenes 4 x 16 on small shards: squarer tiles keep a
+    // wave's rays closer together (config 5: 170.4 -> 167.7 ms; at 1/8 38.5 ->
+    // 35.2).  Full brute-force frames took 16 x 4 until late in round 3; with
+    // the kernel of then, 8 x 8 is ahead (bench kernel average, config 3,
+    // three alternating runs: 0.7495 / 0.7535 / 0.7497 vs 0.7579 / 0.7616 /
+    // 0.7559 ms; c2 -3 %, c4 5.51 vs 5.53 ms; 1/2 shard -2 %, 1/4 flat;
+    // profiles/r03e/c3_knobs.txt, profiles/r03e/tiles/)
+    const bool small = (long)K.rows * K.width <= (long)c->num_cus * 1024;
+    K.tile_w = c->tile_w >= 0 ? c->tile_w : K.bvh_nodes ? (small ? 4 : 8) : (small ? 32 : 8);
+    K.tile_sq = c->tile_sq;
+    // BVH refill kernel: test the parked leaves once this many of a wave's 64
+    // lanes are ready; small shards (every wave resident at once, the frame
+    // ends with the slowest waves) batch later
+    K.leaf_batch = c->leaf_batch > 0 ? c->leaf_batch : small ? RT_LEAF_BATCH_SMALL : RT_LEAF_BATCH;
+    K.refill = c->refill > 0 ? c->refill : small ? RT_REFILL_SMALL : RT_REFILL;
+    // deep paths: the sorted kernel's record stack in global memory (launch policy)
+    K.rec = nullptr;
+    const bool fast = c->precision == RT_PRECISION_REFERENCE_FAST;
+    if (!c->simple && (c->grec == 1 || (c->grec < 0 && (fast ? rt_fast::rt_render_wants_global_records(K, c->num_cus)
+                                                             : rt_render_wants_global_records(K, c->num_cus))))) {
+        const int rc = ensure_buf(c, c->rec, rt_render_rec_floats(K) * sizeof(float));
+        if (rc) return rc;
+        K.rec = c->rec.as<float>();
+    }
+    unsigned long long* stamps = nullptr;
+    const int NST = 40;  // 8 per-phase wave-cycle sums + utilisation / branch counters
+    if (tuning_env("BWRT_STAMPS")) {  // diagnostic builds (-DRT_STAMPS)
+        if (hipMalloc(&stamps, NST * sizeof(unsigned long long)) == hipSuccess)
+            (void)hipMemsetAsync(stamps, 0, NST * sizeof(unsigned long long), s);
+        K.stamps = stamps;
+    }
+    const char* gtimes = tuning_env("BWRT_GTIMES");  // diagnostic builds (-DRT_GTIMES): group times file
+    const size_t NGT = (size_t)RT_GTIMES_WORDS;
+    if (gtimes && !stamps) {
+        if (hipMalloc(&stamps, NGT * sizeof(unsigned long long)) == hipSuccess)
+            (void)hipMemsetAsync(stamps, 0, NGT * sizeof(unsigned long long), s);
+        K.stamps = stamps;
+    }
+    // launch-order feedback: room for a grid of 64-lane groups over the
+    // padded wave tiles (any block size needs fewer groups)
+    if (c->order_feedback && !c->simple) {
+        const size_t cap = ((size_t)K.width + 128) * ((size_t)K.rows + 128) / 64 + 1;  // tiles padded to 2 x 2
+        const void* before = c->gorder.p;
+        int rc = ensure_buf(c, c->gcost, cap * sizeof(unsigned));
+        if (!rc) rc = ensure_buf(c, c->gorder, cap * sizeof(int));
+        if (rc) return rc;
+        if (c->gorder.p != before) c->order_n = 0;  // fresh buffer: no order yet
+        K.group_cost = c->gcost.as<unsigned>();
+        K.group_order = c->gorder.as<int>();
+        K.order_n = c->order_n;
+        K.order_cap = (long)(c->gorder.bytes / sizeof(int));
+        // BVH scenes re-sort every launch: their order keeps improving when
+        // sorted from costs measured under the previous order (config 5: 85.8
+        // / 86.3 / 86.1 ms every launch vs 86.7 / 87.0 / 87.0 every 16th), and
+        // the sort is 6.5 us of an 86 ms frame (profiles/r03g/order_period_configs_ab.txt)
+        K.order_sort = K.bvh_nodes || c->order_stale || c->launches % (unsigned long long)c->order_period == 0;
+        c->order_stale = false;
+    }
+    // after the last render, denoise and reprojection pass on another stream
+    int orc = order_after_all(c, s);
+    if (orc) return orc;
+    rt_order_groups_last = 0;
+    rt_launched_kernel[0] = 0;
+    // the start marker only with kernel timing on; the one end event serves
+    // both the ordering of later calls and the timing (Pass::end)
+    HIP_TRY(c, c->render.begin(s, c->ktiming));
+    hipError_t e = fast ? rt_fast::rt_launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread)
+                        : rt_launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread);
+    if (e == hipSuccess && rt_order_groups_last > 0) c->order_n = rt_order_groups_last;
+    c->kernel_name = rt_launched_kernel;
+    c->launches++;
+    if (gtimes && stamps) {
+        std::vector<unsigned long long> h(NGT);
+        (void)hipMemcpyAsync(h.data(), stamps, NGT * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+        (void)hipStreamSynchronize(s);
+        if (FILE* f = std::fopen(gtimes, "wb")) {
+            std::fwrite(h.data(), sizeof(unsigned long long), NGT, f);
+            std::fclose(f);
+        }
+        (void)hipFree(stamps);
+        stamps = nullptr;
+    }
+    if (stamps) {
+        unsigned long long h[NST] = {0};
+        (void)hipMemcpyAsync(h, stamps, sizeof h, hipMemcpyDeviceToHost, s);
+        (void)hipStreamSynchronize(s);
+        std::fprintf(stderr, "stamps");
+        for (int k = 0; k < NST; k++) std::fprintf(stderr, " %llu", h[k]);
+        std::fprintf(stderr, "\n");
+        (void)hipFree(stamps);
+    }
+    if (e != hipSuccess) return hip_fail(c, e, "rt_render_kernel launch");
+    HIP_TRY(c, c->render.end(s));
+    c->frame = first + (unsigned)samples;  // Main.cu:480 accumulatedFrames++
+    return RT_OK;
+}
+
+// The context's next `samples` frames of a shard, at its own bounce limit
+static rt_render_params next_frames(const rt_context* c, int width, int height, int samples, int row_offset,
+                                    int row_stride) {
+    rt_render_params p;
+    p.width = width;
+    p.height = height;
+    p.samples = samples;
+    p.max_bounces = c->max_bounces;
+    p.first_frame = 0;
+    p.row_offset = row_offset;
+    p.row_stride = row_stride;
+    return p;
+}
+
+extern "C" {
+
+int rt_render_ex(rt_context* c, const rt_render_params* p, uint8_t* rgba_out, float* accum_out) {
+    if (c && c->cpu) return cpu_render(c, p, 0, rgba_out, accum_out);
+    rt_kparams K;
+    unsigned first = 0;
+    int rc = prepare(c, p, K, first);
+    if (rc) return rc;
+    const size_t npix = (size_t)c->rows * c->width;
+    rc = ensure_buf(c, c->rgba, npix * 4);
+    if (rc) return rc;
+    K.rgba = c->rgba.as<unsigned>();
+    rc = launch(c, K, c->stream, first, p->samples);
+    if (rc) return rc;
+    if (rgba_out) HIP_TRY(c, hipMemcpyAsync(rgba_out, c->rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    if (accum_out) {
+        std::vector<float> planes(npix * 3);
+        HIP_TRY(c, hipMemcpyAsync(planes.data(), c->accum.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost,
+                                  c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        planes_to_rgb(planes.data(), npix, accum_out);
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
+int rt_render(rt_context* c, int width, int height, int samples, uint8_t* rgba_out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    const rt_render_params p = next_frames(c, width, height, samples, 0, 1);
+    return rt_render_ex(c, &p, rgba_out, nullptr);
+}
+
+// Single-process multi-GPU (the C++ host's counterpart of bench.py's one
+// process per GPU): context i renders rows y = i (mod n) on its own stream,
+// all launches in flight at once; the shards come back through pinned host
+// buffers and are interleaved on the host.
+int rt_render_multi(rt_context* const* ctxs, int n, int width, int height, int samples, uint8_t* rgba_out) {
+    if (!ctxs || n <= 0 || width <= 0 || height <= 0 || samples <= 0) return RT_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n; i++) {
+        if (!ctxs[i]) return RT_ERR_INVALID_ARGUMENT;
+        if (ctxs[i]->cpu) return fail(ctxs[i], RT_ERR_UNSUPPORTED, "rt_render_multi: CPU context");
+        for (int j = 0; j < i; j++)
+            if (ctxs[j] == ctxs[i]) return fail(ctxs[i], RT_ERR_INVALID_ARGUMENT, "context listed twice");
+    }
+    const int active = n < height ? n : height;  // contexts beyond the image height get no rows
+    // a failure at context i leaves contexts 0..i-1 with renders and copies
+    // into their pinned buffers in flight: drain them before returning, so a
+    // later call cannot reuse host_rgba under a running copy
+    auto drain = [&](int launched, int rc) {
+        for (int j = 0; j < launched; j++) {
+            (void)hipSetDevice(ctxs[j]->device);
+            (void)hipStreamSynchronize(ctxs[j]->stream);
+        }
+        return rc;
+    };
+    for (int i = 0; i < active; i++) {
+        rt_context* c = ctxs[i];
+        const rt_render_params p = next_frames(c, width, height, samples, i, n);
+        rt_kparams K;
+        unsigned first = 0;
+        int rc = prepare(c, &p, K, first);
+        if (rc) return drain(i, rc);
+        const size_t bytes = (size_t)c->rows * width * 4;
+        rc = ensure_buf(c, c->rgba, bytes);
+        if (rc) return drain(i, rc);
+        if (c->host_rgba_bytes < bytes) {
+            rc = quiesce(c);
+            if (rc) return drain(i, rc);
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return drain(i, fail(c, RT_ERR_HIP, "stream sync"));
+            if (c->host_rgba) (void)hipHostFree(c->host_rgba);
+            c->host_rgba = nullptr;
+            c->host_rgba_bytes = 0;
+            const hipError_t e = hipHostMalloc(&c->host_rgba, bytes, hipHostMallocDefault);
+            if (e != hipSuccess) return drain(i, hip_fail(c, e, "hipHostMalloc"));
+            c->host_rgba_bytes = bytes;
+        }
+        K.rgba = c->rgba.as<unsigned>();
+        rc = launch(c, K, c->stream, first, samples);
+        if (rc) return drain(i + 1, rc);
+        const hipError_t e = hipMemcpyAsync(c->host_rgba, c->rgba.p, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) return drain(i + 1, hip_fail(c, e, "hipMemcpyAsync"));
+    }
+    for (int i = 0; i < active; i++) {
+        rt_context* c = ctxs[i];
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (!rgba_out) continue;
+        const uint8_t* src = (const uint8_t*)c->host_rgba;
+        for (int j = 0; j < c->rows; j++)
+            std::memcpy(rgba_out + ((size_t)(i + j * n) * width) * 4, src + (size_t)j * width * 4, (size_t)width * 4);
+    }
+    return RT_OK;
+}
+
+int rt_render_device(rt_context* c, const rt_render_params* p, void* rgba_device, void* stream) {
+    if (c && c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_render_device: CPU context");
+    rt_kparams K;
+    unsigned first = 0;
+    int rc = prepare(c, p, K, first);
+    if (rc) return rc;
+    if (rgba_device && ((uintptr_t)rgba_device & 3u))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
+    K.rgba = (unsigned*)rgba_device;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return launch(c, K, s, first, p->samples);
+}
+
+int rt_deinterleave_rows_device(rt_context* c, const void* gathered, void* image, int width, int height,
+                                int shards, int rows_per_shard, void* stream) {
+    if (!c || !gathered || !image) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (width <= 0 || height <= 0 || shards <= 0 || rows_per_shard * shards < height)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "bad deinterleave geometry");
+    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_deinterleave_rows_device: CPU context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    HIP_TRY(c, rt_launch_deinterleave((const unsigned*)gathered, (unsigned*)image, width, height, shards,
+                                      rows_per_shard, c->deint_blocks, s));
+    HIP_TRY(c, c->aux.end(s));
+    return RT_OK;
+}
+
+int rt_render_cpu(rt_context* c, const rt_render_params* p, int threads, uint8_t* rgba_out, float* accum_out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->cpu) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_render_cpu: not a CPU context (rt_create_cpu)");
+    if (threads < 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "threads < 0");
+    return cpu_render(c, p, threads, rgba_out, accum_out);
+}
+
+}  // extern "C"

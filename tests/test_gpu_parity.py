@@ -1008,7 +1008,7 @@ def test_launch_order_feedback(bwrt_lib, oracle, monkeypatch, scene_name, w, h, 
         r.set_scene(scene)
         # blockIdx order first, then orders re-sorted every 2nd launch (launch 1
         # keeps launch 0's sort, launch 2 sorts again; the product re-sorts
-        # every 16th, rt_context.cpp order_period)
+        # every 16th, rt_context.h order_period)
         for _ in range(4):
             r.init_rand(w, h)
             img = r.render(w, h, spp, mb, first_frame=1)
