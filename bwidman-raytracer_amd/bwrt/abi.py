@@ -83,6 +83,14 @@ class DenoiseParams(C.Structure):
                 ("sigma_plane", C.c_float)]
 
 
+class DenoiseVarParams(C.Structure):
+    """rt_denoise_var_params: levels, the luminance sigma in standard
+    deviations, the two geometry sigmas and the batch threshold of the
+    tracked variance."""
+    _fields_ = [("iterations", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_plane", C.c_float), ("min_batches", C.c_int)]
+
+
 class TemporalParams(C.Structure):
     """rt_temporal_params: the history cap and the two tap-rejection thresholds."""
     _fields_ = [("max_history", C.c_float), ("normal_cos_min", C.c_float), ("plane_tol", C.c_float)]
@@ -146,11 +154,19 @@ def _proto(lib):
         "rt_denoise": (C.c_int, [vp, P(DenoiseParams), vp, vp]),
         "rt_denoise_device": (C.c_int, [vp, P(DenoiseParams), vp, vp]),
         "rt_last_denoise_ms": (C.c_float, [vp]),
+        "rt_denoise_var_params_default": (DenoiseVarParams, []),
+        "rt_denoise_var": (C.c_int, [vp, P(DenoiseVarParams), vp, vp, vp]),
+        "rt_denoise_var_device": (C.c_int, [vp, P(DenoiseVarParams), vp, vp]),
+        "rt_last_denoise_var_ms": (C.c_float, [vp]),
         "rt_temporal_params_default": (TemporalParams, []),
         "rt_temporal": (C.c_int, [vp, P(TemporalParams), P(DenoiseParams), vp, vp, vp]),
         "rt_temporal_device": (C.c_int, [vp, P(TemporalParams), P(DenoiseParams), vp, vp]),
         "rt_temporal_reset": (C.c_int, [vp]),
         "rt_last_temporal_ms": (C.c_float, [vp]),
+        "rt_set_moments": (C.c_int, [vp, C.c_int]),
+        "rt_get_moments": (C.c_int, [vp]),
+        "rt_moments_batches": (C.c_int, [vp]),
+        "rt_get_variance": (C.c_int, [vp, vp, vp]),
         "rt_error_string": (C.c_char_p, [C.c_int]),
         "rt_last_error": (C.c_char_p, [vp]),
         "rt_last_kernel_name": (C.c_char_p, [vp]),

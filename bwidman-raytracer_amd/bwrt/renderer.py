@@ -234,6 +234,42 @@ class Renderer:
     def last_denoise_ms(self) -> float:
         return self.lib.rt_last_denoise_ms(self.ctx)
 
+    # -- variance-guided filter -------------------------------------------------
+    def denoise_var_params(self, iterations=None, sigma_lum=None, sigma_normal=None, sigma_plane=None,
+                           min_batches=None):
+        """rt_denoise_var_params_default() with the given fields replaced."""
+        d = self.lib.rt_denoise_var_params_default()
+        for name, v in (("iterations", iterations), ("sigma_lum", sigma_lum), ("sigma_normal", sigma_normal),
+                        ("sigma_plane", sigma_plane), ("min_batches", min_batches)):
+            if v is not None:
+                setattr(d, name, v)
+        return d
+
+    def denoise_var(self, width, height, want_color=False, want_var=False, **params):
+        """rt_denoise_var: the variance-guided a-trous filter over the
+        accumulated full frame (width x height: the shape of the last render);
+        `params` are denoise_var_params() fields.  Returns the RGBA8 image,
+        with want_color / want_var also the filtered linear colour (H, W, 3)
+        and the filtered variance of the mean luminance (H, W), in that order."""
+        d = self.denoise_var_params(**params)
+        out = np.empty((height, width, 4), np.uint8)
+        col = np.empty((height, width, 3), np.float32) if want_color else None
+        var = np.empty((height, width), np.float32) if want_var else None
+        self._check(self.lib.rt_denoise_var(self.ctx, C.byref(d), out.ctypes.data,
+                                            col.ctypes.data if col is not None else None,
+                                            var.ctypes.data if var is not None else None))
+        res = (out,) + ((col,) if want_color else ()) + ((var,) if want_var else ())
+        return res if len(res) > 1 else out
+
+    def denoise_var_device(self, rgba_ptr: int, stream_ptr: int | None = None, **params):
+        """rt_denoise_var_device: the filtered RGBA8 into device memory on a
+        stream (asynchronous; ordered after the last render on the device)."""
+        d = self.denoise_var_params(**params)
+        self._check(self.lib.rt_denoise_var_device(self.ctx, C.byref(d), rgba_ptr, stream_ptr))
+
+    def last_denoise_var_ms(self) -> float:
+        return self.lib.rt_last_denoise_var_ms(self.ctx)
+
     # -- temporal reprojection ------------------------------------------------
     def temporal_params(self, max_history=None, normal_cos_min=None, plane_tol=None):
         """rt_temporal_params_default() with the given fields replaced."""
@@ -279,6 +315,30 @@ class Renderer:
 
     def last_temporal_ms(self) -> float:
         return self.lib.rt_last_temporal_ms(self.ctx)
+
+    # -- luminance moment tracking ---------------------------------------------
+    def set_moments(self, enable: bool = True):
+        """rt_set_moments: track per-pixel luminance moments behind every render
+        call (one batch per call); live from the next render of frame 1."""
+        self._check(self.lib.rt_set_moments(self.ctx, int(bool(enable))))
+
+    @property
+    def moments(self) -> bool:
+        return bool(self.lib.rt_get_moments(self.ctx))
+
+    @property
+    def moments_batches(self) -> int:
+        """Tracked render calls J of the current accumulation (0: not live)."""
+        return self.lib.rt_moments_batches(self.ctx)
+
+    def variance(self, rows, width, want_lum=False):
+        """rt_get_variance: the (rows, width) unbiased estimate of the variance
+        of each pixel's mean luminance after the accumulated frames (needs two
+        tracked render calls); with want_lum also that mean luminance."""
+        var = np.empty((rows, width), np.float32)
+        lum = np.empty((rows, width), np.float32) if want_lum else None
+        self._check(self.lib.rt_get_variance(self.ctx, var.ctypes.data, lum.ctypes.data if want_lum else None))
+        return (var, lum) if want_lum else var
 
     # -- checkpoint / resume -----------------------------------------------
     def get_state(self, rows, width):

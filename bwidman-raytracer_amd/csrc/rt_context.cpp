@@ -65,7 +65,7 @@ int hip_fail(rt_context* c, hipError_t e, const char* what) {
 int quiesce(rt_context* c) {
     if (c->cpu) return RT_OK;
     HIP_TRY(c, c->render.flush());
-    for (Pass* p : {&c->denoise, &c->temporal, &c->render}) HIP_TRY(c, p->sync());
+    for (Pass* p : {&c->denoise, &c->temporal, &c->denoise_var, &c->render}) HIP_TRY(c, p->sync());
     return RT_OK;
 }
 
@@ -74,7 +74,7 @@ int quiesce(rt_context* c) {
 // of any of the three on stream s waits for the last of each that ran on
 // another stream (no host sync)
 int order_after_all(rt_context* c, hipStream_t s) {
-    for (Pass* p : {&c->render, &c->denoise, &c->temporal}) HIP_TRY(c, p->wait_on(s));
+    for (Pass* p : {&c->render, &c->denoise, &c->temporal, &c->denoise_var}) HIP_TRY(c, p->wait_on(s));
     return RT_OK;
 }
 
@@ -192,7 +192,7 @@ int rt_create_cpu(int threads, rt_context** out) {
     if (!rt_cpu_supported()) return RT_ERR_UNSUPPORTED;
     rt_context* c = new rt_context();
     c->cpu = true;
-    c->render.host = c->denoise.host = c->temporal.host = true;
+    c->render.host = c->denoise.host = c->temporal.host = c->denoise_var.host = true;
     c->device = -1;
     c->threads = threads > 0 ? threads : rt_cpu_threads();
     *out = c;
@@ -227,7 +227,7 @@ void rt_destroy(rt_context* c) {
         (void)hipSetDevice(c->device);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
         c->render.pending = false;  // its launch is done: the stream is synchronised
-        for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal}) {
+        for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var}) {
             (void)p->sync();
             p->destroy();
         }
@@ -441,6 +441,7 @@ int rt_init_rand(rt_context* c, int width, int height, int row_offset, int row_s
     const int rows = shard_rows(height, row_offset, row_stride);
     const size_t npix = (size_t)rows * width;
     c->new_view();  // the guides are those of one frame shape
+    c->mom_drop();  // the moments are those of one shard
     if (width != c->tp_w || height != c->tp_h) c->tp_has_hist = c->tp_has_pending = false;
     if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
     int rc = quiesce(c);  // a render on a caller's stream may still use the state
@@ -477,7 +478,7 @@ int rt_synchronize(rt_context* c) {
     // marks the last render (later renders on a caller's stream wait on it)
     HIP_TRY(c, c->render.flush());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal}) HIP_TRY(c, p->sync());
+    for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var}) HIP_TRY(c, p->sync());
     return RT_OK;
 }
 
@@ -516,6 +517,7 @@ int rt_set_state(rt_context* c, const uint32_t* rng, const float* accum, unsigne
         if (rng) std::memcpy(c->rng.p, rng, npix * 6 * sizeof(unsigned));
         if (accum) rgb_to_planes(accum, npix, c->accum.as<float>());
         c->frame = frame_counter;
+        c->mom_drop();
         return RT_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -532,6 +534,7 @@ int rt_set_state(rt_context* c, const uint32_t* rng, const float* accum, unsigne
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->frame = frame_counter;
+    c->mom_drop();  // frameSum is no longer the sum the moments followed
     return RT_OK;
 }
 

@@ -4,7 +4,7 @@
 //
 //   rt_context.cpp  create / destroy, setters, controls, state, errors
 //   rt_render.cpp   prepare, fill_view, launch, rt_render*, multi-GPU, de-interleave
-//   rt_post.cpp     first-hit features, denoiser, temporal reprojection
+//   rt_post.cpp     first-hit features, denoiser, temporal reprojection, moment readout
 //   rt_scene.cpp    the scene compiler (rt_scene.h; no HIP, no context)
 #pragma once
 
@@ -47,6 +47,8 @@ bool rt_cpu_supported();
 void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb);
 void rt_cpu_denoise_level(const rt_dn_level& L, int threads);
 void rt_cpu_temporal(const rt_tp_args& T, int threads);
+void rt_cpu_moments(const rt_mom_args& A, int threads);
+void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads);
 // first-hit feature kernel (rt_kernels.hip; the BVH walk in rt_kernels_bvh.hip) and the
 // a-trous filter (rt_denoise.hip)
 hipError_t rt_launch_aov(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream);
@@ -54,6 +56,10 @@ hipError_t rt_launch_aov_bvh(const rt_kparams& K, float4* ga, float4* gb, float4
 hipError_t rt_launch_denoise_level(const rt_dn_level& L, bool tiled, hipStream_t stream);
 // temporal reprojection (rt_temporal.hip)
 hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream);
+// luminance moment update (rt_moments.hip)
+hipError_t rt_launch_moments(const rt_mom_args& A, hipStream_t stream);
+// variance-guided filter (rt_denoise_var.hip): stage 0 input, 1 sigma pass, 2 level
+hipError_t rt_launch_denoise_var(const rt_dv_args& A, int stage, bool tiled, hipStream_t stream);
 
 // ---- buffers -------------------------------------------------------------------
 // Device memory on a GPU context, host memory on a CPU context (ensure_buf);
@@ -171,8 +177,10 @@ struct rt_context {
     // aux: the last de-interleave (rt_synchronize waits for it; it touches no
     // state).  denoise: its levels read frameSum and share the guides and
     // colour buffers.  temporal: the reprojection pass, likewise; its events
-    // are created by the first temporal call.
-    Pass render, aux, denoise, temporal;
+    // are created by the first temporal call.  denoise_var: the
+    // variance-guided filter, which shares the guides and colour buffers with
+    // the denoiser; its events are created by its first call.
+    Pass render, aux, denoise, temporal, denoise_var;
     // CPU backend (rt_create_cpu): host buffers, and the scalar fallback of
     // rt_cpu.cpp instead of the kernels
     bool cpu = false;
@@ -228,6 +236,7 @@ struct rt_context {
     // {n.xyz, prim} / {P.xyz, depth}, valid until the scene, the camera or the
     // frame shape changes, and two ping-pong colour buffers
     Buf guide_a, guide_b, dn_col[2], dn_rgba;
+    Buf dn_rs;  // rt_denoise_var: the reciprocal luminance sigma, one float per pixel
     Buf aov_a, aov_b, aov_alb;  // rt_render_aov scratch (any shard; GPU contexts)
     bool guides_valid = false;
     int dn_kernel = -1;  // BWRT_DENOISE_KERNEL: 0 direct, 1 tiled, -1 = the measured per-level policy
@@ -248,6 +257,21 @@ struct rt_context {
     bool tp_has_hist = false, tp_has_pending = false;
     unsigned long long tp_pending_view = 0;
     int tp_w = 0, tp_h = 0;  // frame shape of both sets
+
+    // luminance moment tracking (rt_set_moments): a copy of frameSum before
+    // the last tracked batch (3 planes) and {M, M2} per shard pixel, updated
+    // by one pass behind every render call while `mom_live`.  Tracking goes
+    // live at a render whose first frame is 1 and stays live while each render
+    // starts at mom_next, the frame after the last tracked one; mom_batches
+    // counts the tracked render calls (J).  Nothing is allocated before
+    // tracking is on and a render runs.
+    bool mom_on = false, mom_live = false;
+    unsigned mom_batches = 0, mom_next = 0;
+    Buf mom_prev, mom_m;
+    void mom_drop() {
+        mom_live = false;
+        mom_batches = 0;
+    }
 
     // a new view (scene, camera, frame shape): the guides are stale
     void new_view() {
@@ -286,9 +310,9 @@ int hip_fail(rt_context* c, hipError_t e, const char* what);
     } while (0)
 
 // Host-side wait for every pass that uses the shard state (render, denoise,
-// temporal), on whatever streams they ran; no-op on a CPU context
+// temporal, variance-guided denoise), on whatever streams they ran; no-op on a CPU context
 int quiesce(rt_context* c);
-// Order stream s after the same three passes (no host sync)
+// Order stream s after the same passes (no host sync)
 int order_after_all(rt_context* c, hipStream_t s);
 // At least `bytes` in b (never shrinks).  A CPU context allocates host
 // memory; its failure is RT_ERR_OUT_OF_MEMORY with the message host_oom

@@ -227,6 +227,8 @@ int rt_cpu_render(const rt_kparams& K, int threads) {
 
 // ---- first-hit features and the a-trous filter on the host -------------------
 #include "rt_denoise.h"
+#include "rt_denoise_var.h"
+#include "rt_moments.h"
 #include "rt_temporal.h"
 
 namespace {
@@ -313,5 +315,27 @@ void rt_cpu_temporal(const rt_tp_args& T, int threads) {
     parallel_items((long)T.width * T.height, threads, [&](long p) {
         const int y = (int)(p / T.width);
         tp_run_pixel(T, (int)(p - (long)y * T.width), y);
+    });
+}
+
+// The luminance moment update of one render call (rt_moments.h), on the same pool
+void rt_cpu_moments(const rt_mom_args& A, int threads) {
+    parallel_items(A.npix, threads, [&](long p) { mom_update(A, p); });
+}
+
+// One pass of the variance-guided filter (rt_denoise_var.h): stage 0 the input
+// stage, 1 a sigma pass, 2 a level
+void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads) {
+    parallel_items((long)A.width * A.height, threads, [&](long p) {
+        const int y = (int)(p / A.width);
+        const int x = (int)(p - (long)y * A.width);
+        if (stage == 0) {
+            dv_store(A, p, dv_input(A, x, y));
+        } else if (stage == 1) {
+            A.rs[p] = dv_sigma(A, x, y);
+        } else {
+            const DvGlobalFetch fetch{A};
+            dv_store(A, p, dv_pixel(A, x, y, fetch));
+        }
     });
 }

@@ -204,3 +204,38 @@ struct rt_tp_args {
     float4* p_gb;
     unsigned* rgba;      // tone_map(out, 1) when non-null
 };
+
+// One luminance-moment update (rt_moments.h) over the npix pixels of the
+// context's shard: the batch of k frames first .. first + k - 1 that a render
+// call just added to frameSum.
+struct rt_mom_args {
+    long npix;
+    int first;           // the batch starts the accumulation (frame 1): prev, M, M2 count as 0 and are not read
+    float kf;            // (float)k
+    float invk;          // 1.0f / kf
+    float kw;            // kf / (float)(n0 + k), n0 = frames accumulated before the batch
+    const float* accum;  // frameSum after the batch, 3 planes of npix
+    float* prev;         // frameSum before the batch, same layout; becomes frameSum
+    float2* mom;         // {M, M2}: weighted mean of the batch luminances and sum of k_j (l_j - mean)^2
+};
+
+// One pass of the variance-guided filter (rt_denoise_var.h) over a full width
+// x height frame: the input stage, a sigma pass or a level.
+struct rt_dv_args {
+    int width, height;
+    int step;            // level: 1 << level
+    int last;            // input stage and level: also write tone_map(c, 1) to rgba (when non-null)
+    int tracked;         // input stage: v0 from the tracked moments, else the spatial estimate
+    float in, ip;        // 1 / sigma^2 of the normal and plane terms
+    float inv;           // 1 / n, n = frame counter - 1
+    float rd;            // tracked: 1 / ((J - 1) n)
+    float sigma_lum;     // sigma pass
+    const float* accum;  // input stage: frameSum, 3 planes of width * height
+    const float2* mom;   // input stage, tracked: {M, M2}
+    const float4* src;   // sigma pass and level: {colour, variance} of the previous stage
+    float4* dst;         // input stage and level: {colour, variance}
+    float* rs;           // reciprocal luminance sigma: the sigma pass writes it, the level reads its centre
+    unsigned* rgba;
+    const float4* ga;    // guides {n.xyz, prim as bits}
+    const float4* gb;    //        {P.xyz, depth}
+};

@@ -147,6 +147,89 @@ int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_t s, un
     return RT_OK;
 }
 
+// The variance-guided filter (rt_denoise_var.h) of one call on stream s: the
+// input stage, then per level a sigma pass and the level.  The final {colour,
+// variance} ends in dn_col[*final_buf] and, tone-mapped, in rgba (device
+// pointer on a GPU context; may be null).
+int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream_t s, unsigned* rgba,
+                       int* final_buf) {
+    const HostFpEnv fp;
+    if (!c || !dp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (dp->iterations < 0 || dp->iterations > RT_DENOISE_MAX_ITERATIONS)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "iterations %d outside 0..%d", dp->iterations,
+                    RT_DENOISE_MAX_ITERATIONS);
+    if (!(dp->sigma_lum > 0.0f) || !(dp->sigma_normal > 0.0f) || !(dp->sigma_plane > 0.0f))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "sigmas must be > 0 (luminance %g, normal %g, plane %g)",
+                    (double)dp->sigma_lum, (double)dp->sigma_normal, (double)dp->sigma_plane);
+    if (dp->min_batches < 2) return fail(c, RT_ERR_INVALID_ARGUMENT, "min_batches %d < 2", dp->min_batches);
+    int rc = full_frame_check(c, "the denoiser");
+    if (rc) return rc;
+    const size_t npix = (size_t)c->height * c->width;
+    if (!c->cpu) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, c->denoise_var.create(true));  // on first use
+    }
+    for (Buf& b : c->dn_col)
+        if ((rc = ensure_buf(c, b, npix * sizeof(float4), "host colour buffers for %zu pixels", npix))) return rc;
+    if ((rc = ensure_buf(c, c->dn_rs, npix * sizeof(float), "host sigma plane for %zu pixels", npix))) return rc;
+    // after the render that made the frame (and its moment update), and after
+    // every pass that shares the guides and the colour buffers
+    if ((rc = order_after_all(c, s))) return rc;
+    rc = ensure_guides(c, s);
+    if (rc) return rc;
+    rt_dv_args A;
+    std::memset(&A, 0, sizeof A);
+    A.width = c->width;
+    A.height = c->height;
+    const float n = (float)(c->frame - 1u);
+    A.inv = 1.0f / n;
+    A.in = 1.0f / (dp->sigma_normal * dp->sigma_normal);
+    A.ip = 1.0f / (dp->sigma_plane * dp->sigma_plane);
+    A.sigma_lum = dp->sigma_lum;
+    // the tracked variance of this very frame, else the spatial estimate
+    A.tracked = c->mom_live && c->mom_next == c->frame && c->mom_batches >= (unsigned)dp->min_batches;
+    if (A.tracked) {
+        A.rd = 1.0f / ((float)(c->mom_batches - 1u) * n);
+        A.mom = c->mom_m.as<float2>();
+    }
+    A.accum = c->accum.as<float>();
+    A.ga = c->guide_a.as<float4>();
+    A.gb = c->guide_b.as<float4>();
+    A.rs = c->dn_rs.as<float>();
+    float4* col[2] = {c->dn_col[0].as<float4>(), c->dn_col[1].as<float4>()};
+    auto pass = [&](int stage) -> int {
+        if (c->cpu) {
+            rt_cpu_denoise_var(A, stage, c->threads);
+            return RT_OK;
+        }
+        // BWRT_DENOISE_KERNEL forces a variant; the policy is the per-level
+        // winner of tools/time_denoise_var.py at 1920x1080 (profiles/denoise_var/,
+        // DESIGN.md section 11; sigma pass included): the LDS-tiled kernel up to
+        // step 16 (0.120-0.171 against 0.195-0.206 ms), the direct one at step 32
+        // (0.236 against 0.346 ms)
+        const bool tiled = c->dn_kernel >= 0 ? c->dn_kernel == 1 : A.step <= 16;
+        HIP_TRY(c, rt_launch_denoise_var(A, stage, tiled, s));
+        return RT_OK;
+    };
+    HIP_TRY(c, c->denoise_var.begin(s, true));
+    const int levels = dp->iterations;
+    A.dst = col[0];
+    A.last = levels == 0;
+    A.rgba = A.last ? rgba : nullptr;
+    if ((rc = pass(0))) return rc;
+    for (int i = 0; i < levels; i++) {
+        A.step = 1 << i;
+        A.src = col[i & 1];
+        A.dst = col[(i + 1) & 1];
+        A.last = i == levels - 1;
+        A.rgba = A.last ? rgba : nullptr;
+        if ((rc = pass(1)) || (rc = pass(2))) return rc;
+    }
+    *final_buf = levels & 1;
+    HIP_TRY(c, c->denoise_var.end(s));
+    return RT_OK;
+}
+
 static int temporal_check(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn) {
     if (!c || !tp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
     if (!(tp->max_history > 0.0f) || !(tp->plane_tol > 0.0f) ||
@@ -332,6 +415,43 @@ int rt_denoise_device(rt_context* c, const rt_denoise_params* dp, void* rgba_dev
 
 float rt_last_denoise_ms(rt_context* c) { return c ? c->denoise.elapsed_ms() : -1.0f; }
 
+// ---- variance-guided filter ------------------------------------------------------
+// (csrc/rt_denoise_var.h has the arithmetic)
+
+rt_denoise_var_params rt_denoise_var_params_default(void) {
+    rt_denoise_var_params d;
+    d.iterations = 5;
+    // tools/denoise_var_sweep.py: on 8-frame estimates
+    // the grid prefers a far wider luminance term than SVGF's 4
+    d.sigma_lum = 32.0f;
+    d.sigma_normal = 0.5f;
+    d.sigma_plane = 0.1f;
+    d.min_batches = 4;
+    return d;
+}
+
+int rt_denoise_var(rt_context* c, const rt_denoise_var_params* dp, uint8_t* rgba_out, float* color_out,
+                   float* var_out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    const size_t npix = (size_t)c->height * c->width;
+    int fb = 0;
+    int rc = ensure_rgba(c, rgba_out, npix);
+    if (!rc) rc = denoise_var_passes(c, dp, c->stream, rgba_out ? c->dn_rgba.as<unsigned>() : nullptr, &fb);
+    if (rc) return rc;
+    return read_back(c, npix, rgba_out, &c->dn_col[fb], color_out, &c->dn_col[fb], var_out);
+}
+
+int rt_denoise_var_device(rt_context* c, const rt_denoise_var_params* dp, void* rgba_device, void* stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_denoise_var_device: CPU context");
+    if (rgba_device && ((uintptr_t)rgba_device & 3u))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
+    int fb = 0;
+    return denoise_var_passes(c, dp, stream ? (hipStream_t)stream : c->stream, (unsigned*)rgba_device, &fb);
+}
+
+float rt_last_denoise_var_ms(rt_context* c) { return c ? c->denoise_var.elapsed_ms() : -1.0f; }
+
 // ---- temporal reprojection ----------------------------------------------------
 // (csrc/rt_temporal.h has the arithmetic)
 
@@ -374,5 +494,56 @@ int rt_temporal_reset(rt_context* c) {
 }
 
 float rt_last_temporal_ms(rt_context* c) { return c ? c->temporal.elapsed_ms() : -1.0f; }
+
+// ---- luminance moment tracking ------------------------------------------------
+// (csrc/rt_moments.h has the update, rt_render.cpp runs
+// it behind every render call)
+
+int rt_set_moments(rt_context* c, int enable) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    const bool on = enable != 0;
+    // off ends the tracking; on starts not live (a render of frame 1 makes it
+    // live), also in mid-accumulation.  The buffers stay for the next use.
+    if (on != c->mom_on) c->mom_drop();
+    c->mom_on = on;
+    return RT_OK;
+}
+
+int rt_get_moments(const rt_context* c) { return c && c->mom_on ? 1 : 0; }
+
+int rt_moments_batches(const rt_context* c) { return c && c->mom_live ? (int)c->mom_batches : 0; }
+
+int rt_get_variance(rt_context* c, float* var_out, float* lum_out) {
+    const HostFpEnv fp;
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->mom_live || c->mom_batches < 2u)
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "no variance yet: moment tracking %s, %u batches (needs rt_set_moments and two render calls "
+                    "of one accumulation)",
+                    c->mom_live ? "live" : "not live", c->mom_live ? c->mom_batches : 0u);
+    const size_t npix = (size_t)c->rows * c->width;
+    const float2* m = c->mom_m.as<float2>();
+    std::vector<float2> host;
+    if (!c->cpu) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        try {
+            host.resize(npix);
+        } catch (...) {
+            return fail(c, RT_ERR_OUT_OF_MEMORY, "host moments for %zu pixels", npix);
+        }
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        const int rc = quiesce(c);  // the last render (and its update pass), on whatever stream it ran
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(host.data(), m, npix * sizeof(float2), hipMemcpyDeviceToHost));
+        m = host.data();
+    }
+    // 1 / ((J - 1) n), n = the frames accumulated
+    const float rd = 1.0f / ((float)(c->mom_batches - 1u) * (float)(c->mom_next - 1u));
+    for (size_t i = 0; i < npix; i++) {
+        if (var_out) var_out[i] = m[i].y * rd;
+        if (lum_out) lum_out[i] = m[i].x;
+    }
+    return RT_OK;
+}
 
 }  // extern "C"

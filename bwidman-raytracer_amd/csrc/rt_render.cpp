@@ -96,6 +96,44 @@ void fill_view(rt_context* c, int width, int height, int row_offset, int stride,
     K.spp_inner = c->spp_inner;
 }
 
+// Luminance moment tracking (rt_set_moments, rt_moments.h) of the call that
+// renders frames first .. first + samples - 1: whether it is tracked (`run`),
+// its buffers and the arguments of its update pass.  Tracking goes live at a
+// render that starts the accumulation and stays live while every render
+// starts at the frame after the last tracked one; any other render ends it.
+static int moments_prepare(rt_context* c, unsigned first, int samples, rt_mom_args& A, bool& run) {
+    run = c->mom_on && (first == 1u || (c->mom_live && first == c->mom_next));
+    if (!run) {
+        c->mom_drop();
+        return RT_OK;
+    }
+    const size_t npix = (size_t)c->rows * c->width;
+    const char* oom = "host moments for %zu pixels";
+    int rc = ensure_buf(c, c->mom_prev, npix * 3 * sizeof(float), oom, npix);
+    if (!rc) rc = ensure_buf(c, c->mom_m, npix * sizeof(float2), oom, npix);
+    if (rc) {
+        c->mom_drop();
+        return rc;
+    }
+    const HostFpEnv fp;
+    A.npix = (long)npix;
+    A.first = first == 1u;
+    A.kf = (float)samples;
+    A.invk = 1.0f / A.kf;
+    A.kw = A.kf / (float)(first - 1u + (unsigned)samples);
+    A.accum = c->accum.as<float>();
+    A.prev = c->mom_prev.as<float>();
+    A.mom = c->mom_m.as<float2>();
+    return RT_OK;
+}
+
+static void moments_commit(rt_context* c, unsigned first, int samples) {
+    if (first == 1u) c->mom_batches = 0;
+    c->mom_live = true;
+    c->mom_batches++;
+    c->mom_next = first + (unsigned)samples;
+}
+
 // The CPU backend's render: rt_cpu.cpp over the host state, synchronous
 static int cpu_render(rt_context* c, const rt_render_params* p, int threads, uint8_t* rgba_out, float* accum_out) {
     rt_kparams K;
@@ -104,8 +142,15 @@ static int cpu_render(rt_context* c, const rt_render_params* p, int threads, uin
     if (rc) return rc;
     const size_t npix = (size_t)c->rows * c->width;
     K.rgba = c->rgba.as<unsigned>();
+    rt_mom_args MA;
+    bool track = false;
+    if ((rc = moments_prepare(c, first, p->samples, MA, track))) return rc;
     (void)c->render.begin(nullptr, true);
     rt_cpu_render(K, threads > 0 ? threads : c->threads);
+    if (track) {
+        rt_cpu_moments(MA, threads > 0 ? threads : c->threads);
+        moments_commit(c, first, p->samples);
+    }
     (void)c->render.end(nullptr);
     c->frame = first + (unsigned)p->samples;  // Main.cu:480 accumulatedFrames++
     if (rgba_out) std::memcpy(rgba_out, c->rgba.p, npix * 4);
@@ -174,6 +219,10 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
         K.order_sort = K.bvh_nodes || c->order_stale || c->launches % (unsigned long long)c->order_period == 0;
         c->order_stale = false;
     }
+    // moment tracking: its buffers before anything is queued
+    rt_mom_args MA;
+    bool track = false;
+    if (const int rc = moments_prepare(c, first, samples, MA, track)) return rc;
     // after the last render, denoise and reprojection pass on another stream
     int orc = order_after_all(c, s);
     if (orc) return orc;
@@ -207,7 +256,22 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
         std::fprintf(stderr, "\n");
         (void)hipFree(stamps);
     }
-    if (e != hipSuccess) return hip_fail(c, e, "rt_render_kernel launch");
+    if (e != hipSuccess) {
+        c->mom_drop();
+        return hip_fail(c, e, "rt_render_kernel launch");
+    }
+    // the moment update of this call's batch: behind the render kernel on the
+    // same stream and inside the render pass, so the pass's one end event (or
+    // none, between back-to-back renders on the context's stream) orders every
+    // later call after it and no packet of its own goes on the stream
+    if (track) {
+        e = rt_launch_moments(MA, s);
+        if (e != hipSuccess) {
+            c->mom_drop();
+            return hip_fail(c, e, "rt_moments_kernel launch");
+        }
+        moments_commit(c, first, samples);
+    }
     HIP_TRY(c, c->render.end(s));
     c->frame = first + (unsigned)samples;  // Main.cu:480 accumulatedFrames++
     return RT_OK;

@@ -17,7 +17,8 @@
 
 #include "rt_scene.h"
 
-struct float4;  // rt_layout.h names it in pointer members only; no HIP header here
+struct float4;  // rt_layout.h names them in pointer members only; no HIP header here
+struct float2;
 #include "rt_layout.h"
 
 namespace {

@@ -13,7 +13,7 @@
 //               [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]
 //               [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]
 //               [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]
-//               [--aov PREFIX]
+//               [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]
 //
 // --keys: comma-separated steps KEY[+KEY...]*FRAMES (keys W A S D SPACE
 // LEFT_SHIFT LEFT RIGHT UP DOWN ESCAPE; an empty key list holds nothing);
@@ -39,7 +39,17 @@
 // --aov PREFIX writes the first-hit feature buffers (rt_render_aov) as
 // PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5) and PREFIX_depth (1 / (1 +
 // depth), a miss black) images in --out's format (PNG without --out).
+// --moments turns the luminance moment tracking on (rt_set_moments: one batch
+// per render call, so it needs --frames-per-call below --frames) and prints
+// the tracked batches and the frame's mean relative standard error; --aov
+// PREFIX then also writes PREFIX_var, the standard error s = sqrt(variance of
+// the pixel's mean luminance) as s / (1 + s) (one context only).
+// --denoise-var [N] turns the tracking on and filters the final frame with
+// rt_denoise_var (N levels; --sigma-lum, --min-batches, --sigma-normal and
+// --sigma-plane replace the fields of rt_denoise_var_params_default()); it
+// cannot be combined with --denoise (and so not with --temporal's filter).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -64,7 +74,7 @@ static const char* kUsage =
     "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n"
     "                   [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]\n"
     "                   [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]\n"
-    "                   [--aov PREFIX]\n";
+    "                   [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]\n";
 
 struct KeyStep {
     unsigned keys;
@@ -128,6 +138,8 @@ int main(int argc, char** argv) {
     bool temporal = false;
     rt_temporal_params tp = rt_temporal_params_default();
     std::string aov;
+    bool moments = false, denoise_var = false;
+    rt_denoise_var_params dv = rt_denoise_var_params_default();
     for (int i = 1; i < argc; i++) {
         auto next = [&](void) -> const char* { return i + 1 < argc ? argv[++i] : ""; };
         if (!std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h")) {
@@ -171,17 +183,28 @@ int main(int argc, char** argv) {
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn.iterations = std::atoi(argv[++i]);
         }
         else if (!std::strcmp(argv[i], "--sigma-color")) dn.sigma_color = (float)std::atof(next());
-        else if (!std::strcmp(argv[i], "--sigma-normal")) dn.sigma_normal = (float)std::atof(next());
-        else if (!std::strcmp(argv[i], "--sigma-plane")) dn.sigma_plane = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--sigma-normal")) dn.sigma_normal = dv.sigma_normal = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--sigma-plane")) dn.sigma_plane = dv.sigma_plane = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--denoise-var")) {
+            denoise_var = moments = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dv.iterations = std::atoi(argv[++i]);
+        }
+        else if (!std::strcmp(argv[i], "--sigma-lum")) dv.sigma_lum = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--min-batches")) dv.min_batches = std::atoi(next());
         else if (!std::strcmp(argv[i], "--temporal")) temporal = true;
         else if (!std::strcmp(argv[i], "--max-history")) tp.max_history = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--normal-cos")) tp.normal_cos_min = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--plane-tol")) tp.plane_tol = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--aov")) aov = next();
+        else if (!std::strcmp(argv[i], "--moments")) moments = true;
         else {
             std::fprintf(stderr, "unknown option %s\n%s", argv[i], kUsage);
             return 2;
         }
+    }
+    if (denoise && denoise_var) {
+        std::fprintf(stderr, "--denoise and --denoise-var cannot be combined: one filter writes the frame\n");
+        return 2;
     }
     std::vector<KeyStep> steps;
     if (!keys_spec.empty()) {
@@ -225,6 +248,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--temporal needs one context (a frame gathered from several GPUs is not reprojected)\n");
         return 2;
     }
+    if (moments && gpus != 1) {
+        std::fprintf(stderr, "--moments needs one context (each GPU of a gathered frame tracks its own rows)\n");
+        return 2;
+    }
     const int ndev = cpu_threads >= 0 ? 1 : rt_device_count() > 0 ? rt_device_count() : 1;
     std::vector<rt_context*> ctxs(gpus, nullptr);
     int rc = 0;
@@ -241,6 +268,7 @@ int main(int argc, char** argv) {
         if ((rc = rt_set_scene(ctxs[g], &view))) return die(ctxs[g], rc, "rt_set_scene");
         if ((rc = rt_set_max_bounces(ctxs[g], max_bounces))) return die(ctxs[g], rc, "rt_set_max_bounces");
         if ((rc = rt_set_background(ctxs[g], bg[0], bg[1], bg[2]))) return die(ctxs[g], rc, "rt_set_background");
+        if (moments && (rc = rt_set_moments(ctxs[g], 1))) return die(ctxs[g], rc, "rt_set_moments");
     }
     rt_context* ctx = ctxs[0];
     std::vector<uint8_t> rgba((size_t)width * height * 4);
@@ -301,6 +329,37 @@ int main(int argc, char** argv) {
         if ((rc = rt_denoise(ctx, &dn, rgba.data(), nullptr))) return die(ctx, rc, "rt_denoise");
         std::printf("denoise: %d levels, %.3f ms\n", dn.iterations, rt_last_denoise_ms(ctx));
     }
+    if (denoise_var) {
+        const int batches = rt_moments_batches(ctx);
+        if ((rc = rt_denoise_var(ctx, &dv, rgba.data(), nullptr, nullptr))) return die(ctx, rc, "rt_denoise_var");
+        if (batches >= dv.min_batches)
+            std::printf("denoise-var: %d levels, tracked variance of %d batches, %.3f ms\n", dv.iterations, batches,
+                        rt_last_denoise_var_ms(ctx));
+        else
+            std::printf("denoise-var: %d levels, spatial variance (%d batches < %d), %.3f ms\n", dv.iterations,
+                        batches, dv.min_batches, rt_last_denoise_var_ms(ctx));
+    }
+    std::vector<float> var;  // of the mean luminance, per pixel
+    if (moments) {
+        const int batches = rt_moments_batches(ctx);
+        std::printf("moments: %d batches", batches);
+        if (batches >= 2 || !aov.empty()) {
+            const size_t npix = (size_t)width * height;
+            std::vector<float> lum(npix);
+            var.resize(npix);
+            if ((rc = rt_get_variance(ctx, var.data(), lum.data()))) {
+                std::printf("\n");
+                return die(ctx, rc, "rt_get_variance");
+            }
+            double se = 0.0, mean = 0.0;
+            for (size_t i = 0; i < npix; i++) {
+                se += std::sqrt((double)var[i]);
+                mean += lum[i];
+            }
+            std::printf(", mean standard error %.4g of mean luminance %.4g", se / (double)npix, mean / (double)npix);
+        }
+        std::printf("\n");
+    }
     if (!aov.empty()) {
         const size_t npix = (size_t)width * height;
         std::vector<float> albedo(npix * 3), normal(npix * 3), depth(npix);
@@ -313,15 +372,18 @@ int main(int argc, char** argv) {
         const bool ppm = out.size() > 4 && out.compare(out.size() - 4, 4, ".ppm") == 0;
         auto u8 = [](float v) { return (uint8_t)(v >= 1.0f ? 255 : v > 0.0f ? (int)(v * 255.0f + 0.5f) : 0); };
         std::vector<uint8_t> img(npix * 4);
-        for (int k = 0; k < 3; k++) {
+        for (int k = 0; k < (moments ? 4 : 3); k++) {
             for (size_t i = 0; i < npix; i++) {
+                const float se = k == 3 ? std::sqrt(var[i]) : 0.0f;
                 for (int ch = 0; ch < 3; ch++)
                     img[4 * i + ch] = k == 0   ? u8(albedo[3 * i + ch])
                                       : k == 1 ? u8(normal[3 * i + ch] * 0.5f + 0.5f)
-                                               : u8(1.0f / (1.0f + depth[i]));
+                                      : k == 2 ? u8(1.0f / (1.0f + depth[i]))
+                                               : u8(se / (1.0f + se));
                 img[4 * i + 3] = 255;
             }
-            const std::string name = aov + (k == 0 ? "_albedo" : k == 1 ? "_normal" : "_depth") + (ppm ? ".ppm" : ".png");
+            const std::string name =
+                aov + (k == 0 ? "_albedo" : k == 1 ? "_normal" : k == 2 ? "_depth" : "_var") + (ppm ? ".ppm" : ".png");
             if (!(ppm ? bwrt::write_ppm(name, width, height, img.data()) : bwrt::write_png(name, width, height, img.data()))) {
                 std::fprintf(stderr, "cannot write %s\n", name.c_str());
                 return 1;

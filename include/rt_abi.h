@@ -24,8 +24,8 @@
  *    cross the ABI.  rt_last_error() gives a human-readable message.
  *  - One context = one GPU (HIP device) and one pixel-row shard.  A context
  *    must be used by one host thread at a time.  All calls except
- *    rt_render_device()/rt_denoise_device()/rt_temporal_device()/
- *    rt_deinterleave_rows_device() are synchronous.
+ *    rt_render_device()/rt_denoise_device()/rt_denoise_var_device()/
+ *    rt_temporal_device()/rt_deinterleave_rows_device() are synchronous.
  *  - Output RGBA8 buffers are row-major, row 0 = BOTTOM of the screen
  *    (the reference draws texcoord (0,0) at the bottom-left, Main.cu:358).
  *  - Semantics of one "sample" (progressive frame) follow the reference
@@ -45,7 +45,8 @@
  *                       BWRT_STREAM_PRIO=0 (the context's stream at normal
  *                       instead of the highest priority), BWRT_DEINT_BLOCKS,
  *                       BWRT_PRECISION=fast|exact,
- *                       BWRT_DENOISE_KERNEL=direct|tiled (filter kernel variant)
+ *                       BWRT_DENOISE_KERNEL=direct|tiled (filter kernel variant,
+ *                       rt_denoise and rt_denoise_var)
  *      at rt_set_scene: BWRT_BVH_MIN, BWRT_BVH_LEAF, BWRT_BVH_CT, BWRT_BVH_SBVH,
  *                       BWRT_BVH_REFS, BWRT_BVH_ALPHA, BWRT_BVH_ORDER_MASK,
  *                       BWRT_BVH_N16, BWRT_NO_CULL, BWRT_BVH_STATS (report)
@@ -190,8 +191,8 @@ RT_API void rt_destroy(rt_context* ctx);
  * renders on the CPU, and every entry point behaves on it as on a GPU
  * context (rt_set_scene, rt_init_rand, rt_render, rt_render_ex, rt_controls,
  * rt_get_state / rt_set_state, ...; rt_last_kernel_ms gives the last render's
- * wall time) except rt_render_device, rt_denoise_device, rt_temporal_device,
- * rt_render_multi and rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no
+ * wall time) except rt_render_device, rt_denoise_device, rt_denoise_var_device,
+ * rt_temporal_device, rt_render_multi and rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no
  * device memory).
  * Replaces the reference's config-1 CPU path and is the CPU baseline of
  * bench.py (SURVEY §8(b) rt_render_cpu, §8(d)). */
@@ -504,6 +505,78 @@ RT_API int rt_temporal_reset(rt_context* ctx);
 /* Duration (ms) of the reprojection pass alone of the last temporal call (HIP
  * events on its stream; wall time on a CPU context); -1 when unavailable. */
 RT_API float rt_last_temporal_ms(rt_context* ctx);
+
+/* ---- luminance moment tracking (per-pixel noise estimate) -----------------------
+ * Opt-in, off by default.  While on, every render entry point (rt_render,
+ * rt_render_ex, rt_render_device, rt_render_cpu, rt_render_multi per context)
+ * runs one small extra pass over the context's shard behind the render (on a
+ * GPU context on the same stream, before the launch's end event, so
+ * rt_last_kernel_ms includes it and every call ordered after the render is
+ * ordered after it).  It treats the k frames of the call as one *batch*: from
+ * frameSum before and after the call it takes the batch's mean luminance l
+ * (Rec. 709 weights) and updates, per pixel, the weighted mean M of the batch
+ * luminances and M2 = sum_j k_j (l_j - M)^2 (weighted Welford; DESIGN.md
+ * section 11 and csrc/rt_moments.h have the exact arithmetic).  The pass reads
+ * frameSum and writes only its own buffers: RGBA, frameSum, RNG state and
+ * frame counter of any sequence of calls are bit-identical with tracking on
+ * and off, and GPU and CPU contexts compute the same moments bit for bit.
+ *
+ * Tracking goes *live* at a render whose first frame is 1 (the render that
+ * resets frameSum; so after rt_reset_accumulation, rt_set_camera, a moving
+ * rt_controls and rt_set_scene the next render restarts it) and stays live
+ * while each following render's first frame is the frame after the last
+ * tracked one.  It ends (no batches) at rt_set_state, rt_init_rand (also the
+ * implicit one of a shape change), a render whose first frame is neither 1 nor
+ * the expected next, rt_set_moments(ctx, 0), and when it is enabled in
+ * mid-accumulation.  A render while not live skips the pass.  Nothing is
+ * allocated before tracking is on and a render runs (20 bytes per pixel). */
+RT_API int rt_set_moments(rt_context* ctx, int enable);
+RT_API int rt_get_moments(const rt_context* ctx);
+/* Tracked batches J (render calls) of the current accumulation; 0 when not live. */
+RT_API int rt_moments_batches(const rt_context* ctx);
+/* The shard's rows * width estimates, rows as rt_render_ex; either pointer may
+ * be NULL.  var_out = M2 / ((J - 1) n): an unbiased estimate of the variance of
+ * the pixel's MEAN luminance after the n accumulated frames (its square root
+ * is the standard error of frameSum / n in luminance), whatever the batch
+ * sizes; lum_out = M, that mean luminance.  RT_ERR_INVALID_ARGUMENT when
+ * tracking is not live or J < 2 (one batch has no spread).  Synchronous. */
+RT_API int rt_get_variance(rt_context* ctx, float* var_out, float* lum_out);
+
+/* ---- variance-guided a-trous filter ------------------------------------------------
+ * rt_denoise with its colour term replaced by SVGF's (Schied et al. 2017): the
+ * luminance difference of a tap is measured in standard deviations of the
+ * pixel's own noise, so no colour sigma has to be chosen for a scene's
+ * brightness or a frame's sample count, and a per-pixel variance is filtered
+ * along with the colour (sum of w^2 v / (sum of w)^2).  The variance of the
+ * frame comes from the moment tracking when it is live with at least
+ * min_batches batches, else (also with tracking off) from a spatial estimate
+ * over the 7 x 7 neighbourhood; DESIGN.md section 11 and csrc/rt_denoise_var.h
+ * have the exact definition.  Errors, ordering and neutrality are rt_denoise's:
+ * full frames only, frame counter >= 2, exact arithmetic whatever
+ * rt_set_precision says, the same bits on GPU and CPU contexts, and neither the
+ * RNG state, frameSum, the frame counter nor the tracked moments are written. */
+typedef struct rt_denoise_var_params {
+    int iterations;      /* 0..RT_DENOISE_MAX_ITERATIONS; level i has tap step 1<<i */
+    float sigma_lum;     /* > 0: luminance sigma in standard deviations (SVGF: 4) */
+    float sigma_normal;  /* as rt_denoise_params */
+    float sigma_plane;   /* as rt_denoise_params */
+    int min_batches;     /* >= 2: below this many tracked batches, use the spatial estimate (SVGF: 4) */
+} rt_denoise_var_params;
+RT_API rt_denoise_var_params rt_denoise_var_params_default(void);
+/* rgba_out: w*h*4 bytes or NULL; color_out: w*h*3 linear floats or NULL;
+ * var_out: w*h filtered variances of the mean luminance or NULL.  With
+ * iterations == 0 the colour is frameSum / n, the variance the input estimate
+ * and the RGBA equals the last render's.  Errors as rt_denoise, and
+ * RT_ERR_INVALID_ARGUMENT for sigma_lum <= 0 or NaN and min_batches < 2. */
+RT_API int rt_denoise_var(rt_context* ctx, const rt_denoise_var_params* params, uint8_t* rgba_out,
+                          float* color_out, float* var_out);
+/* As above into DEVICE memory on HIP stream `stream`, with rt_denoise_device's
+ * ordering rules (after the context's last render, denoise, temporal and
+ * variance-guided call, before its next ones).  CPU context: RT_ERR_UNSUPPORTED. */
+RT_API int rt_denoise_var_device(rt_context* ctx, const rt_denoise_var_params* params, void* rgba_device,
+                                 void* stream);
+/* Duration (ms) of all passes of the last rt_denoise_var call; -1 when unavailable. */
+RT_API float rt_last_denoise_var_ms(rt_context* ctx);
 
 RT_API const char* rt_error_string(int status);
 RT_API const char* rt_last_error(const rt_context* ctx);
