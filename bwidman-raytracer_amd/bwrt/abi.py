@@ -145,6 +145,8 @@ def _proto(lib):
         "rt_last_kernel_ms": (C.c_float, [vp]),
         "rt_set_kernel_timing": (C.c_int, [vp, C.c_int]),
         "rt_shard_rows": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+        "rt_sky_table": (C.c_int, [vp, P(RenderParams), C.c_int, C.c_int, vp, C.c_size_t, P(C.c_longlong),
+                                   P(C.c_ulonglong)]),
         "rt_deinterleave_rows_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int,
                                                   C.c_int, vp]),
         "rt_get_state": (C.c_int, [vp, vp, vp]),

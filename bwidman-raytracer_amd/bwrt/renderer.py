@@ -172,6 +172,21 @@ class Renderer:
         their end event (no marker packet between back-to-back renders)."""
         return self.lib.rt_get_stream(self.ctx) or 0
 
+    def sky_table(self, width, height, row_offset=0, row_stride=1, tile_w=-1, tile_sq=False):
+        """rt_sky_table: (bits, builds) for a view.  bits: one bool per wave
+        tile of the launch order (tile_w x 64 / tile_w pixels; tile_w -1 = the
+        launch policy's), True where every camera ray provably misses; builds:
+        the tables this context has built so far (a cache-key diagnostic)."""
+        p = self.params(width, height, 1, 0, 0, row_offset, row_stride)
+        tiles, builds = C.c_longlong(), C.c_ulonglong()
+        self._check(self.lib.rt_sky_table(self.ctx, C.byref(p), tile_w, int(bool(tile_sq)), None, 0,
+                                          C.byref(tiles), C.byref(builds)))
+        words = np.zeros(tiles.value // 32 + 1, np.uint32)
+        self._check(self.lib.rt_sky_table(self.ctx, C.byref(p), tile_w, int(bool(tile_sq)), words.ctypes.data,
+                                          words.size, C.byref(tiles), C.byref(builds)))
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:tiles.value].astype(bool)
+        return bits, builds.value
+
     def last_kernel_ms(self) -> float:
         return self.lib.rt_last_kernel_ms(self.ctx)
 

@@ -174,6 +174,10 @@ int rt_create(int device, rt_context** out) {
     if (const char* g = tuning_env("BWRT_REFILL")) c->refill = std::min(std::max(std::atoi(g), 1), 64);
     if (const char* g = tuning_env("BWRT_SPREAD")) c->spread = std::atoi(g) ? 1 : 0;
     if (const char* g = tuning_env("BWRT_ORDER")) c->order_feedback = std::atoi(g) != 0;
+    if (const char* g = tuning_env("BWRT_SKY")) {
+        c->sky_on = std::atoi(g) != 0;
+        c->sky_eager = std::atoi(g) == 2;
+    }
     if (const char* g = tuning_env("BWRT_ORDER_PERIOD")) c->order_period = std::max(std::atoi(g), 1);
     if (const char* g = tuning_env("BWRT_DENOISE_KERNEL"))
         c->dn_kernel = std::strcmp(g, "tiled") == 0 ? 1 : std::strcmp(g, "direct") == 0 ? 0 : -1;
@@ -232,6 +236,10 @@ void rt_destroy(rt_context* c) {
             p->destroy();
         }
         if (c->host_rgba) (void)hipHostFree(c->host_rgba);
+        if (c->sky_ev) {
+            (void)hipEventSynchronize(c->sky_ev);
+            (void)hipEventDestroy(c->sky_ev);
+        }
         if (c->stream) (void)hipStreamDestroy(c->stream);
     }
     delete c;  // every Buf frees itself
@@ -267,12 +275,14 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
         HIP_TRY(c, hipMemcpyAsync(c->scene_buf.p, cs.data.data(), bytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
+    rt_sky_collect(*s, cs, c->sky_prims);
     std::vector<float>().swap(cs.data);
     c->scene = std::move(cs);
     c->camera = s->camera;
     c->has_scene = true;
     c->frame = 1;
     c->order_stale = true;
+    c->sky_gen++;
     c->new_view();
     c->tp_has_hist = c->tp_has_pending = false;  // primitive ids change meaning
     return RT_OK;
@@ -283,6 +293,7 @@ int rt_set_camera(rt_context* c, const rt_camera* cam) {
     c->camera = *cam;
     c->frame = 1;  // Controls.cuh: any movement sets accumulatedFrames = 1
     c->order_stale = true;
+    c->sky_gen++;
     c->new_view();
     return RT_OK;
 }
@@ -393,6 +404,7 @@ int rt_controls(rt_context* c, unsigned keys, float dt) {
     if (flags > 0 && (flags & RT_CONTROLS_MOVED)) {
         c->frame = 1;  // accumulatedFrames = 1
         c->order_stale = true;
+        c->sky_gen++;
         c->new_view();
     }
     return flags;

@@ -22,12 +22,14 @@
 #include "../../include/rt_abi.h"
 #include "rt_layout.h"
 #include "rt_scene.h"
+#include "rt_sky.h"
 
 // ---- kernel launchers ---------------------------------------------------------
 size_t rt_render_rec_floats(const rt_kparams& K);
 bool rt_render_wants_global_records(const rt_kparams& K, int num_cus);
 hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, bool simple, int block_req,
                             hipStream_t stream, int pair_req);
+bool rt_render_takes_sorted(const rt_kparams& K, int num_cus, bool simple, int block_req, int pair_req);
 hipError_t rt_launch_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride,
                                hipStream_t stream);
 // the reference-fast instantiations (rt_kernels_fast.hip, rt_kernels_bvh_fast.hip)
@@ -35,6 +37,7 @@ namespace rt_fast {
 bool rt_render_wants_global_records(const rt_kparams& K, int num_cus);
 hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, bool simple, int block_req,
                             hipStream_t stream, int pair_req);
+bool rt_render_takes_sorted(const rt_kparams& K, int num_cus, bool simple, int block_req, int pair_req);
 }  // namespace rt_fast
 extern thread_local long rt_order_groups_last;
 extern thread_local char rt_launched_kernel[96];
@@ -273,6 +276,36 @@ struct rt_context {
         mom_batches = 0;
     }
 
+    // sky table (rt_sky.h): the table of the view `sky_key`, on the host and
+    // (GPU contexts) in sky_buf; rebuilt and uploaded only when the key
+    // changes.  sky_gen counts scene and camera changes (rt_set_scene,
+    // rt_set_camera, rt_controls); sky_builds counts the tables built.
+    struct SkyKey {
+        unsigned long long gen = 0;
+        int width = 0, height = 0, rows = 0, row_offset = 0, row_stride = 0, tile_w = 0, tile_sq = 0, spp_inner = 0;
+        float jitter = 0.0f;
+        bool operator==(const SkyKey& o) const {
+            return gen == o.gen && width == o.width && height == o.height && rows == o.rows &&
+                   row_offset == o.row_offset && row_stride == o.row_stride && tile_w == o.tile_w &&
+                   tile_sq == o.tile_sq && spp_inner == o.spp_inner && jitter == o.jitter;
+        }
+    };
+    // A render builds the table of a view at the view's SECOND launch: a
+    // build costs about as much host time as the sky path saves in fifty
+    // config-3 launches (DESIGN.md "sky groups"), so a moving camera, whose
+    // views are launched once, never pays for one; an accumulating view pays
+    // once.  BWRT_SKY=0: no sky path; 2: build at the first launch (tests, A/B)
+    bool sky_on = true, sky_eager = false;
+    unsigned long long sky_gen = 1, sky_builds = 0;
+    SkyKey sky_key;   // gen 0: no table yet
+    SkyKey sky_seen;  // the view of the last launch that went without a table
+    bool sky_any = false;  // the table has a set bit
+    bool sky_uploaded = false;  // sky_buf holds sky_bits
+    rt_sky_prims sky_prims;  // of the context's scene (rt_set_scene)
+    std::vector<uint32_t> sky_bits;
+    Buf sky_buf;
+    hipEvent_t sky_ev = nullptr;  // behind the last upload (created by the first one)
+
     // a new view (scene, camera, frame shape): the guides are stale
     void new_view() {
         guides_valid = false;
@@ -324,6 +357,11 @@ int shard_check(rt_context* c, int width, int height, int row_offset, int row_st
 // Camera prelude and compiled scene of a width x height view (shard
 // row_offset, stride, rows) into K; every other field 0 (rt_render.cpp)
 void fill_view(rt_context* c, int width, int height, int row_offset, int stride, int rows, rt_kparams& K);
+// The launch policy's wave tiles of a brute-force view (K.rows, K.width set)
+void policy_tiles(const rt_context* c, rt_kparams& K);
+// The sky table of view K (tile shape set) in c->sky_bits, rebuilt only when
+// its key changed (rt_render.cpp)
+void sky_table(rt_context* c, const rt_kparams& K);
 
 // ---- layouts of the ABI's host arrays -----------------------------------------
 // frameSum: 3 planes of npix on the device, interleaved RGB at the ABI

@@ -560,6 +560,68 @@ enum { T_NONE = 0, T_REGEN = 1, T_DIFF = 2, T_SPEC = 3 };  // a lane's next task
 //      [task slots 13 x BLOCK, field-major][2 x 2 queue counters]
 // GREC: the record levels >= RT_GREC_LDS_LEVELS in global memory (deep paths
 // and full frames, launch policy).  BVH scenes take the ray-refill kernel.
+namespace {
+// A group whose wave tiles are all sky (rt_sky.h): every camera ray of its
+// pixels misses, so a frame is the jitter's rejection loop (ball_try: the
+// draws of genRandomDirection, Main.cu:193-197; its normalisation, the
+// hemisphere flip and the camera ray draw nothing, and the miss discards
+// them) and frameSum += backgroundColor with finish_path's operations.  No
+// barrier, no LDS; the whole group takes it, so no wave is left at a barrier.
+template <int BLOCK, bool ORDER>
+__device__ __forceinline__ void render_sky_group(const rt_kparams& K, long group) {
+    const int tid = threadIdx.x;
+    unsigned t0 = 0u;
+    if (ORDER) t0 = (unsigned)__builtin_amdgcn_s_memrealtime();
+    const long npix = (long)K.rows * K.width;
+    const long nitems = items_of(K, npix);
+    PixelState px;
+    load_item(K, npix, nitems, group * BLOCK + tid, px);  // (d0 is unused here: the compiler drops primary_dir)
+    const float lx = K.bg[0], ly = K.bg[1], lz = K.bg[2];  // backgroundColor (Main.cu:209-211)
+    // One loop over the draws, not one per frame: a lane whose point is
+    // accepted starts its next frame's draws in the next trip instead of
+    // waiting for the wave's slowest rejection loop (a wave then runs the
+    // largest per-lane SUM of trips, about half the sum of per-frame maxima;
+    // each lane's draws, tests and adds are the same sequence either way)
+    while (px.passes_left > 0) {
+        if (!ball_try(px.rs)) continue;
+        if (px.frame == 1u) {
+            px.ax = 0.0f;
+            px.ay = 0.0f;
+            px.az = 0.0f;
+        }
+        px.ax = px.ax + lx;
+        px.ay = px.ay + ly;
+        px.az = px.az + lz;
+        px.frame++;
+        px.passes_left--;
+    }
+    if (px.valid && px.frame != K.first_frame) store_pixel(K, npix, px);
+    // launch-order feedback: the group's span, as the round loop records it
+    // (every wave of a sky group does the same work: wave 0's span stands for all)
+    if (ORDER && tid == 0) K.group_cost[group] = (unsigned)__builtin_amdgcn_s_memrealtime() - t0;
+}
+
+// The call the kernel makes.  Not inlined: inlined, the sky path's address
+// arithmetic shares and re-allocates the round loop's scalar registers (the
+// product kernel went from 68 VGPRs and no spilled SGPR to 69 and 2, with 313
+// changed stretches of its instruction stream, `make asm`).  A callee gets
+// its arguments in vector registers and no kernel-argument base of its own,
+// so the kernel passes the argument segment's address and the callee makes it
+// scalar again (readfirstlane): the parameters then come through scalar loads.
+typedef const __attribute__((address_space(4))) rt_kparams* kparams_ptr;
+template <int BLOCK, bool ORDER>
+__device__ __attribute__((noinline)) void render_sky_group_call(kparams_ptr kp_v, int group_v) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (the host pass has no address-space-4 copy)
+    const unsigned long long a = (unsigned long long)kp_v;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    const kparams_ptr kp = (kparams_ptr)(((unsigned long long)hi << 32) | lo);
+    const rt_kparams K = *kp;
+    render_sky_group<BLOCK, ORDER>(K, (long)__builtin_amdgcn_readfirstlane(group_v));
+#endif
+}
+}  // namespace
+
 RT_MODE_BEGIN
 template <int BLOCK, bool HIT_LDS, bool GREC, bool ORDER = false, bool QUADS = true>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(GREC ? RT_GREC_WAVES : RT_WAVES_PER_EU)))
@@ -567,6 +629,17 @@ rt_render_sorted_kernel(rt_kparams K) {
     extern __shared__ float smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
+    // sky groups (rt_sky.h): every tile of the group proven sky on the host.
+    // Group-uniform (two scalar loads), decided before the first barrier
+    if (K.sky) {
+        constexpr unsigned WPB = BLOCK / 64, ALL = (1u << WPB) - 1u;
+        const long sgroup = ORDER && K.group_order ? (long)K.group_order[blockIdx.x] : (long)blockIdx.x;
+        const unsigned first = (unsigned)sgroup * WPB;  // WPB divides 32: the bits lie in one word
+        if (((K.sky[first >> 5] >> (first & 31)) & ALL) == ALL) {
+            render_sky_group_call<BLOCK, ORDER>((kparams_ptr)__builtin_amdgcn_kernarg_segment_ptr(), (int)sgroup);
+            return;
+        }
+    }
     const int n_prim = K.n_sph + K.n_pln + K.n_tri + K.n_quad;
     const float* hit_tab = K.hit;
     float* rec_base = smem;
@@ -1566,10 +1639,10 @@ hipError_t launch_render(const rt_kparams& K0, size_t lds, int grid_mult, int nu
         else
             launch_kind<KIND, BLOCK, HIT_LDS, GREC, false, false>(K, grid, lds, stream);
     }
-    std::snprintf(rt_launched_kernel, sizeof rt_launched_kernel, "%s<%d%s%s%s%s>%s",
+    std::snprintf(rt_launched_kernel, sizeof rt_launched_kernel, "%s<%d%s%s%s%s>%s%s",
                   KIND == K_PAIR ? "rt_render_pair_kernel" : KIND == K_SORTED ? "rt_render_sorted_kernel" : "rt_render_kernel",
                   KIND == K_PAIR ? 128 : BLOCK, HIT_LDS ? "" : ",hit_global", GREC ? ",grec" : "", BVH ? ",bvh" : "",
-                  RT_MODE_TAG, feedback ? "+order" : "");
+                  RT_MODE_TAG, feedback ? "+order" : "", KIND == K_SORTED && K.sky ? "+sky" : "");
     hipError_t e = hipGetLastError();
     // the sort runs when asked, and always for a grid without an order yet
     if (e == hipSuccess && feedback && (K0.order_sort || K0.order_n != grid)) {
@@ -1750,6 +1823,32 @@ size_t rt_render_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool so
 #define RT_PAIR_MIN_CHAIN 8
 #endif
 RT_MODE_BEGIN
+namespace {
+// (the pair kernel shortens long per-pixel chains: frames of at most
+// RT_PAIR_MIN_CHAIN queries per pixel keep the sorted kernel — config 1,
+// 1 frame x 2 queries: 10.3 vs 10.9 us, profiles/r05c/session.txt)
+bool takes_pair(const rt_kparams& K, bool hit_lds, int num_cus, int block_req, int pair_req) {
+    const long items = (long)K.rows * K.width;
+    return hit_lds && !K.rec && (block_req == 0 || block_req == 128) &&
+           (pair_req > 0 || (pair_req < 0 && block_req == 0 && items <= (long)num_cus * RT_SPREAD_PIX &&
+                             (long)K.samples * (K.max_bounces + 1) >= RT_PAIR_MIN_CHAIN));
+}
+}  // namespace
+
+// Whether rt_launch_render (below) takes the sorted brute-force kernel for K
+// (K.rec as the launch will have it): the only kernel that reads K.sky
+bool rt_render_takes_sorted(const rt_kparams& K, int num_cus, bool simple, int block_req, int pair_req) {
+    if (simple || K.spp_inner > 1 || K.bvh_nodes) return false;
+#ifdef RT_NO_HIT_LDS
+    const bool hit_lds = false;
+#else
+    const int n_prim = K.n_sph + K.n_pln + K.n_tri + K.n_quad;
+    const bool hit_lds = (size_t)n_prim * RT_HIT_FLOATS * sizeof(float) <= 16384;
+#endif
+    const bool small_block = (size_t)3 * (K.max_bounces + 1) * 256 * sizeof(float) > 49152;
+    return small_block || !takes_pair(K, hit_lds, num_cus, block_req, pair_req);
+}
+
 hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, bool simple, int block_req,
                             hipStream_t stream, int pair_req) {
     // samplesPerPixel > 1 (the reference's in-frame loop, off by default):
@@ -1773,12 +1872,7 @@ hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, boo
 #endif
     if (small_block) return launch_block<64, K_SORTED>(K, hit_lds, lds, grid_mult, num_cus, stream);
     const long items = (long)K.rows * K.width;
-    // (the pair kernel shortens long per-pixel chains: frames of at most
-    // RT_PAIR_MIN_CHAIN queries per pixel keep the sorted kernel — config 1,
-    // 1 frame x 2 queries: 10.3 vs 10.9 us, profiles/r05c/session.txt)
-    const bool pair = hit_lds && !K.rec && (block_req == 0 || block_req == 128) &&
-                      (pair_req > 0 || (pair_req < 0 && block_req == 0 && items <= (long)num_cus * RT_SPREAD_PIX &&
-                                        (long)K.samples * (K.max_bounces + 1) >= RT_PAIR_MIN_CHAIN));
+    const bool pair = takes_pair(K, hit_lds, num_cus, block_req, pair_req);
     if (pair)
         return launch_render<K_PAIR, 128, true>(K, rt_pair_lds_bytes(K), grid_mult, num_cus, stream);
     if (block_req == 64 || block_req == 128 || block_req == 256) {  // explicit (BWRT_BLOCK)

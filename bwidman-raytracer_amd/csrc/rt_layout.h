@@ -137,6 +137,10 @@ struct rt_kparams {
     // frame's sample.  1 (the reference build) everywhere but the simple
     // kernel and the CPU fallback, which the launch policy picks for n > 1
     int spp_inner;
+    // sky table (rt_sky.h; sorted kernel): bit t of word t / 32 set when every
+    // camera ray of wave tile t of the launch order provably misses; a group
+    // whose tiles are all sky skips the round loop.  Null = feature off.
+    const unsigned* sky;
 };
 
 // leaf-batch thresholds of the launch policy (full frames / small shards)

@@ -406,6 +406,16 @@ RT_HD f3 random_direction(Xorwow& s, f3 normal, int* iters = nullptr) {
     return r;
 }
 
+// One trip of that rejection loop (Main.cu:194-197): the three draws and the
+// acceptance test, the same float operations as random_direction's
+// condition.  The sorted kernel's sky groups run only these.
+RT_HD bool ball_try(Xorwow& s) {
+    const float x = rand_pm1(s);
+    const float y = rand_pm1(s);
+    const float z = rand_pm1(s);
+    return !(x * x + y * y + z * z > 1.00000012f);
+}
+
 // Specular branch of tracePath after the brdfChoice draw (Main.cu:245-255):
 // microfacet normal (genMicrofacetNormal :170-185) in the tangent frame
 // (baseAroundNormalToRegular :149-168), mirror reflection (:187-191),

@@ -158,7 +158,35 @@ static int cpu_render(rt_context* c, const rt_render_params* p, int threads, uin
     return RT_OK;
 }
 
-static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, int samples) {
+static rt_context::SkyKey sky_key_of(const rt_context* c, const rt_kparams& K) {
+    rt_context::SkyKey k;
+    k.gen = c->sky_gen;
+    k.width = K.width;
+    k.height = K.height;
+    k.rows = K.rows;
+    k.row_offset = K.row_offset;
+    k.row_stride = K.row_stride;
+    k.tile_w = K.tile_w;
+    k.tile_sq = K.tile_sq;
+    k.spp_inner = K.spp_inner;
+    k.jitter = K.jitter;
+    return k;
+}
+
+void sky_table(rt_context* c, const rt_kparams& K) {
+    const rt_context::SkyKey k = sky_key_of(c, K);
+    if (k == c->sky_key) return;
+    // the last upload read sky_bits (it precedes that launch's kernel on its stream)
+    if (c->sky_uploaded && c->sky_ev) (void)hipEventSynchronize(c->sky_ev);
+    rt_sky_build(K, c->sky_prims, c->sky_bits);
+    c->sky_key = k;
+    c->sky_builds++;
+    c->sky_uploaded = false;
+    c->sky_any = false;
+    for (const uint32_t w : c->sky_bits) c->sky_any = c->sky_any || w != 0u;
+}
+
+void policy_tiles(const rt_context* c, rt_kparams& K) {
     // wave tiles: 8 x 8 pixels; on small shards (one rank of a multi-GPU
     // frame, below 1024 pixels per CU) 32 x 2 (config 3 at 1/8: 0.249 ->
     // 0.244 ms); BVH scenes 4 x 16 on small shards: squarer tiles keep a
@@ -171,6 +199,11 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     const bool small = (long)K.rows * K.width <= (long)c->num_cus * 1024;
     K.tile_w = c->tile_w >= 0 ? c->tile_w : K.bvh_nodes ? (small ? 4 : 8) : (small ? 32 : 8);
     K.tile_sq = c->tile_sq;
+}
+
+static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, int samples) {
+    policy_tiles(c, K);
+    const bool small = (long)K.rows * K.width <= (long)c->num_cus * 1024;
     // BVH refill kernel: test the parked leaves once this many of a wave's 64
     // lanes are ready; small shards (every wave resident at once, the frame
     // ends with the slowest waves) batch later
@@ -226,6 +259,31 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     // after the last render, denoise and reprojection pass on another stream
     int orc = order_after_all(c, s);
     if (orc) return orc;
+    // sky table (rt_sky.h), for launches of the sorted brute-force kernel: an
+    // unchanged view costs the key compare; a view's first launch goes without
+    // a table (rt_context.h sky_eager), its second builds and uploads one
+    // ahead of the kernel on its stream
+    bool sky = c->sky_on && (fast ? rt_fast::rt_render_takes_sorted(K, c->num_cus, c->simple, c->block, c->spread)
+                                  : rt_render_takes_sorted(K, c->num_cus, c->simple, c->block, c->spread));
+    if (sky && !c->sky_eager) {
+        const rt_context::SkyKey k = sky_key_of(c, K);
+        if (!(k == c->sky_key) && !(k == c->sky_seen)) {
+            c->sky_seen = k;
+            sky = false;
+        }
+    }
+    if (sky) {
+        sky_table(c, K);
+        if (c->sky_any && !c->sky_uploaded) {
+            const size_t bytes = c->sky_bits.size() * sizeof(uint32_t);
+            if (const int rc = ensure_buf(c, c->sky_buf, bytes)) return rc;
+            if (!c->sky_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->sky_ev, hipEventDisableTiming));
+            HIP_TRY(c, hipMemcpyAsync(c->sky_buf.p, c->sky_bits.data(), bytes, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipEventRecord(c->sky_ev, s));
+            c->sky_uploaded = true;
+        }
+        if (c->sky_any) K.sky = c->sky_buf.as<unsigned>();
+    }
     rt_order_groups_last = 0;
     rt_launched_kernel[0] = 0;
     // the start marker only with kernel timing on; the one end event serves
@@ -409,6 +467,31 @@ int rt_deinterleave_rows_device(rt_context* c, const void* gathered, void* image
     HIP_TRY(c, rt_launch_deinterleave((const unsigned*)gathered, (unsigned*)image, width, height, shards,
                                       rows_per_shard, c->deint_blocks, s));
     HIP_TRY(c, c->aux.end(s));
+    return RT_OK;
+}
+
+int rt_sky_table(rt_context* c, const rt_render_params* p, int tile_w, int tile_sq, uint32_t* bits, size_t words,
+                 long long* tiles_out, unsigned long long* builds_out) {
+    const HostFpEnv fp;
+    if (!c || !p) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    const int stride = p->row_stride == 0 ? 1 : p->row_stride;
+    if (const int rc = shard_check(c, p->width, p->height, p->row_offset, stride)) return rc;
+    if (tile_w > 64 || (tile_w > 0 && (tile_w & (tile_w - 1))))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_sky_table: tile_w %d is not a power of two up to 64", tile_w);
+    if (words && !bits) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_sky_table: null bits");
+    rt_kparams K;
+    fill_view(c, p->width, p->height, p->row_offset, stride, shard_rows(p->height, p->row_offset, stride), K);
+    if (tile_w < 0) {
+        policy_tiles(c, K);
+    } else {
+        K.tile_w = tile_w;
+        K.tile_sq = tile_sq != 0;
+    }
+    sky_table(c, K);
+    for (size_t i = 0; i < words; i++) bits[i] = i < c->sky_bits.size() ? c->sky_bits[i] : 0u;
+    if (tiles_out) *tiles_out = rt_sky_tiles(K);
+    if (builds_out) *builds_out = c->sky_builds;
     return RT_OK;
 }
 

@@ -42,6 +42,8 @@
  *      at rt_create:    BWRT_KERNEL=simple, BWRT_BLOCK, BWRT_TILE, BWRT_TILE_SQ,
  *                       BWRT_GREC, BWRT_GRID_MULT, BWRT_LEAF_BATCH, BWRT_REFILL,
  *                       BWRT_SPREAD, BWRT_ORDER, BWRT_ORDER_PERIOD,
+ *                       BWRT_SKY=0 (no sky table: every tile group runs the
+ *                       round loop, see rt_sky_table),
  *                       BWRT_STREAM_PRIO=0 (the context's stream at normal
  *                       instead of the highest priority), BWRT_DEINT_BLOCKS,
  *                       BWRT_PRECISION=fast|exact,
@@ -372,7 +374,8 @@ RT_API float rt_last_kernel_ms(rt_context* ctx);
  * (full frames), "rt_render_pair_kernel<128>+order" (small frames and
  * shards), "rt_render_bvh_refill_kernel<64,n16>" (BVH scenes); a
  * RT_PRECISION_REFERENCE_FAST launch carries ",fast" inside the angle
- * brackets, e.g. "rt_render_pair_kernel<128,fast>+order"; "" before
+ * brackets, e.g. "rt_render_pair_kernel<128,fast>+order"; a sorted-kernel
+ * launch that was given a sky table (rt_sky_table) ends in "+sky"; "" before
  * the first render and on a CPU context.  A diagnostic of the launch
  * policy (tests assert which kernel a workload runs); valid until the next
  * render on the context.  The reference launches one kernel, Main.cu:342. */
@@ -387,6 +390,27 @@ RT_API const char* rt_last_kernel_name(const rt_context* ctx);
  * reference times nothing on the device (it prints host-side FPS,
  * Main.cu:486-495). */
 RT_API int rt_set_kernel_timing(rt_context* ctx, int enable);
+
+/* The sky table of the view (p: width, height, row_offset, row_stride; the
+ * context's scene and camera): one bit per 64-pixel wave tile of the launch
+ * order (tile t: bit t % 32 of word t / 32), set when every camera ray of
+ * the tile, under any jitter, provably misses every primitive.  A full frame's
+ * sorted brute-force launch renders tile groups whose bits are all set
+ * without the path machinery (per frame: the jitter's rejection loop and
+ * frameSum += background; bit-identical results).  tile_w: the tile's width in
+ * pixels (a power of two up to 64; 64 / tile_w rows), -1 = the launch policy's
+ * for this view; tile_sq: every 4 consecutive tiles as a 2 x 2 block.  Writes
+ * the first `words` words of the table (zero past its end), the number of
+ * tiles and the number of tables the context has built so far (it keeps the
+ * last one and rebuilds only when the scene, the camera or the view changes).
+ * No bit is set when nothing can be proven: scenes scaled beyond 1e9,
+ * non-finite values, the camera inside a bounding sphere, skinny triangles,
+ * non-convex or non-planar quads, BVH scenes, samplesPerPixel > 1, tile_w 0.
+ * Host arithmetic only: works on CPU contexts too.  No counterpart in the
+ * reference. */
+RT_API int rt_sky_table(rt_context* ctx, const rt_render_params* p, int tile_w, int tile_sq,
+                        uint32_t* bits, size_t words, long long* tiles_out,
+                        unsigned long long* builds_out);
 
 /* Number of pixel rows in the shard (row_offset, row_stride) of `height`. */
 RT_API int rt_shard_rows(int height, int row_offset, int row_stride);
