@@ -6,6 +6,10 @@
 //   rt_render.cpp   prepare, fill_view, launch, rt_render*, multi-GPU, de-interleave
 //   rt_post.cpp     first-hit features, denoiser, temporal reprojection, moment readout
 //   rt_scene.cpp    the scene compiler (rt_scene.h; no HIP, no context)
+// The post-render passes' kernels and arithmetic: rt_atrous.h (what the filters
+// and the reprojection share, host and device), rt_atrous_tile.h (the pixel and
+// the LDS-tiled kernel with their launchers, device only), then one header and
+// one unit each: rt_denoise, rt_denoise_var, rt_temporal, rt_moments.
 #pragma once
 
 #include <hip/hip_runtime.h>

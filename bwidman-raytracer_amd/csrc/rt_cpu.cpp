@@ -266,14 +266,22 @@ void parallel_items(long n, int threads, const Fn& fn) {
     for (std::thread& t : pool) t.join();
 }
 
+// fn(x, y, p) for every pixel p = y * width + x of a width x height image, as
+// parallel_items
+template <class Fn>
+void parallel_pixels(int width, int height, int threads, const Fn& fn) {
+    parallel_items((long)width * height, threads, [&](long p) {
+        const int y = (int)(p / width);
+        fn((int)(p - (long)y * width), y, p);
+    });
+}
+
 }  // namespace
 
 // The feature buffers of the shard in K (rt_kernels.hip rt_aov_kernel): ga, gb
 // and alb as the kernel packs them (alb may be null)
 void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb) {
-    parallel_items((long)K.rows * K.width, threads, [&](long p) {
-        const int j = (int)(p / K.width);
-        const int x = (int)(p - (long)j * K.width);
+    parallel_pixels(K.width, K.rows, threads, [&](int x, int j, long p) {
         const int y = K.row_offset + j * K.row_stride;
         const f3 o = mk(K.cam_pos[0], K.cam_pos[1], K.cam_pos[2]);
         const f3 d = primary_dir(K, x, y);
@@ -290,32 +298,21 @@ void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4
     });
 }
 
-// One filter level (L.step >= 1) or, with L.step == 0, the conversion pass
+// One filter level (L.f.step >= 1) or, with L.f.step == 0, the conversion pass
 void rt_cpu_denoise_level(const rt_dn_level& L, int threads) {
-    const long npix = (long)L.width * L.height;
-    if (L.step == 0) {
-        parallel_items(npix, threads, [&](long p) { dn_store(L, p, dn_color<true>(L, p)); });
-        return;
-    }
-    parallel_items(npix, threads, [&](long p) {
-        const int y = (int)(p / L.width);
-        const int x = (int)(p - (long)y * L.width);
-        if (L.first) {
-            const DnGlobalFetch<true> fetch{L};
-            dn_store(L, p, dn_pixel(L, x, y, fetch));
-        } else {
-            const DnGlobalFetch<false> fetch{L};
-            dn_store(L, p, dn_pixel(L, x, y, fetch));
-        }
+    parallel_pixels(L.f.width, L.f.height, threads, [&](int x, int y, long p) {
+        if (L.f.step == 0)
+            at_store(L.f, p, DnFilter<true>::texel(L, p));
+        else if (L.first)
+            at_run_direct<DnFilter<true>>(L, x, y);
+        else
+            at_run_direct<DnFilter<false>>(L, x, y);
     });
 }
 
 // The temporal reprojection pass (rt_temporal.h), on the same pool
 void rt_cpu_temporal(const rt_tp_args& T, int threads) {
-    parallel_items((long)T.width * T.height, threads, [&](long p) {
-        const int y = (int)(p / T.width);
-        tp_run_pixel(T, (int)(p - (long)y * T.width), y);
-    });
+    parallel_pixels(T.width, T.height, threads, [&](int x, int y, long) { tp_run_pixel(T, x, y); });
 }
 
 // The luminance moment update of one render call (rt_moments.h), on the same pool
@@ -326,16 +323,12 @@ void rt_cpu_moments(const rt_mom_args& A, int threads) {
 // One pass of the variance-guided filter (rt_denoise_var.h): stage 0 the input
 // stage, 1 a sigma pass, 2 a level
 void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads) {
-    parallel_items((long)A.width * A.height, threads, [&](long p) {
-        const int y = (int)(p / A.width);
-        const int x = (int)(p - (long)y * A.width);
-        if (stage == 0) {
-            dv_store(A, p, dv_input(A, x, y));
-        } else if (stage == 1) {
+    parallel_pixels(A.f.width, A.f.height, threads, [&](int x, int y, long p) {
+        if (stage == 0)
+            at_store(A.f, p, dv_input(A, x, y));
+        else if (stage == 1)
             A.rs[p] = dv_sigma(A, x, y);
-        } else {
-            const DvGlobalFetch fetch{A};
-            dv_store(A, p, dv_pixel(A, x, y, fetch));
-        }
+        else
+            at_run_direct<DvFilter>(A, x, y);
     });
 }

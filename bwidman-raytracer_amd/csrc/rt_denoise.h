@@ -19,95 +19,58 @@
 // Result sum_c / sum_w when sum_w > 0, else c_p (a non-finite centre passes
 // through unchanged).
 #pragma once
-#include "rt_path.h"
+#include "rt_atrous.h"
 
 namespace {
 
-template <bool FIRST>
-RT_HD f3 dn_color(const rt_dn_level& L, long q) {
-    if (FIRST) {
-        const long npix = (long)L.width * L.height;
-        return mk(L.inv * L.accum[q], L.inv * L.accum[npix + q], L.inv * L.accum[2 * npix + q]);
-    }
-    const float4 c = L.src[q];
-    return mk(c.x, c.y, c.z);
-}
-
-struct DnSums {
+// the centre and the sums of one pixel; operator() is steps 4-10 of one tap
+struct DnTap {
+    const rt_dn_level& L;
+    f3 cp, np, Pp;
     float w;
     f3 c;
+    RT_HD void operator()(float h, float4 cq, f3 nq, f3 Pq) {
+        const f3 dc = sub(mk(cq.x, cq.y, cq.z), cp);
+        const float ec = dot(dc, dc) * L.ic;
+        float en, ex;
+        at_geom(L.f, np, Pp, nq, Pq, en, ex);
+        const float e = (ec + en) + ex;
+        if (!(e >= 0.0f)) return;
+        const float wt = h * exp_nn(-e);
+        if (!(wt > 0.0f)) return;
+        w = w + wt;
+        c.x = c.x + wt * cq.x;
+        c.y = c.y + wt * cq.y;
+        c.z = c.z + wt * cq.z;
+    }
 };
 
-// steps 4-10 of one tap
-RT_HD void dn_tap(const rt_dn_level& L, float h, f3 cp, f3 np, f3 Pp, f3 cq, f3 nq, f3 Pq, DnSums& s) {
-    const f3 dc = sub(cq, cp);
-    const float ec = dot(dc, dc) * L.ic;
-    const f3 dn = sub(nq, np);
-    const float en = dot(dn, dn) * L.in;
-    const float pd = dot(np, sub(Pq, Pp));
-    const float ex = (pd * pd) * L.ip;
-    const float e = (ec + en) + ex;
-    if (!(e >= 0.0f)) return;
-    const float w = h * exp_nn(-e);
-    if (!(w > 0.0f)) return;
-    s.w = s.w + w;
-    s.c.x = s.c.x + w * cq.x;
-    s.c.y = s.c.y + w * cq.y;
-    s.c.z = s.c.z + w * cq.z;
-}
-
-RT_HD float dn_k(int o) {  // B3 spline {1/16, 1/4, 3/8, 1/4, 1/16}
-    const int a = o < 0 ? -o : o;
-    return a == 0 ? 0.375f : a == 1 ? 0.25f : 0.0625f;
-}
-
-// The filtered colour of pixel (x, y).  fetch(dx, dy, qx, qy, c, a, b) gives
-// the colour and the two guide words of the in-image tap (qx, qy) = (x + dx s,
-// y + dy s): from global memory (direct kernel, CPU) or from an LDS tile.
+// The filtered colour of pixel (x, y) (fetch: rt_atrous.h)
 template <class Fetch>
 RT_HD f3 dn_pixel(const rt_dn_level& L, int x, int y, const Fetch& fetch) {
-    f3 cp;
-    float4 ap, bp;
+    float4 cp, ap, bp;
     fetch(0, 0, x, y, cp, ap, bp);
-    const f3 np = mk(ap.x, ap.y, ap.z), Pp = mk(bp.x, bp.y, bp.z);
-    const bool missp = rt_f2i(ap.w) < 0;
-    DnSums s;
-    s.w = 0.0f;
-    s.c = mk(0.0f, 0.0f, 0.0f);
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-        const int qy = y + dy * L.step;
-        if (qy < 0 || qy >= L.height) continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const int qx = x + dx * L.step;
-            if (qx < 0 || qx >= L.width) continue;
-            f3 cq;
-            float4 aq, bq;
-            fetch(dx, dy, qx, qy, cq, aq, bq);
-            if ((rt_f2i(aq.w) < 0) != missp) continue;
-            dn_tap(L, dn_k(dy) * dn_k(dx), cp, np, Pp, cq, mk(aq.x, aq.y, aq.z), mk(bq.x, bq.y, bq.z), s);
-        }
-    }
-    if (s.w > 0.0f) return mk(rt_div(s.c.x, s.w), rt_div(s.c.y, s.w), rt_div(s.c.z, s.w));
-    return cp;
+    DnTap t{L, mk(cp.x, cp.y, cp.z), mk(ap.x, ap.y, ap.z), mk(bp.x, bp.y, bp.z), 0.0f, mk(0.0f, 0.0f, 0.0f)};
+    at_walk(L.f, x, y, rt_f2i(ap.w) < 0, fetch, t);
+    if (t.w > 0.0f) return mk(rt_div(t.c.x, t.w), rt_div(t.c.y, t.w), rt_div(t.c.z, t.w));
+    return t.cp;
 }
 
-// taps straight from the frame's buffers
+// the filter as rt_atrous.h takes it; FIRST: level 0 of a call without a source
+// colour reads inv * frameSum
 template <bool FIRST>
-struct DnGlobalFetch {
-    const rt_dn_level& L;
-    RT_HD void operator()(int, int, int qx, int qy, f3& c, float4& a, float4& b) const {
-        const long q = (long)qy * L.width + qx;
-        a = L.ga[q];
-        b = L.gb[q];
-        c = dn_color<FIRST>(L, q);
+struct DnFilter {
+    using Args = rt_dn_level;
+    static RT_HD float4 texel(const rt_dn_level& L, long q) {
+        if (!FIRST) return L.f.src[q];  // (.w: not read; rt_temporal's source carries the history length there)
+        const f3 c = at_c0(L.f, q);
+        return make_float4(c.x, c.y, c.z, 0.0f);
+    }
+    template <class Fetch>
+    static RT_HD void run(const rt_dn_level& L, int x, int y, const Fetch& fetch) {
+        const f3 c = dn_pixel(L, x, y, fetch);
+        at_store(L.f, (long)y * L.f.width + x, make_float4(c.x, c.y, c.z, 0.0f));
     }
 };
-
-RT_HD void dn_store(const rt_dn_level& L, long p, f3 c) {
-    L.dst[p] = make_float4(c.x, c.y, c.z, 0.0f);
-    if (L.last && L.rgba) L.rgba[p] = tone_map(c.x, c.y, c.z, 1u);
-}
 
 }  // namespace

@@ -14,7 +14,7 @@
 // (otherwise): over the 7 x 7 unit-step window around p, dy outer, dx inner,
 // skipping q outside the image, of the other hit / miss class or with a
 // non-finite colour channel:
-//   wn = exp_nn(-(en + ex))   en, ex as rt_denoise.h forms them
+//   wn = exp_nn(-(en + ex))   en, ex as rt_denoise.h forms them (rt_atrous.h at_geom)
 //   l = lum(c_q);  s0 += wn;  s1 += wn l;  s2 += wn (l l)
 // v0 = fmaxf(s2 / s0 - m1 m1, 0), m1 = s1 / s0; 0 unless s0 > 0.
 //
@@ -38,44 +38,30 @@
 
 namespace {
 
-RT_HD bool dv_finite(float x) { return (rt_f2i(x) & 0x7f800000) != 0x7f800000; }
-
-RT_HD f3 dv_c0(const rt_dv_args& A, long q) {
-    const long npix = (long)A.width * A.height;
-    return mk(A.inv * A.accum[q], A.inv * A.accum[npix + q], A.inv * A.accum[2 * npix + q]);
-}
-
-// the geometry terms en, ex of a tap, as rt_denoise.h dn_tap
-RT_HD void dv_geom(const rt_dv_args& A, f3 np, f3 Pp, f3 nq, f3 Pq, float& en, float& ex) {
-    const f3 dn = sub(nq, np);
-    en = dot(dn, dn) * A.in;
-    const float pd = dot(np, sub(Pq, Pp));
-    ex = (pd * pd) * A.ip;
-}
-
 // Input stage of pixel p = (x, y): {c0, v0}
 RT_HD float4 dv_input(const rt_dv_args& A, int x, int y) {
-    const long p = (long)y * A.width + x;
-    const f3 c = dv_c0(A, p);
+    const rt_at_frame& F = A.f;
+    const long p = (long)y * F.width + x;
+    const f3 c = at_c0(F, p);
     if (A.tracked) return make_float4(c.x, c.y, c.z, A.mom[p].y * A.rd);
-    const float4 ap = A.ga[p], bp = A.gb[p];
+    const float4 ap = F.ga[p], bp = F.gb[p];
     const f3 np = mk(ap.x, ap.y, ap.z), Pp = mk(bp.x, bp.y, bp.z);
     const bool missp = rt_f2i(ap.w) < 0;
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
     for (int dy = -3; dy <= 3; dy++) {
         const int qy = y + dy;
-        if (qy < 0 || qy >= A.height) continue;
+        if (qy < 0 || qy >= F.height) continue;
         for (int dx = -3; dx <= 3; dx++) {
             const int qx = x + dx;
-            if (qx < 0 || qx >= A.width) continue;
-            const long q = (long)qy * A.width + qx;
-            const float4 aq = A.ga[q];
+            if (qx < 0 || qx >= F.width) continue;
+            const long q = (long)qy * F.width + qx;
+            const float4 aq = F.ga[q];
             if ((rt_f2i(aq.w) < 0) != missp) continue;
-            const f3 cq = dv_c0(A, q);
-            if (!dv_finite(cq.x) || !dv_finite(cq.y) || !dv_finite(cq.z)) continue;
-            const float4 bq = A.gb[q];
+            const f3 cq = at_c0(F, q);
+            if (!at_finite(cq.x) || !at_finite(cq.y) || !at_finite(cq.z)) continue;
+            const float4 bq = F.gb[q];
             float en, ex;
-            dv_geom(A, np, Pp, mk(aq.x, aq.y, aq.z), mk(bq.x, bq.y, bq.z), en, ex);
+            at_geom(F, np, Pp, mk(aq.x, aq.y, aq.z), mk(bq.x, bq.y, bq.z), en, ex);
             const float wn = exp_nn(-(en + ex));
             const float l = mom_lum(cq.x, cq.y, cq.z);
             s0 = s0 + wn;
@@ -91,22 +77,18 @@ RT_HD float4 dv_input(const rt_dv_args& A, int x, int y) {
     return make_float4(c.x, c.y, c.z, v);
 }
 
-RT_HD void dv_store(const rt_dv_args& A, long p, float4 c) {
-    A.dst[p] = c;
-    if (A.last && A.rgba) A.rgba[p] = tone_map(c.x, c.y, c.z, 1u);
-}
-
-// Sigma pass of pixel (x, y): the reciprocal luminance sigma from A.src's .w
+// Sigma pass of pixel (x, y): the reciprocal luminance sigma from src's .w
 RT_HD float dv_sigma(const rt_dv_args& A, int x, int y) {
+    const rt_at_frame& F = A.f;
     float sv = 0.0f, sw = 0.0f;
     for (int dy = -1; dy <= 1; dy++) {
         const int qy = y + dy;
-        if (qy < 0 || qy >= A.height) continue;
+        if (qy < 0 || qy >= F.height) continue;
         for (int dx = -1; dx <= 1; dx++) {
             const int qx = x + dx;
-            if (qx < 0 || qx >= A.width) continue;
-            const float v = A.src[(long)qy * A.width + qx].w;
-            if (!dv_finite(v)) continue;
+            if (qx < 0 || qx >= F.width) continue;
+            const float v = F.src[(long)qy * F.width + qx].w;
+            if (!at_finite(v)) continue;
             const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
             sv = sv + k * v;
             sw = sw + k;
@@ -117,59 +99,50 @@ RT_HD float dv_sigma(const rt_dv_args& A, int x, int y) {
     return rt_div(1.0f, A.sigma_lum * rt_sqrt(g) + 1e-10f);
 }
 
-// The filtered {colour, variance} of pixel (x, y).  fetch(dx, dy, qx, qy, c, a,
-// b) gives the colour + variance and the two guide words of the in-image tap
-// (qx, qy) = (x + dx s, y + dy s): from global memory (direct kernel, CPU) or
-// from an LDS tile.
+// the centre and the sums of one pixel of a level; operator() is one tap
+struct DvTap {
+    const rt_at_frame& F;
+    f3 np, Pp;
+    float lp, rs;
+    float w, v;
+    f3 c;
+    RT_HD void operator()(float h, float4 cq, f3 nq, f3 Pq) {
+        if (!at_finite(cq.w)) return;
+        const float ec = fabsf(mom_lum(cq.x, cq.y, cq.z) - lp) * rs;
+        float en, ex;
+        at_geom(F, np, Pp, nq, Pq, en, ex);
+        const float e = (ec + en) + ex;
+        if (!(e >= 0.0f)) return;
+        const float wt = h * exp_nn(-e);
+        if (!(wt > 0.0f)) return;
+        w = w + wt;
+        c.x = c.x + wt * cq.x;
+        c.y = c.y + wt * cq.y;
+        c.z = c.z + wt * cq.z;
+        v = v + (wt * wt) * cq.w;
+    }
+};
+
+// The filtered {colour, variance} of pixel (x, y) (fetch: rt_atrous.h)
 template <class Fetch>
 RT_HD float4 dv_pixel(const rt_dv_args& A, int x, int y, const Fetch& fetch) {
     float4 cp, ap, bp;
     fetch(0, 0, x, y, cp, ap, bp);
-    if (!dv_finite(cp.x) || !dv_finite(cp.y) || !dv_finite(cp.z) || !dv_finite(cp.w)) return cp;
-    const float rs = A.rs[(long)y * A.width + x];
-    const f3 np = mk(ap.x, ap.y, ap.z), Pp = mk(bp.x, bp.y, bp.z);
-    const bool missp = rt_f2i(ap.w) < 0;
-    const float lp = mom_lum(cp.x, cp.y, cp.z);
-    float sw = 0.0f, sv = 0.0f;
-    f3 sc = mk(0.0f, 0.0f, 0.0f);
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-        const int qy = y + dy * A.step;
-        if (qy < 0 || qy >= A.height) continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const int qx = x + dx * A.step;
-            if (qx < 0 || qx >= A.width) continue;
-            float4 cq, aq, bq;
-            fetch(dx, dy, qx, qy, cq, aq, bq);
-            if ((rt_f2i(aq.w) < 0) != missp) continue;
-            if (!dv_finite(cq.w)) continue;
-            const float ec = fabsf(mom_lum(cq.x, cq.y, cq.z) - lp) * rs;
-            float en, ex;
-            dv_geom(A, np, Pp, mk(aq.x, aq.y, aq.z), mk(bq.x, bq.y, bq.z), en, ex);
-            const float e = (ec + en) + ex;
-            if (!(e >= 0.0f)) continue;
-            const float w = (dn_k(dy) * dn_k(dx)) * exp_nn(-e);
-            if (!(w > 0.0f)) continue;
-            sw = sw + w;
-            sc.x = sc.x + w * cq.x;
-            sc.y = sc.y + w * cq.y;
-            sc.z = sc.z + w * cq.z;
-            sv = sv + (w * w) * cq.w;
-        }
-    }
-    if (!(sw > 0.0f)) return cp;
-    return make_float4(rt_div(sc.x, sw), rt_div(sc.y, sw), rt_div(sc.z, sw), rt_div(sv, sw * sw));
+    if (!at_finite(cp.x) || !at_finite(cp.y) || !at_finite(cp.z) || !at_finite(cp.w)) return cp;
+    DvTap t{A.f, mk(ap.x, ap.y, ap.z), mk(bp.x, bp.y, bp.z), mom_lum(cp.x, cp.y, cp.z),
+            A.rs[(long)y * A.f.width + x], 0.0f, 0.0f, mk(0.0f, 0.0f, 0.0f)};
+    at_walk(A.f, x, y, rt_f2i(ap.w) < 0, fetch, t);
+    if (!(t.w > 0.0f)) return cp;
+    return make_float4(rt_div(t.c.x, t.w), rt_div(t.c.y, t.w), rt_div(t.c.z, t.w), rt_div(t.v, t.w * t.w));
 }
 
-// taps straight from the frame's buffers
-struct DvGlobalFetch {
-    const rt_dv_args& A;
-    RT_HD void operator()(int, int, int qx, int qy, float4& c, float4& a, float4& b) const {
-        const long q = (long)qy * A.width + qx;
-        a = A.ga[q];
-        b = A.gb[q];
-        c = A.src[q];
+// the filter's level as rt_atrous.h takes it
+struct DvFilter {
+    using Args = rt_dv_args;
+    static RT_HD float4 texel(const rt_dv_args& A, long q) { return A.f.src[q]; }
+    template <class Fetch>
+    static RT_HD void run(const rt_dv_args& A, int x, int y, const Fetch& fetch) {
+        at_store(A.f, (long)y * A.f.width + x, dv_pixel(A, x, y, fetch));
     }
 };
 

@@ -1,5 +1,5 @@
 // rt_layout.h — device-side data layout shared by the host scene compiler
-// (rt_context.cpp) and the HIP kernels (rt_kernels.hip).
+// (rt_scene.cpp) and the HIP kernels (rt_kernels.hip).
 //
 // The scene is "compiled" once on upload: every quantity the reference
 // recomputes per ray but that depends only on the primitive (plane normal
@@ -50,7 +50,7 @@
 #define RT_MAX_LEVELS 33           // recursion records per path: RT_MAX_BOUNCES (rt_abi.h) + 1
 
 // diagnostic builds (-DRT_GTIMES, BWRT_GTIMES): words of the group / lane
-// time buffer (rt_diag.h; rt_context.cpp allocates it)
+// time buffer (rt_diag.h; rt_render.cpp allocates it)
 #define RT_GTIMES_WORDS (1ull << 22)
 
 struct rt_kparams {
@@ -168,21 +168,29 @@ struct rt_kparams {
 // keeps the LAST tested primitive, i.e. the largest key.
 #define RT_KEY(kind, i) ((i) * 4 + (kind))
 
-// One level of the denoiser (rt_denoise.h) over a full width x height frame
-// (float4: every includer has <hip/hip_runtime.h> first).
-struct rt_dn_level {
+// The frame of one a-trous pass over a full width x height image: what the two
+// filters (rt_denoise.h, rt_denoise_var.h) share and the common code
+// (rt_atrous.h, rt_atrous_tile.h) takes (float4: every includer has
+// <hip/hip_runtime.h> first).
+struct rt_at_frame {
     int width, height;
-    int step;            // 1 << level
-    int first;           // colour in = inv * frameSum (tone_map's first step), else src
+    int step;            // level: 1 << level
     int last;            // also write tone_map(c, 1) to rgba (when non-null)
-    float ic, in, ip;    // 1 / sigma^2 of the colour (this level's), normal and plane terms
+    float in, ip;        // 1 / sigma^2 of the normal and plane terms
     float inv;           // rt_div(1, n), n = frame counter - 1
     const float* accum;  // frameSum, 3 planes of width * height
-    const float4* src;   // colour of the previous level
-    float4* dst;         // colour of this level {r, g, b, 0}
+    const float4* src;   // colour of the previous level or stage
+    float4* dst;         // colour of this one
     unsigned* rgba;
     const float4* ga;    // guides {n.xyz, prim as bits}
     const float4* gb;    //        {P.xyz, depth}
+};
+
+// One level of the denoiser (rt_denoise.h): dst holds {r, g, b, 0}.
+struct rt_dn_level {
+    rt_at_frame f;
+    int first;           // colour in = inv * frameSum (tone_map's first step), else src
+    float ic;            // 1 / sigma^2 of the colour term (this level's)
 };
 
 // One temporal reprojection pass (rt_temporal.h) over a full width x height
@@ -223,23 +231,14 @@ struct rt_mom_args {
     float2* mom;         // {M, M2}: weighted mean of the batch luminances and sum of k_j (l_j - mean)^2
 };
 
-// One pass of the variance-guided filter (rt_denoise_var.h) over a full width
-// x height frame: the input stage, a sigma pass or a level.
+// One pass of the variance-guided filter (rt_denoise_var.h): the input stage
+// (reads accum, writes dst), a sigma pass (reads src) or a level; src and dst
+// hold {colour, variance}.
 struct rt_dv_args {
-    int width, height;
-    int step;            // level: 1 << level
-    int last;            // input stage and level: also write tone_map(c, 1) to rgba (when non-null)
+    rt_at_frame f;
     int tracked;         // input stage: v0 from the tracked moments, else the spatial estimate
-    float in, ip;        // 1 / sigma^2 of the normal and plane terms
-    float inv;           // 1 / n, n = frame counter - 1
     float rd;            // tracked: 1 / ((J - 1) n)
     float sigma_lum;     // sigma pass
-    const float* accum;  // input stage: frameSum, 3 planes of width * height
     const float2* mom;   // input stage, tracked: {M, M2}
-    const float4* src;   // sigma pass and level: {colour, variance} of the previous stage
-    float4* dst;         // input stage and level: {colour, variance}
     float* rs;           // reciprocal luminance sigma: the sigma pass writes it, the level reads its centre
-    unsigned* rgba;
-    const float4* ga;    // guides {n.xyz, prim as bits}
-    const float4* gb;    //        {P.xyz, depth}
 };

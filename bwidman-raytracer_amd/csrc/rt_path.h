@@ -467,7 +467,7 @@ RT_HD bool polygon_edges(cfloat_ptr q, int nv, f3 P) {
 //   |w|^2 a (1 - 2^-14) - (w.d)^2 > Rc^2 a,   w = c - o,  a = |d|^2
 // i.e. distance^2 > Rc^2 + 2^-14 |w|^2 (the 2^-14 term dominates the
 // evaluation error, ~2^-22 |w|^2), and only for origins within the scene
-// scale (rt_context.cpp cull_sphere: the reference rejects every such
+// scale (rt_scene.cpp cull_sphere: the reference rejects every such
 // polygon).  NaN/inf rays compare false and are never culled.
 struct CullRay {
     float a, a_k;  // |d|^2, |d|^2 (1 - 2^-14)
@@ -726,7 +726,7 @@ RT_HD void leaf_test(const rt_kparams& K, const float* r, f3 o, f3 d, float a2, 
     }
     if (VTX) {
         // {key, v0 | v1, v2.x | v2.yz, v3.xy | v3.z}: edges, normal, offset and
-        // inner normals exactly as compile_polygon (rt_context.cpp) forms them
+        // inner normals exactly as compile_polygon (rt_scene.cpp) forms them
         const f3 v0 = mk(c0.y, c0.z, c0.w), v1 = mk(c1.x, c1.y, c1.z), v2 = mk(c1.w, c2.x, c2.y);
         const f3 n = cross(sub(v1, v0), sub(v2, v1));
         const float dd = -dot(n, v0);
@@ -825,7 +825,7 @@ RT_HD AovHit aov_shade(const rt_kparams& K, f3 o, f3 d, float t, int id) {
 //   L = emitted + (brdf * L) * cosAngle,  emitted = emittance * albedo,
 //   brdf = kspec * {1,1,1} (specular) or 4 * albedo (diffuse, :259).
 RT_HD void fold_level(int c0, float k, float c, const float* hit_tab, float& lx, float& ly, float& lz) {
-    // hit table (rt_context.cpp put_material): [4..6] emitted = emittance *
+    // hit table (rt_scene.cpp put_material): [4..6] emitted = emittance *
     // albedo, [12..14] diffuse brdf = (2/(1-specularChance)) * albedo, both
     // formed on the host with the same single float multiplications
     const bool spec = c0 < 0;

@@ -6,6 +6,7 @@
 // render kernels only).  Compiled with -ffp-contract=off (fill_view's camera
 // prelude, the sigma terms).
 #include <cmath>
+#include <initializer_list>
 
 #include "rt_context.h"
 
@@ -77,203 +78,200 @@ int full_frame_check(rt_context* c, const char* who) {
     return RT_OK;
 }
 
-// The conditions of a denoise call (and of the filter part of a temporal one)
-static int denoise_check(rt_context* c, const rt_denoise_params* dp) {
-    if (!c || !dp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (dp->iterations < 0 || dp->iterations > RT_DENOISE_MAX_ITERATIONS)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "iterations %d outside 0..%d", dp->iterations,
-                    RT_DENOISE_MAX_ITERATIONS);
-    if (!(dp->sigma_color > 0.0f) || !(dp->sigma_normal > 0.0f) || !(dp->sigma_plane > 0.0f))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "sigmas must be > 0 (colour %g, normal %g, plane %g)",
-                    (double)dp->sigma_color, (double)dp->sigma_normal, (double)dp->sigma_plane);
-    return full_frame_check(c, "the denoiser");
+// iterations and sigmas of a filter (`term`: what its first sigma weighs)
+int filter_check(rt_context* c, int iterations, const char* term, float s0, float sn, float sp) {
+    if (iterations < 0 || iterations > RT_DENOISE_MAX_ITERATIONS)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "iterations %d outside 0..%d", iterations, RT_DENOISE_MAX_ITERATIONS);
+    if (!(s0 > 0.0f) || !(sn > 0.0f) || !(sp > 0.0f))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "sigmas must be > 0 (%s %g, normal %g, plane %g)", term, (double)s0,
+                    (double)sn, (double)sp);
+    return RT_OK;
 }
 
-// Every level of one denoise call; the final colour ends in dn_col[*final_buf]
-// and, tone-mapped, in rgba (device pointer on a GPU context; may be null).
-// src0 non-null (rt_temporal; iterations >= 1): level 0 filters that colour
-// buffer instead of inv * frameSum.
-int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_t s, unsigned* rgba, int* final_buf,
+// The conditions of a denoise call (and of the filter part of a temporal one)
+int denoise_check(rt_context* c, const rt_denoise_params* dp) {
+    if (!c || !dp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    const int rc = filter_check(c, dp->iterations, "colour", dp->sigma_color, dp->sigma_normal, dp->sigma_plane);
+    return rc ? rc : full_frame_check(c, "the denoiser");
+}
+
+// A buffer of a full-frame pass: `elem` bytes per pixel, and the message of a
+// CPU context that cannot allocate it
+struct Need {
+    Buf* buf;
+    size_t elem;
+    const char* host_oom;
+};
+
+// Everything a full-frame pass (`who`) on stream s does before its first
+// kernel: the frame check, the device, the pass's events (on first use), its
+// buffers, then stream s ordered after the render that made the frame (and its
+// moment update) and after every earlier pass (they share the guides, the
+// colour buffers and the history sets, whatever streams they ran on), and the
+// guides.
+int prepare_frame(rt_context* c, const char* who, Pass& pass, hipStream_t s, std::initializer_list<Need> bufs) {
+    int rc = full_frame_check(c, who);
+    if (rc) return rc;
+    const size_t npix = (size_t)c->height * c->width;
+    if (!c->cpu) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, pass.create(true));
+    }
+    for (const Need& n : bufs)
+        if ((rc = ensure_buf(c, *n.buf, npix * n.elem, n.host_oom, npix))) return rc;
+    if ((rc = order_after_all(c, s))) return rc;
+    return ensure_guides(c, s);
+}
+
+Need colour_buf(Buf& b) { return {&b, sizeof(float4), "host colour buffers for %zu pixels"}; }
+
+// The fields of an a-trous frame that hold for every pass of one call
+void fill_frame(const rt_context* c, float sigma_normal, float sigma_plane, rt_at_frame& F) {
+    F.width = c->width;
+    F.height = c->height;
+    F.inv = 1.0f / (float)(c->frame - 1u);
+    F.in = 1.0f / (sigma_normal * sigma_normal);
+    F.ip = 1.0f / (sigma_plane * sigma_plane);
+    F.accum = c->accum.as<float>();
+    F.ga = c->guide_a.as<float4>();
+    F.gb = c->guide_b.as<float4>();
+}
+
+// The variant of a filter level on a GPU context.  BWRT_DENOISE_KERNEL forces
+// one; the policy is the per-level winner at 1920x1080, the same for both
+// filters: the LDS-tiled kernel up to step 16, the direct one at step 32 (the
+// tile's 108 KiB leave one workgroup per CU).
+//   rt_denoise, tools/time_denoise.py (profiles/denoise/):
+//     tiled 0.084-0.139 against 0.17-0.19 ms up to step 16, direct 0.24 against
+//     0.31 ms at step 32
+//   rt_denoise_var, tools/time_denoise_var.py (profiles/denoise_var/, DESIGN.md
+//     section 11; sigma pass included): tiled 0.120-0.171 against 0.195-0.206
+//     ms up to step 16, direct 0.236 against 0.346 ms at step 32
+bool level_tiled(const rt_context* c, int step) { return c->dn_kernel >= 0 ? c->dn_kernel == 1 : step <= 16; }
+
+// Where a pass left its result for read_back
+struct Result {
+    const Buf* color = nullptr;
+    const Buf* length = nullptr;
+};
+
+// Every level of one denoise call on stream s; the final colour ends in
+// out.color and, tone-mapped, in rgba (device pointer on a GPU context; may be
+// null).  src0 non-null (rt_temporal; iterations >= 1): level 0 filters that
+// colour buffer instead of inv * frameSum.
+int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_t s, unsigned* rgba, Result& out,
                    const float4* src0 = nullptr) {
     const HostFpEnv fp;
     int rc = denoise_check(c, dp);
-    if (rc) return rc;
-    const size_t npix = (size_t)c->height * c->width;
-    if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
-    for (Buf& b : c->dn_col)
-        if ((rc = ensure_buf(c, b, npix * sizeof(float4), "host colour buffers for %zu pixels", npix))) return rc;
-    // after the render that made the frame, a previous denoise (shared colour
-    // buffers and guides) and a reprojection pass (it reads the guides; its
-    // filter writes the colour buffers), whatever streams they ran on
-    if ((rc = order_after_all(c, s))) return rc;
-    rc = ensure_guides(c, s);
+    if (!rc) rc = prepare_frame(c, "the denoiser", c->denoise, s, {colour_buf(c->dn_col[0]), colour_buf(c->dn_col[1])});
     if (rc) return rc;
     rt_dn_level L;
     std::memset(&L, 0, sizeof L);
-    L.width = c->width;
-    L.height = c->height;
-    L.inv = 1.0f / (float)(c->frame - 1u);
-    L.in = 1.0f / (dp->sigma_normal * dp->sigma_normal);
-    L.ip = 1.0f / (dp->sigma_plane * dp->sigma_plane);
-    L.accum = c->accum.as<float>();
-    L.ga = c->guide_a.as<float4>();
-    L.gb = c->guide_b.as<float4>();
+    fill_frame(c, dp->sigma_normal, dp->sigma_plane, L.f);
     float4* col[2] = {c->dn_col[0].as<float4>(), c->dn_col[1].as<float4>()};
     HIP_TRY(c, c->denoise.begin(s, true));
     const int levels = dp->iterations;
     for (int i = 0; i < (levels > 0 ? levels : 1); i++) {
-        L.step = levels > 0 ? 1 << i : 0;  // step 0: the conversion pass of iterations == 0
+        L.f.step = levels > 0 ? 1 << i : 0;  // step 0: the conversion pass of iterations == 0
         const float sc = dp->sigma_color * std::ldexp(1.0f, -i);
         L.ic = 1.0f / (sc * sc);
         L.first = i == 0 && !src0;
-        L.last = i >= levels - 1;
-        L.src = i > 0 ? col[(i - 1) & 1] : src0;
-        L.dst = col[i & 1];
-        L.rgba = L.last ? rgba : nullptr;
-        if (c->cpu) {
+        L.f.last = i >= levels - 1;
+        L.f.src = i > 0 ? col[(i - 1) & 1] : src0;
+        L.f.dst = col[i & 1];
+        L.f.rgba = L.f.last ? rgba : nullptr;
+        if (c->cpu)
             rt_cpu_denoise_level(L, c->threads);
-        } else {
-            // BWRT_DENOISE_KERNEL forces a variant; the policy is the per-level
-            // winner of tools/time_denoise.py at 1920x1080 (profiles/denoise/,
-            // DESIGN.md section 9): the LDS-tiled kernel up to step 16 (0.084-0.139
-            // against 0.17-0.19 ms), the direct one at step 32 (0.24 against 0.31
-            // ms: the tile's 108 KiB leave one workgroup per CU)
-            const bool tiled = c->dn_kernel >= 0 ? c->dn_kernel == 1 : L.step <= 16;
-            HIP_TRY(c, rt_launch_denoise_level(L, tiled, s));
-        }
+        else
+            HIP_TRY(c, rt_launch_denoise_level(L, level_tiled(c, L.f.step), s));
     }
-    *final_buf = levels > 0 ? (levels - 1) & 1 : 0;
+    out.color = &c->dn_col[levels > 0 ? (levels - 1) & 1 : 0];
     HIP_TRY(c, c->denoise.end(s));
     return RT_OK;
 }
 
 // The variance-guided filter (rt_denoise_var.h) of one call on stream s: the
 // input stage, then per level a sigma pass and the level.  The final {colour,
-// variance} ends in dn_col[*final_buf] and, tone-mapped, in rgba (device
+// variance} ends in out.color = out.length and, tone-mapped, in rgba (device
 // pointer on a GPU context; may be null).
-int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream_t s, unsigned* rgba,
-                       int* final_buf) {
+int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream_t s, unsigned* rgba, Result& out) {
     const HostFpEnv fp;
     if (!c || !dp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (dp->iterations < 0 || dp->iterations > RT_DENOISE_MAX_ITERATIONS)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "iterations %d outside 0..%d", dp->iterations,
-                    RT_DENOISE_MAX_ITERATIONS);
-    if (!(dp->sigma_lum > 0.0f) || !(dp->sigma_normal > 0.0f) || !(dp->sigma_plane > 0.0f))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "sigmas must be > 0 (luminance %g, normal %g, plane %g)",
-                    (double)dp->sigma_lum, (double)dp->sigma_normal, (double)dp->sigma_plane);
-    if (dp->min_batches < 2) return fail(c, RT_ERR_INVALID_ARGUMENT, "min_batches %d < 2", dp->min_batches);
-    int rc = full_frame_check(c, "the denoiser");
+    int rc = filter_check(c, dp->iterations, "luminance", dp->sigma_lum, dp->sigma_normal, dp->sigma_plane);
     if (rc) return rc;
-    const size_t npix = (size_t)c->height * c->width;
-    if (!c->cpu) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, c->denoise_var.create(true));  // on first use
-    }
-    for (Buf& b : c->dn_col)
-        if ((rc = ensure_buf(c, b, npix * sizeof(float4), "host colour buffers for %zu pixels", npix))) return rc;
-    if ((rc = ensure_buf(c, c->dn_rs, npix * sizeof(float), "host sigma plane for %zu pixels", npix))) return rc;
-    // after the render that made the frame (and its moment update), and after
-    // every pass that shares the guides and the colour buffers
-    if ((rc = order_after_all(c, s))) return rc;
-    rc = ensure_guides(c, s);
+    if (dp->min_batches < 2) return fail(c, RT_ERR_INVALID_ARGUMENT, "min_batches %d < 2", dp->min_batches);
+    rc = prepare_frame(c, "the denoiser", c->denoise_var, s,
+                       {colour_buf(c->dn_col[0]), colour_buf(c->dn_col[1]),
+                        {&c->dn_rs, sizeof(float), "host sigma plane for %zu pixels"}});
     if (rc) return rc;
     rt_dv_args A;
     std::memset(&A, 0, sizeof A);
-    A.width = c->width;
-    A.height = c->height;
-    const float n = (float)(c->frame - 1u);
-    A.inv = 1.0f / n;
-    A.in = 1.0f / (dp->sigma_normal * dp->sigma_normal);
-    A.ip = 1.0f / (dp->sigma_plane * dp->sigma_plane);
+    fill_frame(c, dp->sigma_normal, dp->sigma_plane, A.f);
     A.sigma_lum = dp->sigma_lum;
     // the tracked variance of this very frame, else the spatial estimate
     A.tracked = c->mom_live && c->mom_next == c->frame && c->mom_batches >= (unsigned)dp->min_batches;
     if (A.tracked) {
-        A.rd = 1.0f / ((float)(c->mom_batches - 1u) * n);
+        A.rd = 1.0f / ((float)(c->mom_batches - 1u) * (float)(c->frame - 1u));
         A.mom = c->mom_m.as<float2>();
     }
-    A.accum = c->accum.as<float>();
-    A.ga = c->guide_a.as<float4>();
-    A.gb = c->guide_b.as<float4>();
     A.rs = c->dn_rs.as<float>();
     float4* col[2] = {c->dn_col[0].as<float4>(), c->dn_col[1].as<float4>()};
-    auto pass = [&](int stage) -> int {
-        if (c->cpu) {
+    const int levels = dp->iterations;
+    // stage 0 into col[0], then level i (sigma pass and level) from col[i & 1] into the other
+    auto pass = [&](int stage, int i) -> int {
+        A.f.last = i == levels - 1;
+        A.f.rgba = A.f.last ? rgba : nullptr;
+        if (c->cpu)
             rt_cpu_denoise_var(A, stage, c->threads);
-            return RT_OK;
-        }
-        // BWRT_DENOISE_KERNEL forces a variant; the policy is the per-level
-        // winner of tools/time_denoise_var.py at 1920x1080 (profiles/denoise_var/,
-        // DESIGN.md section 11; sigma pass included): the LDS-tiled kernel up to
-        // step 16 (0.120-0.171 against 0.195-0.206 ms), the direct one at step 32
-        // (0.236 against 0.346 ms)
-        const bool tiled = c->dn_kernel >= 0 ? c->dn_kernel == 1 : A.step <= 16;
-        HIP_TRY(c, rt_launch_denoise_var(A, stage, tiled, s));
+        else
+            HIP_TRY(c, rt_launch_denoise_var(A, stage, level_tiled(c, A.f.step), s));
         return RT_OK;
     };
     HIP_TRY(c, c->denoise_var.begin(s, true));
-    const int levels = dp->iterations;
-    A.dst = col[0];
-    A.last = levels == 0;
-    A.rgba = A.last ? rgba : nullptr;
-    if ((rc = pass(0))) return rc;
+    A.f.dst = col[0];
+    if ((rc = pass(0, -1))) return rc;
     for (int i = 0; i < levels; i++) {
-        A.step = 1 << i;
-        A.src = col[i & 1];
-        A.dst = col[(i + 1) & 1];
-        A.last = i == levels - 1;
-        A.rgba = A.last ? rgba : nullptr;
-        if ((rc = pass(1)) || (rc = pass(2))) return rc;
+        A.f.step = 1 << i;
+        A.f.src = col[i & 1];
+        A.f.dst = col[(i + 1) & 1];
+        if ((rc = pass(1, i)) || (rc = pass(2, i))) return rc;
     }
-    *final_buf = levels & 1;
+    out.color = out.length = &c->dn_col[levels & 1];
     HIP_TRY(c, c->denoise_var.end(s));
     return RT_OK;
 }
 
-static int temporal_check(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn) {
+int temporal_check(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn) {
     if (!c || !tp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
     if (!(tp->max_history > 0.0f) || !(tp->plane_tol > 0.0f) ||
         !(tp->normal_cos_min >= -1.0f && tp->normal_cos_min <= 1.0f))
         return fail(c, RT_ERR_INVALID_ARGUMENT,
                     "max_history and plane_tol must be > 0, normal_cos_min in -1..1 (%g, %g, %g)",
                     (double)tp->max_history, (double)tp->plane_tol, (double)tp->normal_cos_min);
-    if (dn) {
-        const int rc = denoise_check(c, dn);
-        if (rc) return rc;
-    }
-    return full_frame_check(c, "reprojection");
+    return dn ? denoise_check(c, dn) : RT_OK;
 }
 
 // One temporal call on stream s: promote, reproject, store the pending result
-// of the current view in tp[*set]; with a filter (dn, iterations >= 1) its
-// levels follow and *filtered_buf is the dn_col buffer of the final colour
-// (else -1: the final colour is the pending one).  rgba: device pointer on a
-// GPU context; may be null.
+// of the current view {colour, history length} in out.length; with a filter
+// (dn, iterations >= 1) its levels follow and out.color is their final colour,
+// else the pending one.  rgba: device pointer on a GPU context; may be null.
 int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn, hipStream_t s,
-                  unsigned* rgba, int* set, int* filtered_buf) {
+                  unsigned* rgba, Result& out) {
     const HostFpEnv fp;
     int rc = temporal_check(c, tp, dn);
+    if (!rc) {
+        auto hist = [](Buf& b) { return Need{&b, sizeof(float4), "host history buffers for %zu pixels"}; };
+        rt_context::TpSet *t0 = &c->tp[0], *t1 = &c->tp[1];
+        rc = prepare_frame(c, "reprojection", c->temporal, s,
+                           {hist(t0->col), hist(t0->ga), hist(t0->gb), hist(t1->col), hist(t1->ga), hist(t1->gb)});
+    }
     if (rc) return rc;
     const bool filter = dn && dn->iterations > 0;
-    const size_t npix = (size_t)c->height * c->width;
     if (c->tp_w != c->width || c->tp_h != c->height) {  // (rt_init_rand dropped them already)
         c->tp_has_hist = c->tp_has_pending = false;
         c->tp_w = c->width;
         c->tp_h = c->height;
     }
-    if (!c->cpu) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, c->temporal.create(true));  // on first use
-    }
-    for (rt_context::TpSet& t : c->tp)
-        for (Buf* b : {&t.col, &t.ga, &t.gb})
-            if ((rc = ensure_buf(c, *b, npix * sizeof(float4), "host history buffers for %zu pixels", npix))) return rc;
-    // after the render that made the frame, a previous denoise (the guides;
-    // its levels may still read a pending colour) and a previous temporal
-    // call (it reads the set this one writes), whatever streams they ran on
-    if ((rc = order_after_all(c, s))) return rc;
-    rc = ensure_guides(c, s);
-    if (rc) return rc;
     // the first call of a later view: the pending result becomes the history.
     // The swap is of host-side roles only; the stream waits above order this
     // call's kernel after every earlier reader of the set it now writes.
@@ -320,22 +318,34 @@ int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_
     P.screen_z = K.screen_z;
     c->tp_has_pending = true;
     c->tp_pending_view = c->view;
-    *set = c->tp_hist ^ 1;
-    *filtered_buf = -1;
-    if (filter) {
-        int fb = 0;
-        rc = denoise_levels(c, dn, s, rgba, &fb, T.p_col);
-        if (rc) return rc;
-        *filtered_buf = fb;
-    }
-    return RT_OK;
+    out.color = out.length = &P.col;
+    return filter ? denoise_levels(c, dn, s, rgba, out, T.p_col) : RT_OK;
 }
 
-// dn_rgba for a call that wants the tone-mapped image on the host
-int ensure_rgba(rt_context* c, uint8_t* rgba_out, size_t npix) {
-    if (!rgba_out) return RT_OK;
-    if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
-    return ensure_buf(c, c->dn_rgba, npix * 4, "host RGBA for %zu pixels", npix);
+// A host entry point: run(stream, rgba, out) is the pass, on the context's
+// stream, with dn_rgba for its RGBA when the caller wants the image; then the
+// host copies of what it left in `out`
+template <class Run>
+int host_call(rt_context* c, uint8_t* rgba_out, float* color_out, float* length_out, const Run& run) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    const size_t npix = (size_t)c->height * c->width;
+    if (rgba_out) {
+        if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
+        if (const int rc = ensure_buf(c, c->dn_rgba, npix * 4, "host RGBA for %zu pixels", npix)) return rc;
+    }
+    Result out;
+    if (const int rc = run(c->stream, rgba_out ? c->dn_rgba.as<unsigned>() : nullptr, out)) return rc;
+    return read_back(c, npix, rgba_out, out.color, color_out, out.length, length_out);
+}
+
+// A device entry point (`name`): RT_OK and the stream of the call, or the failure
+int device_call(rt_context* c, const char* name, void* rgba_device, void* stream, hipStream_t* s) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "%s: CPU context", name);
+    if (rgba_device && ((uintptr_t)rgba_device & 3u))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
+    *s = stream ? (hipStream_t)stream : c->stream;
+    return RT_OK;
 }
 
 }  // namespace
@@ -395,22 +405,16 @@ rt_denoise_params rt_denoise_params_default(void) {
 }
 
 int rt_denoise(rt_context* c, const rt_denoise_params* dp, uint8_t* rgba_out, float* color_out) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const size_t npix = (size_t)c->height * c->width;
-    int fb = 0;
-    int rc = ensure_rgba(c, rgba_out, npix);
-    if (!rc) rc = denoise_levels(c, dp, c->stream, rgba_out ? c->dn_rgba.as<unsigned>() : nullptr, &fb);
-    if (rc) return rc;
-    return read_back(c, npix, rgba_out, &c->dn_col[fb], color_out, nullptr, nullptr);
+    return host_call(c, rgba_out, color_out, nullptr, [&](hipStream_t s, unsigned* rgba, Result& out) {
+        return denoise_levels(c, dp, s, rgba, out);
+    });
 }
 
 int rt_denoise_device(rt_context* c, const rt_denoise_params* dp, void* rgba_device, void* stream) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_denoise_device: CPU context");
-    if (rgba_device && ((uintptr_t)rgba_device & 3u))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
-    int fb = 0;
-    return denoise_levels(c, dp, stream ? (hipStream_t)stream : c->stream, (unsigned*)rgba_device, &fb);
+    hipStream_t s;
+    Result out;
+    const int rc = device_call(c, "rt_denoise_device", rgba_device, stream, &s);
+    return rc ? rc : denoise_levels(c, dp, s, (unsigned*)rgba_device, out);
 }
 
 float rt_last_denoise_ms(rt_context* c) { return c ? c->denoise.elapsed_ms() : -1.0f; }
@@ -432,22 +436,16 @@ rt_denoise_var_params rt_denoise_var_params_default(void) {
 
 int rt_denoise_var(rt_context* c, const rt_denoise_var_params* dp, uint8_t* rgba_out, float* color_out,
                    float* var_out) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const size_t npix = (size_t)c->height * c->width;
-    int fb = 0;
-    int rc = ensure_rgba(c, rgba_out, npix);
-    if (!rc) rc = denoise_var_passes(c, dp, c->stream, rgba_out ? c->dn_rgba.as<unsigned>() : nullptr, &fb);
-    if (rc) return rc;
-    return read_back(c, npix, rgba_out, &c->dn_col[fb], color_out, &c->dn_col[fb], var_out);
+    return host_call(c, rgba_out, color_out, var_out, [&](hipStream_t s, unsigned* rgba, Result& out) {
+        return denoise_var_passes(c, dp, s, rgba, out);
+    });
 }
 
 int rt_denoise_var_device(rt_context* c, const rt_denoise_var_params* dp, void* rgba_device, void* stream) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_denoise_var_device: CPU context");
-    if (rgba_device && ((uintptr_t)rgba_device & 3u))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
-    int fb = 0;
-    return denoise_var_passes(c, dp, stream ? (hipStream_t)stream : c->stream, (unsigned*)rgba_device, &fb);
+    hipStream_t s;
+    Result out;
+    const int rc = device_call(c, "rt_denoise_var_device", rgba_device, stream, &s);
+    return rc ? rc : denoise_var_passes(c, dp, s, (unsigned*)rgba_device, out);
 }
 
 float rt_last_denoise_var_ms(rt_context* c) { return c ? c->denoise_var.elapsed_ms() : -1.0f; }
@@ -466,24 +464,17 @@ rt_temporal_params rt_temporal_params_default(void) {
 
 int rt_temporal(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn, uint8_t* rgba_out,
                 float* color_out, float* length_out) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const size_t npix = (size_t)c->height * c->width;
-    int set = 0, fb = -1;
-    int rc = ensure_rgba(c, rgba_out, npix);
-    if (!rc) rc = temporal_pass(c, tp, dn, c->stream, rgba_out ? c->dn_rgba.as<unsigned>() : nullptr, &set, &fb);
-    if (rc) return rc;
-    const Buf& pending = c->tp[set].col;  // {colour, history length}
-    return read_back(c, npix, rgba_out, fb >= 0 ? &c->dn_col[fb] : &pending, color_out, &pending, length_out);
+    return host_call(c, rgba_out, color_out, length_out, [&](hipStream_t s, unsigned* rgba, Result& out) {
+        return temporal_pass(c, tp, dn, s, rgba, out);
+    });
 }
 
 int rt_temporal_device(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn, void* rgba_device,
                        void* stream) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_temporal_device: CPU context");
-    if (rgba_device && ((uintptr_t)rgba_device & 3u))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
-    int set = 0, fb = -1;
-    return temporal_pass(c, tp, dn, stream ? (hipStream_t)stream : c->stream, (unsigned*)rgba_device, &set, &fb);
+    hipStream_t s;
+    Result out;
+    const int rc = device_call(c, "rt_temporal_device", rgba_device, stream, &s);
+    return rc ? rc : temporal_pass(c, tp, dn, s, (unsigned*)rgba_device, out);
 }
 
 int rt_temporal_reset(rt_context* c) {

@@ -24,11 +24,9 @@
 // Stored: pending colour {out, len_out}, a copy of the two guide words, and
 // (optionally) tone_map(out, 1).
 #pragma once
-#include "rt_path.h"
+#include "rt_atrous.h"
 
 namespace {
-
-RT_HD bool tp_finite(float v) { return (rt_f2i(v) & 0x7f800000) != 0x7f800000; }
 
 struct TpOut {
     f3 c;
@@ -37,13 +35,12 @@ struct TpOut {
 
 // The reprojected colour of pixel p = y * width + x whose guide words are a, b
 RT_HD TpOut tp_pixel(const rt_tp_args& T, int x, int y, long p, float4 a, float4 b) {
-    const long npix = (long)T.width * T.height;
     TpOut o;
-    o.c = mk(T.inv * T.accum[p], T.inv * T.accum[npix + p], T.inv * T.accum[2 * npix + p]);
+    o.c = at_c0(T.accum, (long)T.width * T.height, T.inv, p);
     o.len = T.n;
     const int prim = rt_f2i(a.w);
     if (!T.has_history || prim < 0) return o;
-    if (!(tp_finite(o.c.x) && tp_finite(o.c.y) && tp_finite(o.c.z))) return o;
+    if (!(at_finite(o.c.x) && at_finite(o.c.y) && at_finite(o.c.z))) return o;
     const f3 np = mk(a.x, a.y, a.z), Pp = mk(b.x, b.y, b.z);
     const f3 w = sub(Pp, mk(T.h_cam[0], T.h_cam[1], T.h_cam[2]));
     const float vx = T.h_rot[0] * w.x + T.h_rot[3] * w.y + T.h_rot[6] * w.z;
@@ -53,7 +50,7 @@ RT_HD TpOut tp_pixel(const rt_tp_args& T, int x, int y, long p, float4 a, float4
     const float k = rt_div(T.h_screen_z, vz);
     const float fx = vx * k + (float)(T.width / 2);
     const float fy = vy * k + (float)(T.height / 2);
-    if (!(tp_finite(fx) && tp_finite(fy))) return o;
+    if (!(at_finite(fx) && at_finite(fy))) return o;
     if (!(fx >= -1.0f && fx < (float)T.width && fy >= -1.0f && fy < (float)T.height)) return o;
     const float x0f = floorf(fx), y0f = floorf(fy);
     const float ax = fx - x0f, ay = fy - y0f;
@@ -79,7 +76,7 @@ RT_HD TpOut tp_pixel(const rt_tp_args& T, int x, int y, long p, float4 a, float4
             const float4 bq = T.h_gb[q];
             if (!(fabsf(dot(np, sub(mk(bq.x, bq.y, bq.z), Pp))) <= tol)) continue;
             const float4 hq = T.h_col[q];
-            if (!(tp_finite(hq.x) && tp_finite(hq.y) && tp_finite(hq.z) && hq.w > 0.0f)) continue;
+            if (!(at_finite(hq.x) && at_finite(hq.y) && at_finite(hq.z) && hq.w > 0.0f)) continue;
             sw = sw + bw;
             sc.x = sc.x + bw * hq.x;
             sc.y = sc.y + bw * hq.y;

@@ -336,6 +336,45 @@ def test_moments_survive_the_filter(bwrt_lib):
     assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])
 
 
+# rt_denoise, rt_denoise_var, rt_temporal with the default filter and rt_denoise
+# again: every pass that shares the guides and the two colour buffers
+PASS_CALLS = (
+    lambda r, w, h: r.denoise(w, h, want_color=True),
+    lambda r, w, h: r.denoise_var(w, h, want_color=True, want_var=True),
+    lambda r, w, h: r.temporal(w, h, denoise={}, want_color=True, want_length=True),
+    lambda r, w, h: r.denoise(w, h, want_color=True),
+)
+
+
+def passes(make, calls, w=67, h=45):
+    """The PASS_CALLS `calls`, in that order, on one fresh context (`make`)
+    that holds scene 07 under the sky after 8 tracked one-frame calls."""
+    with make() as r:
+        r.set_scene(scenes.scene_07())
+        r.set_background(*SKY)
+        r.init_rand(w, h)
+        accumulate(r, w, h)
+        assert r.moments_batches == 8
+        return [PASS_CALLS[i](r, w, h) for i in calls]
+
+
+def same_results(a, b):
+    return len(a) == len(b) and all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
+
+
+def test_passes_carry_nothing_over(bwrt_lib):
+    """The four passes in a row on one accumulated frame: each gives what it
+    gives alone on a fresh context, and rt_denoise gives the same bits before
+    and after the others used its colour buffers and guides."""
+    def make():
+        return Renderer.cpu(0, lib=bwrt_lib)
+    row = passes(make, range(4))
+    assert same_results(row[0], row[3])
+    for i in range(3):
+        assert same_results(passes(make, [i])[0], row[i]), i
+    assert not np.array_equal(row[0][1], row[1][1])  # (two filters; the first temporal call has no history)
+
+
 @pytest.mark.parametrize("w,h", [(1, 1), (5, 3), (333, 187)])
 def test_shapes(cpu, w, h):
     scene = scenes.scene_07()

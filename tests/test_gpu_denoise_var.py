@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from bwrt import Renderer, scenes
-from test_denoise_var import SIGMA, SKY, accumulate, neutrality_sequence, same_sequences, special_frame
+from test_denoise_var import (SIGMA, SKY, accumulate, neutrality_sequence, passes, same_results, same_sequences,
+                              special_frame)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +56,25 @@ def test_filter_equals_cpu_every_level_count(monkeypatch, bwrt_lib, cpu07, varia
             assert same(g, c), (variant, key)
     assert np.array_equal(want["tracked", 0][0], img)  # iterations == 0: the render's RGBA
     assert not same(want["tracked", 5][1], want["spatial", 5][1])
+
+
+@pytest.fixture(scope="module")
+def cpu_row(bwrt_lib):
+    """test_denoise_var.passes: the four passes in a row on the CPU backend."""
+    return passes(lambda: Renderer.cpu(0, lib=bwrt_lib), range(4))
+
+
+@pytest.mark.parametrize("variant", ["direct", "tiled"])
+def test_passes_carry_nothing_over(monkeypatch, bwrt_lib, cpu_row, variant):
+    """rt_denoise, rt_denoise_var, rt_temporal with the default filter and
+    rt_denoise again on one context: the CPU backend's bits (each of which
+    equals the call made alone, tests/test_denoise_var.py), so the shared colour
+    buffers and guides carry nothing from one pass to the next."""
+    monkeypatch.setenv("BWRT_DENOISE_KERNEL", variant)
+    row = passes(lambda: Renderer(0, lib=bwrt_lib), range(4))
+    for i, (g, c) in enumerate(zip(row, cpu_row)):
+        assert same_results(g, c), (variant, i)
+    assert same_results(row[0], row[3])
 
 
 @pytest.mark.parametrize("variant", [None, "direct", "tiled"])

@@ -65,6 +65,19 @@ def test_equals_cpu(gpu, cpu, name, w, h, move):
     assert gpu.last_temporal_ms() > 0
 
 
+@pytest.mark.parametrize("variant", ["direct", "tiled"])
+def test_filtered_walk_equals_cpu_forced_variant(monkeypatch, bwrt_lib, cpu, variant):
+    """The filter behind the reprojection with a forced level variant, six
+    levels (step 32 included): the one path on which the plain filter's level-0
+    source carries a non-zero .w, the history length, through the tile."""
+    monkeypatch.setenv("BWRT_DENOISE_KERNEL", variant)  # read at rt_create (BWRT_TUNING=1)
+    with Renderer(0, lib=bwrt_lib) as r:
+        g = walk(r, "07", 67, 45, "yaw", denoise_last={"iterations": 6})
+    c = walk(cpu, "07", 67, 45, "yaw", denoise_last={"iterations": 6})
+    assert_same_views(g, c)
+    assert (c[3]["length"] > 0).all() and not same(c[3]["color"], c[2]["color"])
+
+
 def test_equals_cpu_zero_iterations_and_parameters(gpu, cpu):
     out = []
     for r in (gpu, cpu):

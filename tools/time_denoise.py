@@ -14,35 +14,23 @@ for scale.  The summary goes to stdout and to --out.
 import argparse
 import os
 import statistics
-import sys
 
 os.environ["BWRT_TUNING"] = "1"
-sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bwidman-raytracer_amd")]
-import torch  # noqa: E402,F401  (one HIP runtime with libbwrt)
+import timing_common as tc  # noqa: E402
+from timing_common import BOUNCES, FRAMES, H, W  # noqa: E402
 
-from bwrt import Renderer, scenes  # noqa: E402
-
-W, H, FRAMES, BOUNCES, LEVELS = 1920, 1080, 8, 4, 5
-FLOOR_MS = (48 + 16) * W * H / 6.3e12 * 1e3
+LEVELS = 5
+FLOOR_MS = tc.floor_ms(48 + 16)
 
 
 def make(variant):
-    if variant:
-        os.environ["BWRT_DENOISE_KERNEL"] = variant
-    else:
-        os.environ.pop("BWRT_DENOISE_KERNEL", None)
-    r = Renderer(0)
-    r.set_scene(scenes.scene_07())
+    r = tc.make(variant)
     r.render(W, H, FRAMES, BOUNCES, first_frame=1)
     return r
 
 
 def timed(r, buf, levels, reps):
-    ts = []
-    for _ in range(reps):
-        r.denoise_device(buf.data_ptr(), None, iterations=levels)
-        ts.append(r.last_denoise_ms())
-    return statistics.median(ts)
+    return tc.timed(lambda: r.denoise_device(buf.data_ptr(), None, iterations=levels), r.last_denoise_ms, reps)
 
 
 def main():
@@ -54,8 +42,7 @@ def main():
     ap.add_argument("--levels", type=int, default=LEVELS, help="level counts timed (6 adds step 32)")
     args = ap.parse_args()
     LEVELS = args.levels
-    buf = torch.zeros(H * W, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
+    buf = tc.output_buffer()
     ctx = {v: make(v) for v in ("direct", "tiled", None)}
     lines = [f"denoise A/B: scene 07 {W}x{H}, {FRAMES} frames, {BOUNCES} bounces; {args.reps} calls per point, "
              f"median ms; streaming floor per level {FLOOR_MS:.4f} ms"]
@@ -77,23 +64,13 @@ def main():
         d, t = statistics.median(level_ms["direct"][i]), statistics.median(level_ms["tiled"][i])
         lines.append(f"{i:5d} {1 << i:4d}  {d:.4f}  {t:.4f}  ({d / FLOOR_MS:.1f}x / {t / FLOOR_MS:.1f}x)  "
                      f"{'direct' if d <= t else 'tiled'}")
-    r = ctx[None]
-    ks = []
-    for _ in range(12):
-        r.render(W, H, FRAMES, BOUNCES, first_frame=1)
-        ks.append(r.last_kernel_ms())
-    step = statistics.median(ks[2:])
+    step = tc.render_step_ms(ctx[None])
     for v in ("direct", "tiled", None):
         m = statistics.median(total[v])
         lines.append(f"{v or 'policy':6s}: {LEVELS} levels {m:.4f} ms = {m / step:.3f} of the render step ({step:.4f} ms)")
     for r in ctx.values():
         r.close()
-    text = "\n".join(lines) + "\n"
-    sys.stdout.write(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    tc.write_out(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -26,18 +26,15 @@ in the same rounds.  The sigma pass alone shows in a kernel trace of this tool
 import argparse
 import os
 import statistics
-import sys
 import time
 
 os.environ["BWRT_TUNING"] = "1"
-sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bwidman-raytracer_amd")]
-import torch  # noqa: E402,F401  (one HIP runtime with libbwrt)
+import timing_common as tc  # noqa: E402
+from timing_common import BOUNCES, H, W, timed  # noqa: E402
 
-from bwrt import Renderer, scenes  # noqa: E402
-
-W, H, CALLS, BOUNCES = 1920, 1080, 8, 4
-LEVEL_FLOOR_MS = (48 + 16) * W * H / 6.3e12 * 1e3
-UPDATE_FLOOR_MS = 52 * W * H / 6.3e12 * 1e3
+CALLS = 8
+LEVEL_FLOOR_MS = tc.floor_ms(48 + 16)
+UPDATE_FLOOR_MS = tc.floor_ms(52)
 
 
 def accumulate(r, buf, track):
@@ -53,23 +50,10 @@ def accumulate(r, buf, track):
 
 
 def make(variant, buf):
-    if variant:
-        os.environ["BWRT_DENOISE_KERNEL"] = variant
-    else:
-        os.environ.pop("BWRT_DENOISE_KERNEL", None)
-    r = Renderer(0)
-    r.set_scene(scenes.scene_07())
+    r = tc.make(variant)
     accumulate(r, buf, True)
     assert r.moments_batches == CALLS
     return r
-
-
-def timed(call, ms, reps):
-    ts = []
-    for _ in range(reps):
-        call()
-        ts.append(ms())
-    return statistics.median(ts)
 
 
 def main():
@@ -80,13 +64,11 @@ def main():
     ap.add_argument("--levels", type=int, default=5, help="level counts timed (6 adds step 32)")
     args = ap.parse_args()
     L = args.levels
-    buf = torch.zeros(H * W, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
+    buf = tc.output_buffer()
     lines = [f"scene 07 {W}x{H}, {CALLS} one-frame calls, {BOUNCES} bounces; {args.reps} per point, median ms"]
 
     # ---- the tracking -----------------------------------------------------------
-    r = Renderer(0)
-    r.set_scene(scenes.scene_07())
+    r = tc.make()
     for track in (True, False):
         for _ in range(5):
             accumulate(r, buf, track)
@@ -159,12 +141,7 @@ def main():
                      f"policy {med(total[None, m]):.4f} ms")
     for r in ctx.values():
         r.close()
-    text = "\n".join(lines) + "\n"
-    sys.stdout.write(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    tc.write_out(lines, args.out)
 
 
 if __name__ == "__main__":

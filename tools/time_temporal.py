@@ -24,24 +24,20 @@ writes 16 B pending colour + 32 B guide copy + 4 B RGBA; at 6.3 TB/s.  The
 summary goes to stdout and to --out.
 """
 import argparse
-import os
 import statistics
-import sys
 
-sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bwidman-raytracer_amd")]
-import torch  # noqa: E402,F401  (one HIP runtime with libbwrt)
+import timing_common as tc
+from timing_common import BOUNCES, FRAMES, H, W
+from timing_common import timed as med
 
-from bwrt import Renderer, scenes  # noqa: E402
-
-W, H, FRAMES, BOUNCES, LEVELS = 1920, 1080, 8, 4, 5
+LEVELS = 5
 READ_B, WRITE_B = 32 + 12 + 48, 16 + 32 + 4
-FLOOR_MS = (READ_B + WRITE_B) * W * H / 6.3e12 * 1e3
-FLOOR_NOHIST_MS = (32 + 12 + WRITE_B) * W * H / 6.3e12 * 1e3
+FLOOR_MS = tc.floor_ms(READ_B + WRITE_B)
+FLOOR_NOHIST_MS = tc.floor_ms(32 + 12 + WRITE_B)
 
 
 def make(with_history):
-    r = Renderer(0)
-    r.set_scene(scenes.scene_07())
+    r = tc.make()
     r.render(W, H, FRAMES, BOUNCES, first_frame=1)
     r.temporal(W, H)
     assert r.controls(["LEFT"], 0.02) & 1
@@ -51,22 +47,13 @@ def make(with_history):
     return r
 
 
-def med(fn, read, reps):
-    ts = []
-    for _ in range(reps):
-        fn()
-        ts.append(read())
-    return statistics.median(ts)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=50)
     args = ap.parse_args()
-    buf = torch.zeros(H * W, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
+    buf = tc.output_buffer()
     rh, rn = make(True), make(False)
     _, ln = rh.temporal(W, H, want_length=True)
     share = float((ln > FRAMES).mean())
@@ -91,11 +78,7 @@ def main():
             res[k].append(med(fn, read, args.reps))
         lines.append(f"round {rnd}: " + "  ".join(f"{k} {v[-1]:.4f}" for k, v in res.items()))
     m = {k: statistics.median(v) for k, v in res.items()}
-    ks = []
-    for _ in range(12):
-        rn.render(W, H, FRAMES, BOUNCES, first_frame=1)
-        ks.append(rn.last_kernel_ms())
-    step = statistics.median(ks[2:])
+    step = tc.render_step_ms(rn)
     levels = [m[f"denoise-{k + 1}"] - m[f"denoise-{k}"] for k in range(LEVELS)]
     lines += [
         f"reprojection pass, history:    {m['history']:.4f} ms = {m['history'] / FLOOR_MS:.2f} x floor = "
@@ -108,12 +91,7 @@ def main():
     ]
     rh.close()
     rn.close()
-    text = "\n".join(lines) + "\n"
-    sys.stdout.write(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    tc.write_out(lines, args.out)
 
 
 if __name__ == "__main__":
