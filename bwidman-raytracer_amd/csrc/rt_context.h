@@ -6,6 +6,10 @@
 //   rt_render.cpp   prepare, fill_view, launch, rt_render*, multi-GPU, de-interleave
 //   rt_post.cpp     first-hit features, denoiser, temporal reprojection, moment readout
 //   rt_scene.cpp    the scene compiler (rt_scene.h; no HIP, no context)
+// The render kernels: rt_launch.h declares the launchers of their units
+// (rt_kernels{,_bvh,_fast,_bvh_fast,_shared}.hip); one header per kernel
+// (rt_kernel_simple.h, rt_kernel_sorted.h, rt_kernel_pair.h, rt_kernel_refill.h)
+// over rt_pixel.h and rt_hit.h, the launch policy in rt_launch_brute.h.
 // The post-render passes' kernels and arithmetic: rt_atrous.h (what the filters
 // and the reprojection share, host and device), rt_atrous_tile.h (the pixel and
 // the LDS-tiled kernel with their launchers, device only), then one header and
@@ -24,29 +28,12 @@
 #include <xmmintrin.h>
 
 #include "../../include/rt_abi.h"
+#include "rt_launch.h"
 #include "rt_layout.h"
 #include "rt_scene.h"
 #include "rt_sky.h"
 
-// ---- kernel launchers ---------------------------------------------------------
-size_t rt_render_rec_floats(const rt_kparams& K);
-bool rt_render_wants_global_records(const rt_kparams& K, int num_cus);
-hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, bool simple, int block_req,
-                            hipStream_t stream, int pair_req);
-bool rt_render_takes_sorted(const rt_kparams& K, int num_cus, bool simple, int block_req, int pair_req);
-hipError_t rt_launch_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride,
-                               hipStream_t stream);
-// the reference-fast instantiations (rt_kernels_fast.hip, rt_kernels_bvh_fast.hip)
-namespace rt_fast {
-bool rt_render_wants_global_records(const rt_kparams& K, int num_cus);
-hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, bool simple, int block_req,
-                            hipStream_t stream, int pair_req);
-bool rt_render_takes_sorted(const rt_kparams& K, int num_cus, bool simple, int block_req, int pair_req);
-}  // namespace rt_fast
-extern thread_local long rt_order_groups_last;
-extern thread_local char rt_launched_kernel[96];
-hipError_t rt_launch_deinterleave(const unsigned* gathered, unsigned* image, int width, int height,
-                                  int shards, int rows_per_shard, int max_blocks, hipStream_t stream);
+// ---- kernel launchers (the render units': rt_launch.h) ------------------------
 // scalar C++ CPU fallback (rt_cpu.cpp)
 int rt_cpu_render(const rt_kparams& K, int threads);
 void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride);
@@ -56,10 +43,7 @@ void rt_cpu_denoise_level(const rt_dn_level& L, int threads);
 void rt_cpu_temporal(const rt_tp_args& T, int threads);
 void rt_cpu_moments(const rt_mom_args& A, int threads);
 void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads);
-// first-hit feature kernel (rt_kernels.hip; the BVH walk in rt_kernels_bvh.hip) and the
 // a-trous filter (rt_denoise.hip)
-hipError_t rt_launch_aov(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream);
-hipError_t rt_launch_aov_bvh(const rt_kparams& K, float4* ga, float4* gb, float4* alb, hipStream_t stream);
 hipError_t rt_launch_denoise_level(const rt_dn_level& L, bool tiled, hipStream_t stream);
 // temporal reprojection (rt_temporal.hip)
 hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream);

@@ -278,7 +278,7 @@ void parallel_pixels(int width, int height, int threads, const Fn& fn) {
 
 }  // namespace
 
-// The feature buffers of the shard in K (rt_kernels.hip rt_aov_kernel): ga, gb
+// The feature buffers of the shard in K (rt_hit.h rt_aov_kernel): ga, gb
 // and alb as the kernel packs them (alb may be null)
 void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb) {
     parallel_pixels(K.width, K.rows, threads, [&](int x, int j, long p) {

@@ -1,5 +1,4 @@
-// rt_kernels_bvh.hip — the BVH instantiations of the render kernels
-// (rt_launch_render_bvh), compiled at -O3 in their own translation unit;
-// everything else in rt_kernels.hip is compiled once, at -O1 (see Makefile).
-#define RT_TU_BVH
-#include "rt_kernels.hip"
+// rt_kernels_bvh.hip — the exact BVH render kernels (ray refill, and the simple
+// kernel's BVH instantiation) with their launchers, and the BVH feature-buffer
+// kernel, compiled at -O3 in their own translation unit (see Makefile).
+#include "rt_kernel_refill.h"

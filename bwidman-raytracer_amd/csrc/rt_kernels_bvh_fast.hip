@@ -2,5 +2,4 @@
 // (rt_fast::rt_launch_render_bvh_*): rt_kernels_bvh.hip's flags plus
 // -ffp-contract=fast (see rt_kernels_fast.hip).
 #define RT_FAST
-#define RT_TU_BVH
-#include "rt_kernels.hip"
+#include "rt_kernel_refill.h"

@@ -5,4 +5,4 @@
 // --use_fast_math build (rt_path.h, rt_sqrt.h).  Never -ffast-math: the isnan
 // guard of specular_weight must survive.
 #define RT_FAST
-#include "rt_kernels.hip"
+#include "rt_launch_brute.h"

@@ -1,5 +1,5 @@
 // rt_layout.h — device-side data layout shared by the host scene compiler
-// (rt_scene.cpp) and the HIP kernels (rt_kernels.hip).
+// (rt_scene.cpp) and the HIP kernels (rt_kernel_*.h).
 //
 // The scene is "compiled" once on upload: every quantity the reference
 // recomputes per ray but that depends only on the primitive (plane normal

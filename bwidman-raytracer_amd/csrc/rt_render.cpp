@@ -211,9 +211,11 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     K.refill = c->refill > 0 ? c->refill : small ? RT_REFILL_SMALL : RT_REFILL;
     // deep paths: the sorted kernel's record stack in global memory (launch policy)
     K.rec = nullptr;
+    // the render units of the precision mode
     const bool fast = c->precision == RT_PRECISION_REFERENCE_FAST;
-    if (!c->simple && (c->grec == 1 || (c->grec < 0 && (fast ? rt_fast::rt_render_wants_global_records(K, c->num_cus)
-                                                             : rt_render_wants_global_records(K, c->num_cus))))) {
+    const auto wants_global_records = fast ? rt_fast::rt_render_wants_global_records : rt_render_wants_global_records;
+    const auto launch_render = fast ? rt_fast::rt_launch_render : rt_launch_render;
+    if (!c->simple && (c->grec == 1 || (c->grec < 0 && wants_global_records(K, c->num_cus)))) {
         const int rc = ensure_buf(c, c->rec, rt_render_rec_floats(K) * sizeof(float));
         if (rc) return rc;
         K.rec = c->rec.as<float>();
@@ -263,8 +265,7 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     // unchanged view costs the key compare; a view's first launch goes without
     // a table (rt_context.h sky_eager), its second builds and uploads one
     // ahead of the kernel on its stream
-    bool sky = c->sky_on && (fast ? rt_fast::rt_render_takes_sorted(K, c->num_cus, c->simple, c->block, c->spread)
-                                  : rt_render_takes_sorted(K, c->num_cus, c->simple, c->block, c->spread));
+    bool sky = c->sky_on && rt_render_takes_sorted(K, c->num_cus, c->simple, c->block, c->spread);
     if (sky && !c->sky_eager) {
         const rt_context::SkyKey k = sky_key_of(c, K);
         if (!(k == c->sky_key) && !(k == c->sky_seen)) {
@@ -289,8 +290,7 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     // the start marker only with kernel timing on; the one end event serves
     // both the ordering of later calls and the timing (Pass::end)
     HIP_TRY(c, c->render.begin(s, c->ktiming));
-    hipError_t e = fast ? rt_fast::rt_launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread)
-                        : rt_launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread);
+    hipError_t e = launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread);
     if (e == hipSuccess && rt_order_groups_last > 0) c->order_n = rt_order_groups_last;
     c->kernel_name = rt_launched_kernel;
     c->launches++;

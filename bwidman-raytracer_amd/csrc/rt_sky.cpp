@@ -150,7 +150,7 @@ bool quad_sphere(const rt_vec3* verts, double scale, double* out) {
     return true;
 }
 
-// the tile grid of rt_kernels.hip launch_items / item_to_pixel
+// the tile grid of rt_pixel.h launch_items / item_to_pixel
 struct TileGrid {
     int tw = 0, th = 0;
     long tiles_x = 0, tiles_y = 0;  // tiles that hold pixels

@@ -1,7 +1,7 @@
 // rt_sky.h — the host-side sky table of a view: one bit per wave tile of the
 // launch order, set when every camera ray of the tile provably misses every
 // primitive (rt_sky.cpp has the argument).  The sorted kernel renders tile
-// groups whose bits are all set without the path machinery (rt_kernels.hip).
+// groups whose bits are all set without the path machinery (rt_kernel_sorted.h).
 //
 // Pure host arithmetic in double precision: no HIP, no context, no environment.
 #pragma once
@@ -30,7 +30,7 @@ struct rt_sky_prims {
 // `out` from the scene and its compiled records (r.data still held)
 void rt_sky_collect(const rt_scene& s, const rt_compiled_scene& r, rt_sky_prims& out);
 
-// Wave tiles of the launch order of K (rt_kernels.hip launch_items / 64); 0
+// Wave tiles of the launch order of K (rt_pixel.h launch_items / 64); 0
 // for the linear order (tile_w <= 0)
 long rt_sky_tiles(const rt_kparams& K);
 // Words of a table the sorted kernel may read for K: a group's bits start at

@@ -24,6 +24,10 @@ FLAGS = ["-O1", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fn
     ("rt_kernels.hip", ["-DRT_WAVES_PER_EU=6", "-DRT_STAMPS", "-DRT_BRANCH_STATS", "-DRT_GTIMES", "-DRT_PHASE_TWICE=4"]),
     ("rt_kernels.hip", ["-DRT_WAVES_PER_EU=6", "-DRT_PHASE_TWICE=3"]),
     ("rt_kernels_bvh.hip", ["-DRT_WAVES_PER_EU=4", "-DRT_STAMPS", "-DRT_GTIMES", "-DRT_BVH_CHECK"]),
+    # the reference-fast roots (their Makefile flag: FMA contraction in the device pass)
+    ("rt_kernels_fast.hip", ["-ffp-contract=fast", "-DRT_WAVES_PER_EU=6", "-DRT_STAMPS", "-DRT_BRANCH_STATS", "-DRT_GTIMES",
+                             "-DRT_PHASE_TWICE=4"]),
+    ("rt_kernels_bvh_fast.hip", ["-ffp-contract=fast", "-DRT_WAVES_PER_EU=4", "-DRT_STAMPS", "-DRT_GTIMES", "-DRT_BVH_CHECK"]),
 ])
 def test_diagnostic_build_compiles(tu, defines):
     r = subprocess.run([HIPCC] + FLAGS + defines + [os.path.join(CSRC, tu)], capture_output=True, text=True,

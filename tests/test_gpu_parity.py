@@ -1020,3 +1020,85 @@ def test_launch_order_feedback(bwrt_lib, oracle, monkeypatch, scene_name, w, h, 
         same_state(r, st)
     finally:
         r.close()
+
+
+def _small_stress():
+    return scenes.stress_scene(n_triangles=400, n_spheres=8)  # 408 primitives: over 16 KB of hit table
+
+
+# Launch-policy cases: (knobs read at rt_create, scene options read at
+# rt_set_scene, scene, width, height, max_bounces).  24 x 16 pixels unless the
+# branch needs a grid of several resident generations (launch-order feedback).
+_NO_BVH = {"BWRT_BVH_MIN": "100000000"}
+_BVH = {"BWRT_BVH_MIN": "1"}
+POLICY_CASES = {
+    "default": ({}, {}, scenes.scene_07, 24, 16, 4),
+    "spread0": ({"BWRT_SPREAD": 0}, {}, scenes.scene_07, 24, 16, 4),
+    "spread1": ({"BWRT_SPREAD": 1}, {}, scenes.scene_07, 24, 16, 4),
+    **{f"block{b}": ({"BWRT_BLOCK": b}, {}, scenes.scene_07, 24, 16, 4) for b in (64, 128, 256)},
+    **{f"block{b}_grec": ({"BWRT_BLOCK": b, "BWRT_GREC": 1}, {}, scenes.scene_07, 24, 16, 4) for b in (64, 128, 256)},
+    "grec0": ({"BWRT_GREC": 0, "BWRT_SPREAD": 0}, {}, scenes.scene_07, 24, 16, 4),
+    "simple": ({"BWRT_KERNEL": "simple"}, {}, scenes.scene_07, 24, 16, 4),
+    # 3 * (mb + 1) * 256 * 4 > 49152 from mb = 16 on: 64-lane groups
+    "deep15": ({}, {}, scenes.scene_07, 24, 16, 15),
+    "deep16": ({}, {}, scenes.scene_07, 24, 16, 16),
+    "deep16_grec0": ({"BWRT_GREC": 0}, {}, scenes.scene_07, 24, 16, 16),
+    "deep16_simple": ({"BWRT_KERNEL": "simple"}, {}, scenes.scene_07, 24, 16, 16),
+    # more than 341 primitives (16 KB / 48 B): the hit table stays in global memory
+    "hit_global": ({}, _NO_BVH, _small_stress, 24, 16, 4),
+    "hit_global_spread1": ({"BWRT_SPREAD": 1}, _NO_BVH, _small_stress, 24, 16, 4),
+    "hit_global_grec": ({"BWRT_GREC": 1}, _NO_BVH, _small_stress, 24, 16, 4),
+    "hit_global_block64": ({"BWRT_BLOCK": 64}, _NO_BVH, _small_stress, 24, 16, 4),
+    "hit_global_simple": ({"BWRT_KERNEL": "simple"}, _NO_BVH, _small_stress, 24, 16, 4),
+    "hit_global_deep16": ({}, _NO_BVH, _small_stress, 24, 16, 16),
+    "bvh_n16_0": ({}, {**_BVH, "BWRT_BVH_N16": "0"}, scenes.scene_07, 24, 16, 4),
+    "bvh_n16_1": ({}, {**_BVH, "BWRT_BVH_N16": "1"}, scenes.scene_07, 24, 16, 4),
+    "bvh_simple": ({"BWRT_KERNEL": "simple"}, _BVH, scenes.scene_07, 24, 16, 4),
+    "bvh_simple_deep16": ({"BWRT_KERNEL": "simple"}, _BVH, scenes.scene_07, 24, 16, 16),
+    # grids past RT_ORDER_MIN_GEN generations (test_launch_order_feedback's frame)
+    "order1": ({"BWRT_ORDER": 1}, {}, scenes.scene_07, 1920, 1080, 4),
+    "order0": ({"BWRT_ORDER": 0}, {}, scenes.scene_07, 1920, 1080, 4),
+    "order1_grec0": ({"BWRT_ORDER": 1, "BWRT_GREC": 0}, {}, scenes.scene_07, 1920, 1080, 4),
+    "order1_small": ({"BWRT_ORDER": 1, "BWRT_SPREAD": 0}, {}, scenes.scene_07, 24, 16, 4),
+    "order1_pair": ({"BWRT_ORDER": 1, "BWRT_SPREAD": 1}, {}, scenes.scene_07, 24, 16, 4),
+    "order1_quads": ({"BWRT_ORDER": 1}, {}, scenes.scene_04_box, 1920, 1080, 4),
+    "order1_bvh_n16_0": ({"BWRT_ORDER": 1}, {**_BVH, "BWRT_BVH_N16": "0"}, scenes.scene_07, 1920, 1080, 4),
+    "order1_bvh_n16_1": ({"BWRT_ORDER": 1}, {**_BVH, "BWRT_BVH_N16": "1"}, scenes.scene_07, 1920, 1080, 4),
+    "order1_bvh_small": ({"BWRT_ORDER": 1}, _BVH, scenes.scene_07, 24, 16, 4),
+    # the sky table built at the view's first launch: only the sorted kernel reads it
+    "sky_sorted": ({"BWRT_SKY": 2, "BWRT_SPREAD": 0}, {}, scenes.scene_07, 256, 144, 4),
+    "sky_pair": ({"BWRT_SKY": 2, "BWRT_SPREAD": 1}, {}, scenes.scene_07, 256, 144, 4),
+    "sky_simple": ({"BWRT_SKY": 2, "BWRT_KERNEL": "simple"}, {}, scenes.scene_07, 256, 144, 4),
+}
+
+
+def _policy_kernel(bwrt_lib, monkeypatch, case, mode):
+    """rt_last_kernel_name of one 2-sample render of a POLICY_CASES entry."""
+    create_env, scene_env, scene, w, h, mb = POLICY_CASES[case]
+    for k, v in scene_env.items():
+        monkeypatch.setenv(k, v)
+    r = _fresh_renderer(bwrt_lib, monkeypatch, **create_env)
+    try:
+        r.set_precision(mode)
+        r.set_scene(scene())
+        r.init_rand(w, h)
+        r.render(w, h, 2, mb, first_frame=1)
+        return r.last_kernel_name()
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("mode", ["exact", "fast"])
+@pytest.mark.parametrize("case", list(POLICY_CASES))
+def test_launch_policy_kernel_names(bwrt_lib, monkeypatch, case, mode):
+    """Every branch of the launchers takes the kernel it took before the
+    kernels were split into one header each: rt_last_kernel_name equals the
+    string recorded from the library built at the commit before the split
+    (tests/golden/launch_policy_kernels.json), in both precision modes.  The
+    forced cases reach the branches the default policy does not take at these
+    sizes.  As assert_kernel: not checked for an A/B variant library."""
+    with open(os.path.join(GOLDEN, "launch_policy_kernels.json")) as f:
+        want = json.load(f)[f"{case}-{mode}"]
+    got = _policy_kernel(bwrt_lib, monkeypatch, case, mode)
+    if not os.environ.get("BWRT_LIB"):
+        assert got == want

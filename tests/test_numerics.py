@@ -54,7 +54,7 @@ def _ulp_err(got, want):
     ("orc_atanf", np.arctan, 0.0, 50.0, 4.0),
 ])
 def test_transcendental_accuracy(oracle, fn, ref, lo, hi, maxulp):
-    """The Cody-Waite + minimax sequence (oracle.c, rt_kernels.hip) against
+    """The Cody-Waite + minimax sequence (oracle.c, rt_path.h) against
     float64 libm over the arguments the path uses (phi = 2*pi*e2 in [0, 2pi],
     theta in [0, pi/2], atan of [0, inf))."""
     f = getattr(oracle.lib(), fn)
