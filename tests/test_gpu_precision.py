@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+import sky_cases
 from bwrt import Renderer, scenes
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,8 @@ GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 WITHIN_1LSB_MIN = 0.995
 MEAN_ABS_MAX = 0.25
 
-SCENES = {"07": scenes.scene_07, "04_box": scenes.scene_04_box, "stress": scenes.stress_scene}
+SCENES = {"07": scenes.scene_07, "04_box": scenes.scene_04_box, "stress": scenes.stress_scene,
+          "07_yaw_pitch": lambda: sky_cases.with_camera(scenes.scene_07(), 0.5, 0.3)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -32,12 +34,14 @@ def _scene(name):
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle_state(name, w, h, spp, mb, off, stride):
-    """The exact reference of a case, computed once and shared (read-only)."""
+def _oracle_state(name, w, h, spp, mb, off, stride, split=None, background=(0.0, 0.0, 0.0)):
+    """The exact reference of a case, computed once and shared (read-only);
+    `split`: the frames of each render call, the oracle continuing alongside."""
     import oracle as O
     O.build()
     st = O.OracleState(w, h, off, stride)
-    O.render(_scene(name), st, spp, mb, first_frame=1)
+    for i, n in enumerate(split or (spp,)):
+        O.render(_scene(name), st, n, mb, first_frame=1 if i == 0 else None, background=background)
     return st
 
 
@@ -72,21 +76,42 @@ CASES = [
     ("bvh_refill", "stress", 96, 54, 2, 8, 0, 1, {}, "rt_render_bvh_refill_kernel<"),
     # the shape the mode is quoted on, switched on the way bench.py can: the create-time knob
     ("headline_frame", "07", 1920, 1080, 8, 4, 0, 1, {"BWRT_PRECISION": "fast"}, None),
+    # the sorted kernel with a sky table and (where the policy gives one) a launch order, which a view's
+    # first launch never has: 8 frames as 3 + 5 under a non-black background
+    ("sky_order_second_launch", "07_yaw_pitch", 320, 180, 8, 4, 0, 1,
+     {"BWRT_SPREAD": 0, "BWRT_SKY": 1, "BWRT_ORDER_PERIOD": 2}, "rt_render_sorted_kernel<"),
+    # the box's shared edges (exact ties in EXACT) through the BVH
+    ("bvh_forced_box", "04_box", 320, 180, 4, 5, 0, 1, {}, "rt_render_bvh_refill_kernel<"),
 ]
+# what a case needs beyond its launch knobs: the frames of each render call, the background, the
+# scene-compile options (read at rt_set_scene) and the end of the last launch's kernel name
+EXTRA = {
+    "sky_order_second_launch": {"split": (3, 5), "background": sky_cases.BG, "ends": "+sky"},
+    "bvh_forced_box": {"scene_env": {"BWRT_BVH_MIN": 1}},
+}
 
 
 @pytest.mark.parametrize("cid,name,w,h,spp,mb,off,stride,env,family", CASES, ids=[c[0] for c in CASES])
 def test_fast_within_tolerance(bwrt_lib, monkeypatch, cid, name, w, h, spp, mb, off, stride, env, family):
-    st = _oracle_state(name, w, h, spp, mb, off, stride)
+    extra = EXTRA.get(cid, {})
+    split, background = extra.get("split"), extra.get("background", (0.0, 0.0, 0.0))
+    assert sum(split or (spp,)) == spp
+    st = _oracle_state(name, w, h, spp, mb, off, stride, split, background)
     r = _fresh(bwrt_lib, monkeypatch, env)
     try:
         if "BWRT_PRECISION" not in env:
             assert r.precision == "exact"
             r.set_precision("fast")
         assert r.precision == "fast"
+        for k, v in extra.get("scene_env", {}).items():
+            monkeypatch.setenv(k, str(v))
         r.set_scene(_scene(name))
+        for k in extra.get("scene_env", {}):
+            monkeypatch.delenv(k)
+        r.set_background(*background)
         r.init_rand(w, h, off, stride)
-        img = r.render(w, h, spp, mb, first_frame=1, row_offset=off, row_stride=stride)
+        for i, n in enumerate(split or (spp,)):
+            img = r.render(w, h, n, mb, first_frame=1 if i == 0 else 0, row_offset=off, row_stride=stride)
         kernel = r.last_kernel_name()
         rng, _ = r.get_state(st.rows, st.width)
     finally:
@@ -100,6 +125,7 @@ def test_fast_within_tolerance(bwrt_lib, monkeypatch, cid, name, w, h, spp, mb, 
     if family and not os.environ.get("BWRT_LIB"):
         assert kernel.startswith(family), kernel
         assert ("grec" in kernel) == (env.get("BWRT_GREC") == 1), kernel
+        assert kernel.endswith(extra.get("ends", "")), kernel
     assert (img[..., 3] == 255).all()
     assert within >= WITHIN_1LSB_MIN, (within, mean)
     assert mean <= MEAN_ABS_MAX, (within, mean)
