@@ -96,6 +96,20 @@ class TemporalParams(C.Structure):
     _fields_ = [("max_history", C.c_float), ("normal_cos_min", C.c_float), ("plane_tol", C.c_float)]
 
 
+class AdaptiveParams(C.Structure):
+    """rt_adaptive_params: frames per selected pixel, the selection's tolerance,
+    luminance floor and window radius, and the forced / capped frame counts."""
+    _fields_ = [("samples", C.c_int), ("tolerance", C.c_float), ("lum_floor", C.c_float), ("radius", C.c_int),
+                ("min_frames", C.c_uint), ("max_frames", C.c_uint)]
+
+
+class AdaptiveStats(C.Structure):
+    """rt_adaptive_stats: pixels the last adaptive call rendered, the sum of the
+    per-pixel frame counts after it, and its three stages' durations (ms)."""
+    _fields_ = [("selected", C.c_longlong), ("frames_total", C.c_longlong), ("select_ms", C.c_float),
+                ("render_ms", C.c_float), ("resolve_ms", C.c_float)]
+
+
 RT_OK = 0
 RT_ERR_INVALID_ARGUMENT = -1
 RT_ERR_NO_DEVICE = -2
@@ -103,6 +117,7 @@ RT_ERR_NO_SCENE = -5
 RT_ERR_UNSUPPORTED = -6
 RT_DENOISE_MAX_ITERATIONS = 6
 RT_MAX_BOUNCES = 32
+RT_ADAPTIVE_MAX_RADIUS = 4
 RT_DEFAULT_MAX_BOUNCES = 5
 RT_PRECISION_EXACT = 0
 RT_PRECISION_REFERENCE_FAST = 1
@@ -169,6 +184,11 @@ def _proto(lib):
         "rt_get_moments": (C.c_int, [vp]),
         "rt_moments_batches": (C.c_int, [vp]),
         "rt_get_variance": (C.c_int, [vp, vp, vp]),
+        "rt_adaptive_params_default": (AdaptiveParams, []),
+        "rt_render_adaptive": (C.c_int, [vp, P(AdaptiveParams), C.c_int, vp, vp, P(AdaptiveStats)]),
+        "rt_render_adaptive_device": (C.c_int, [vp, P(AdaptiveParams), C.c_int, vp, vp]),
+        "rt_adaptive_last_stats": (C.c_int, [vp, P(AdaptiveStats)]),
+        "rt_get_counts": (C.c_int, [vp, vp, vp]),
         "rt_error_string": (C.c_char_p, [C.c_int]),
         "rt_last_error": (C.c_char_p, [vp]),
         "rt_last_kernel_name": (C.c_char_p, [vp]),

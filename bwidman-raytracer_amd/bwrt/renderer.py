@@ -355,6 +355,56 @@ class Renderer:
         self._check(self.lib.rt_get_variance(self.ctx, var.ctypes.data, lum.ctypes.data if want_lum else None))
         return (var, lum) if want_lum else var
 
+    # -- adaptive sampling ------------------------------------------------------
+    def adaptive_params(self, samples=None, tolerance=None, lum_floor=None, radius=None, min_frames=None,
+                        max_frames=None):
+        """rt_adaptive_params_default() with the given fields replaced."""
+        d = self.lib.rt_adaptive_params_default()
+        for name, v in (("samples", samples), ("tolerance", tolerance), ("lum_floor", lum_floor), ("radius", radius),
+                        ("min_frames", min_frames), ("max_frames", max_frames)):
+            if v is not None:
+                setattr(d, name, v)
+        return d
+
+    @staticmethod
+    def _stats(st):
+        return {"selected": st.selected, "frames_total": st.frames_total, "select_ms": st.select_ms,
+                "render_ms": st.render_ms, "resolve_ms": st.resolve_ms}
+
+    def render_adaptive(self, width, height, max_bounces=-1, want_color=False, **params):
+        """rt_render_adaptive: `samples` more frames for the pixels the tracked
+        moments select (width x height: the shape of the accumulated full
+        frame; max_bounces < 0: the context's); `params` are adaptive_params()
+        fields.  Returns (RGBA8 image, stats dict), with want_color (image,
+        frameSum / n_p as (H, W, 3) float32, stats)."""
+        d = self.adaptive_params(**params)
+        out = np.empty((height, width, 4), np.uint8)
+        col = np.empty((height, width, 3), np.float32) if want_color else None
+        st = abi.AdaptiveStats()
+        self._check(self.lib.rt_render_adaptive(self.ctx, C.byref(d), max_bounces, out.ctypes.data,
+                                                col.ctypes.data if col is not None else None, C.byref(st)))
+        return (out, col, self._stats(st)) if want_color else (out, self._stats(st))
+
+    def render_adaptive_device(self, rgba_ptr: int, stream_ptr: int | None = None, max_bounces=-1, **params):
+        """rt_render_adaptive_device: the adaptive call with its RGBA8 into
+        device memory on a stream (asynchronous, ordered like render_device)."""
+        d = self.adaptive_params(**params)
+        self._check(self.lib.rt_render_adaptive_device(self.ctx, C.byref(d), max_bounces, rgba_ptr, stream_ptr))
+
+    def adaptive_stats(self) -> dict:
+        """rt_adaptive_last_stats: the last adaptive call's statistics (synchronises)."""
+        st = abi.AdaptiveStats()
+        self._check(self.lib.rt_adaptive_last_stats(self.ctx, C.byref(st)))
+        return self._stats(st)
+
+    def counts(self, rows, width):
+        """rt_get_counts: per-pixel (frames accumulated, moment batches
+        tracked), two (rows, width) uint32 arrays."""
+        n = np.empty((rows, width), np.uint32)
+        j = np.empty((rows, width), np.uint32)
+        self._check(self.lib.rt_get_counts(self.ctx, n.ctypes.data, j.ctypes.data))
+        return n, j
+
     # -- checkpoint / resume -----------------------------------------------
     def get_state(self, rows, width):
         rng = np.empty((6, rows, width), dtype=np.uint32)

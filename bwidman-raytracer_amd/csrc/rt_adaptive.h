@@ -1,0 +1,110 @@
+// rt_adaptive.h — variance-driven adaptive sampling: the selection criterion,
+// the moment update of a listed pixel and the resolve pass, shared by the HIP
+// unit (rt_adaptive.hip) and the CPU backend (rt_cpu.cpp).  Every float
+// operation is one rounding in the order written (both built with
+// -ffp-contract=off), so GPU and CPU contexts select the same pixels and keep
+// the same moments bit for bit.
+//
+// A context in the non-uniform state holds {n_p, J_p} per pixel: the frames
+// accumulated and the moment batches tracked for that pixel.  Per pixel q
+//   v_q = M2_q * rt_div(1, (float)(J_q - 1) * (float)n_q)
+// estimates the variance of the pixel's mean luminance (rt_moments.h).  The
+// window of p is every q with |dx|, |dy| <= radius inside the image whose v_q
+// and M_q are finite; row sums first, in increasing x, then the column sum of
+// the row sums in increasing y; the tap count c is an integer.  With
+// sv = sum v, sm = sum M, cf = (float)c:
+//   b     = tolerance * (sm + cf * lum_floor)
+//   hot_p = c > 0 && (sv * cf) > (b * b)
+// i.e. the root of the window-mean variance of the mean exceeds `tolerance`
+// times the window-mean luminance (plus the floor), without a division.
+//   selected_p = (max_frames == 0 || n_p + k <= max_frames) && (n_p < min_frames || hot_p)
+//
+// A selected pixel then renders k more frames (rt_kernel_list.h); its moments
+// take the step of rt_moments.h with the pixel's own weight
+//   kw_p = rt_div(kf, (float)(n_p + k)),
+// then J_p += 1, n_p += k, prev_p = frameSum_p.
+#pragma once
+#include "rt_moments.h"
+
+namespace {
+
+RT_HD bool ad_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }  // false for NaN and +-inf
+
+// the variance of pixel q's mean luminance (also rt_get_variance's in the non-uniform state)
+RT_HD float ad_var(float M2, unsigned n, unsigned J) { return M2 * rt_div(1.0f, (float)(J - 1u) * (float)n); }
+
+// row sums of the window of pixel (x, y), taps in increasing x
+RT_HD void ad_row_sums(const rt_ad_args& A, int x, int y, long p) {
+    float sv = 0.0f, sm = 0.0f;
+    int c = 0;
+    const int x0 = x - A.radius < 0 ? 0 : x - A.radius;
+    const int x1 = x + A.radius >= A.width ? A.width - 1 : x + A.radius;
+    for (int qx = x0; qx <= x1; qx++) {
+        const long q = (long)y * A.width + qx;
+        const float2 m = A.mom_in[q];
+        const uint2 cn = A.cnt[q];
+        const float v = ad_var(m.y, cn.x, cn.y);
+        if (!ad_finite(v) || !ad_finite(m.x)) continue;
+        sv = sv + v;
+        sm = sm + m.x;
+        c++;
+    }
+    A.rowv[p] = sv;
+    A.rowm[p] = sm;
+    A.rowc[p] = c;
+}
+
+// the column sum of the row sums in increasing y, the test and the selection of pixel (x, y)
+RT_HD bool ad_selected(const rt_ad_args& A, int x, int y, long p) {
+    const unsigned n = A.cnt[p].x;
+    if (A.max_frames != 0u && (unsigned long long)n + (unsigned)A.k > A.max_frames) return false;
+    if (n < A.min_frames) return true;
+    float sv = 0.0f, sm = 0.0f;
+    int c = 0;
+    const int y0 = y - A.radius < 0 ? 0 : y - A.radius;
+    const int y1 = y + A.radius >= A.height ? A.height - 1 : y + A.radius;
+    for (int qy = y0; qy <= y1; qy++) {
+        const long q = (long)qy * A.width + x;
+        sv = sv + A.rowv[q];
+        sm = sm + A.rowm[q];
+        c += A.rowc[q];
+    }
+    const float cf = (float)c;
+    const float b = A.tolerance * (sm + cf * A.lum_floor);
+    return c > 0 && (sv * cf) > (b * b);
+}
+
+// the moment step of listed pixel p behind its k new frames (rt_moments.h's
+// with the pixel's own weight), and its counts
+RT_HD void ad_update(const rt_ad_args& A, long p) {
+    const uint2 cn = A.cnt[p];
+    const float ax = A.accum[p], ay = A.accum[A.npix + p], az = A.accum[2 * A.npix + p];
+    const float px = A.prev[p], py = A.prev[A.npix + p], pz = A.prev[2 * A.npix + p];
+    const float2 m = A.mom[p];
+    const float kw = rt_div(A.kf, (float)(cn.x + (unsigned)A.k));
+    const float L = mom_lum(ax - px, ay - py, az - pz);
+    const float l = L * A.invk;
+    const float dl = l - m.x;
+    const float M1 = m.x + dl * kw;
+    const float M2n = m.y + (A.kf * dl) * (l - M1);
+    A.prev[p] = ax;
+    A.prev[A.npix + p] = ay;
+    A.prev[2 * A.npix + p] = az;
+    A.mom[p] = make_float2(M1, M2n);
+    A.cnt[p] = make_uint2(cn.x + (unsigned)A.k, cn.y + 1u);
+}
+
+// the image of pixel p: complete whatever earlier renders wrote
+RT_HD void ad_resolve(const rt_ad_args& A, long p) {
+    const unsigned n = A.cnt[p].x;
+    const float ax = A.accum[p], ay = A.accum[A.npix + p], az = A.accum[2 * A.npix + p];
+    if (A.rgba) A.rgba[p] = tone_map(ax, ay, az, n);
+    if (A.color) {
+        const float inv = rt_div(1.0f, (float)n);
+        A.color[3 * p + 0] = inv * ax;
+        A.color[3 * p + 1] = inv * ay;
+        A.color[3 * p + 2] = inv * az;
+    }
+}
+
+}  // namespace

@@ -181,6 +181,8 @@ int rt_create(int device, rt_context** out) {
     if (const char* g = tuning_env("BWRT_ORDER_PERIOD")) c->order_period = std::max(std::atoi(g), 1);
     if (const char* g = tuning_env("BWRT_DENOISE_KERNEL"))
         c->dn_kernel = std::strcmp(g, "tiled") == 0 ? 1 : std::strcmp(g, "direct") == 0 ? 0 : -1;
+    if (const char* g = tuning_env("BWRT_ADAPTIVE_KERNEL"))
+        c->ad_kernel = std::strcmp(g, "simple") == 0 ? 1 : std::strcmp(g, "queued") == 0 ? 2 : 0;
     if (const char* g = tuning_env("BWRT_PRECISION"))
         c->precision = std::strcmp(g, "fast") == 0 ? RT_PRECISION_REFERENCE_FAST : RT_PRECISION_EXACT;
     *out = c;
@@ -236,6 +238,8 @@ void rt_destroy(rt_context* c) {
             p->destroy();
         }
         if (c->host_rgba) (void)hipHostFree(c->host_rgba);
+        for (hipEvent_t e : c->ad_ev)
+            if (e) (void)hipEventDestroy(e);
         if (c->sky_ev) {
             (void)hipEventSynchronize(c->sky_ev);
             (void)hipEventDestroy(c->sky_ev);
@@ -281,6 +285,7 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
     c->camera = s->camera;
     c->has_scene = true;
     c->frame = 1;
+    c->ad_live = false;  // a non-uniform accumulation ends with its scene
     c->order_stale = true;
     c->sky_gen++;
     c->new_view();

@@ -4,6 +4,7 @@
 //
 //   rt_context.cpp  create / destroy, setters, controls, state, errors
 //   rt_render.cpp   prepare, fill_view, launch, rt_render*, multi-GPU, de-interleave
+//   rt_render_adaptive.cpp  rt_render_adaptive*, rt_get_counts (rt_adaptive.h)
 //   rt_post.cpp     first-hit features, denoiser, temporal reprojection, moment readout
 //   rt_scene.cpp    the scene compiler (rt_scene.h; no HIP, no context)
 // The render kernels: rt_launch.h declares the launchers of their units
@@ -36,6 +37,11 @@
 // ---- kernel launchers (the render units': rt_launch.h) ------------------------
 // scalar C++ CPU fallback (rt_cpu.cpp)
 int rt_cpu_render(const rt_kparams& K, int threads);
+// adaptive sampling on the host (rt_adaptive.h): selection into A.list /
+// *A.list_n, the listed pixels' frames, their update, the resolve pass
+void rt_cpu_adaptive_select(const rt_ad_args& A, int threads);
+void rt_cpu_adaptive_render(const rt_kparams& K, const rt_ad_args& A, int threads);
+void rt_cpu_adaptive_finish(const rt_ad_args& A, int threads);
 void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride);
 bool rt_cpu_supported();
 void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb);
@@ -51,6 +57,11 @@ hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream);
 hipError_t rt_launch_moments(const rt_mom_args& A, hipStream_t stream);
 // variance-guided filter (rt_denoise_var.hip): stage 0 input, 1 sigma pass, 2 level
 hipError_t rt_launch_denoise_var(const rt_dv_args& A, int stage, bool tiled, hipStream_t stream);
+// adaptive sampling (rt_adaptive.hip): the count fill; stage 0 row sums, 1 column
+// sums + test + scan + scatter, 2 the listed pixels' moment update, 3 resolve
+hipError_t rt_launch_adaptive_fill(uint2* cnt, unsigned long long* total, long npix, unsigned n, unsigned J,
+                                   hipStream_t stream);
+hipError_t rt_launch_adaptive(const rt_ad_args& A, int stage, hipStream_t stream);
 
 // ---- buffers -------------------------------------------------------------------
 // Device memory on a GPU context, host memory on a CPU context (ensure_buf);
@@ -262,7 +273,26 @@ struct rt_context {
     void mom_drop() {
         mom_live = false;
         mom_batches = 0;
+        ad_live = false;  // the counts go with the moments they belong to
     }
+
+    // adaptive sampling (rt_render_adaptive, rt_adaptive.h).  `ad_live`: the
+    // accumulation is non-uniform, ad_cnt holds {n_p, J_p} per pixel (filled
+    // with the context's counts by the first adaptive call of an accumulation;
+    // nothing is allocated before).  It ends where the moments end, at a
+    // render of frame 1 and at rt_set_scene.  ad_max_n bounds every n_p from
+    // above (host side: the counts themselves stay on the device).  The
+    // selection's scratch: row sums, mask words with their popcounts, the
+    // list and {list_n, frame total}.  ad_ev: select / render / update +
+    // resolve brackets of the last call, recorded only with kernel timing on.
+    bool ad_live = false;
+    unsigned long long ad_max_n = 0;
+    int ad_kernel = 0;  // BWRT_ADAPTIVE_KERNEL: 1 simple, 2 queued, 0 = launch policy
+    Buf ad_cnt, ad_rows, ad_mask, ad_pop, ad_list, ad_stat, ad_color;
+    hipEvent_t ad_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool ad_timed = false, ad_ran = false;
+    float ad_cpu_ms[3] = {-1.0f, -1.0f, -1.0f};
+    long long ad_cpu_selected = 0, ad_cpu_total = 0;
 
     // sky table (rt_sky.h): the table of the view `sky_key`, on the host and
     // (GPU contexts) in sky_buf; rebuilt and uploaded only when the key

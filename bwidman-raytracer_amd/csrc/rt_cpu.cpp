@@ -106,8 +106,10 @@ f3 trace_path(const rt_kparams& K, Xorwow& rs, f3 o, f3 d) {
     return mk(lx, ly, lz);
 }
 
-// Every frame of shard pixel p (Main.cu:285-312 per frame, frames in order)
-void render_pixel(const rt_kparams& K, long npix, long p) {
+// Every frame of shard pixel p (Main.cu:285-312 per frame, frames in order),
+// the first one `first`: K.first_frame, or n_p + 1 of a listed pixel of an
+// adaptive call (rt_adaptive.h), whose image the resolve pass writes
+void render_pixel(const rt_kparams& K, long npix, long p, unsigned first) {
     const int j = (int)(p / K.width);
     const int x = (int)(p - (long)j * K.width);
     const int y = K.row_offset + j * K.row_stride;
@@ -119,14 +121,14 @@ void render_pixel(const rt_kparams& K, long npix, long p) {
     rs.v3 = K.rng[4 * npix + p];
     rs.v4 = K.rng[5 * npix + p];
     float ax = 0.0f, ay = 0.0f, az = 0.0f;
-    if (K.first_frame != 1u) {
+    if (first != 1u) {
         ax = K.accum[0 * npix + p];
         ay = K.accum[1 * npix + p];
         az = K.accum[2 * npix + p];
     }
     const f3 d0 = primary_dir(K, x, y);
     const f3 cam = mk(K.cam_pos[0], K.cam_pos[1], K.cam_pos[2]);
-    unsigned frame = K.first_frame;
+    unsigned frame = first;
     for (int s = 0; s < K.samples; s++) {
         // jittered camera ray (Main.cu:290-292)
         const f3 jit = random_direction(rs, d0);
@@ -207,7 +209,7 @@ int rt_cpu_render(const rt_kparams& K, int threads) {
         _mm_setcsr((saved & ~(_MM_ROUND_MASK | _MM_FLUSH_ZERO_MASK | 0x0040u)) | _MM_ROUND_NEAREST);  // 0x40 = DAZ
         for (long c = next.fetch_add(1); c < chunks; c = next.fetch_add(1)) {
             const long end = (c + 1) * kChunk < npix ? (c + 1) * kChunk : npix;
-            for (long p = c * kChunk; p < end; p++) render_pixel(K, npix, p);
+            for (long p = c * kChunk; p < end; p++) render_pixel(K, npix, p, K.first_frame);
         }
         _mm_setcsr(saved);
     };
@@ -331,4 +333,35 @@ void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads) {
         else
             at_run_direct<DvFilter>(A, x, y);
     });
+}
+
+// ---- adaptive sampling on the host (rt_adaptive.h) -----------------------------
+#include "rt_adaptive.h"
+
+// The selection: row sums, then column sums and the test, then the list in
+// ascending pixel order (one thread: the order is the specification)
+void rt_cpu_adaptive_select(const rt_ad_args& A, int threads) {
+    parallel_pixels(A.width, A.height, threads, [&](int x, int y, long p) { ad_row_sums(A, x, y, p); });
+    std::vector<unsigned char> flags((size_t)A.npix);  // (no ballot on the host: one byte per pixel)
+    parallel_pixels(A.width, A.height, threads,
+                    [&](int x, int y, long p) { flags[(size_t)p] = ad_selected(A, x, y, p) ? 1 : 0; });
+    unsigned n = 0;
+    for (long p = 0; p < A.npix; p++)
+        if (flags[(size_t)p]) A.list[n++] = (int)p;
+    *A.list_n = n;
+    *A.total = *A.total + (unsigned long long)n * (unsigned)A.k;
+}
+
+// A.k more frames of every listed pixel, each from its own frame count
+void rt_cpu_adaptive_render(const rt_kparams& K, const rt_ad_args& A, int threads) {
+    parallel_items((long)*A.list_n, threads, [&](long i) {
+        const long p = A.list[i];
+        render_pixel(K, A.npix, p, A.cnt[p].x + 1u);
+    });
+}
+
+// The listed pixels' moment update, then the resolve pass over every pixel
+void rt_cpu_adaptive_finish(const rt_ad_args& A, int threads) {
+    parallel_items((long)*A.list_n, threads, [&](long i) { ad_update(A, (long)A.list[i]); });
+    parallel_items(A.npix, threads, [&](long p) { ad_resolve(A, p); });
 }

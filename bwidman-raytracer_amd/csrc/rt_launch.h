@@ -15,6 +15,14 @@ hipError_t rt_launch_render(const rt_kparams& K, int num_cus, int grid_mult, boo
                             hipStream_t stream, int pair_req);
 }  // namespace rt_fast
 
+// ---- the list render of an adaptive call (rt_kernel_list.h; exact units only)
+// which: 0 the policy, 1 the one-path-per-lane kernel, 2 the queued one; BVH
+// scenes and samplesPerPixel > 1 take the one-path-per-lane kernel whatever it says
+bool rt_render_list_queued(const rt_kparams& K, int which);
+hipError_t rt_launch_render_list(const rt_kparams& K, const rt_list_args& L, int num_cus, int which, hipStream_t s);
+hipError_t rt_launch_render_list_bvh(const rt_kparams& K, const rt_list_args& L, int block, size_t lds, int num_cus,
+                                     hipStream_t s);
+
 // ---- the same in both modes (rt_kernels_shared.hip) -----------------------------
 // launch policy: hit table in LDS, 64-lane groups (very deep paths), pair
 // kernel (pair_req: 1 / 0 forces it on / off, BWRT_SPREAD; -1 the policy)

@@ -242,3 +242,40 @@ struct rt_dv_args {
     const float2* mom;   // input stage, tracked: {M, M2}
     float* rs;           // reciprocal luminance sigma: the sigma pass writes it, the level reads its centre
 };
+
+// The list of an adaptive render (rt_adaptive.h): what the list render kernels
+// (rt_kernel_list.h) take besides rt_kparams, whose layout they leave alone.
+struct rt_list_args {
+    const int* list;         // selected shard pixel indices, ascending
+    const unsigned* list_n;  // their number (stays on the device)
+    const uint2* cnt;        // {n_p, J_p} per pixel: item i starts at frame n_p + 1
+};
+
+// One adaptive call (rt_adaptive.h) over the full width x height frame of a
+// context in the non-uniform state: the selection passes, the moment update of
+// the listed pixels and the resolve pass share it.
+struct rt_ad_args {
+    int width, height;
+    long npix;
+    int words_per_row;       // 64-pixel mask words per row
+    int k;                   // frames added to every selected pixel
+    int radius;
+    float tolerance, lum_floor;
+    unsigned min_frames, max_frames;
+    float kf, invk;          // (float)k, 1.0f / kf
+    const float2* mom_in;    // {M, M2} (selection)
+    float2* mom;             // (update)
+    uint2* cnt;              // {n_p, J_p}
+    float* accum;            // frameSum, 3 planes
+    float* prev;             // frameSum before the pixel's last tracked batch
+    float* rowv;             // row sums of the window: variance, luminance, taps
+    float* rowm;
+    int* rowc;
+    unsigned long long* mask;  // one word per 64 consecutive pixels of a row
+    unsigned* pop;           // its popcount, then (scan) the exclusive prefix
+    int* list;
+    unsigned* list_n;
+    unsigned long long* total;  // sum of n_p over the frame
+    unsigned* rgba;          // resolve: tone_map(frameSum, n_p) (may be null)
+    float* color;            // resolve: rt_div(1, n_p) * frameSum, interleaved r,g,b (may be null)
+};

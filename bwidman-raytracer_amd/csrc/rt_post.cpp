@@ -75,6 +75,9 @@ int full_frame_check(rt_context* c, const char* who) {
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the context holds a row shard (offset %d, stride %d): %s needs a full frame", c->row_offset,
                     c->row_stride, who);
+    if (c->ad_live)
+        return fail(c, RT_ERR_UNSUPPORTED,
+                    "the accumulation is non-uniform (rt_render_adaptive): %s takes one frame count for all pixels", who);
     return RT_OK;
 }
 
@@ -514,11 +517,14 @@ int rt_get_variance(rt_context* c, float* var_out, float* lum_out) {
                     c->mom_live ? "live" : "not live", c->mom_live ? c->mom_batches : 0u);
     const size_t npix = (size_t)c->rows * c->width;
     const float2* m = c->mom_m.as<float2>();
+    const uint2* cn = c->ad_live ? c->ad_cnt.as<uint2>() : nullptr;  // non-uniform: each pixel's own {n_p, J_p}
     std::vector<float2> host;
+    std::vector<uint2> host_cn;
     if (!c->cpu) {
         HIP_TRY(c, hipSetDevice(c->device));
         try {
             host.resize(npix);
+            if (cn) host_cn.resize(npix);
         } catch (...) {
             return fail(c, RT_ERR_OUT_OF_MEMORY, "host moments for %zu pixels", npix);
         }
@@ -527,6 +533,17 @@ int rt_get_variance(rt_context* c, float* var_out, float* lum_out) {
         if (rc) return rc;
         HIP_TRY(c, hipMemcpy(host.data(), m, npix * sizeof(float2), hipMemcpyDeviceToHost));
         m = host.data();
+        if (cn) {
+            HIP_TRY(c, hipMemcpy(host_cn.data(), cn, npix * sizeof(uint2), hipMemcpyDeviceToHost));
+            cn = host_cn.data();
+        }
+    }
+    if (cn) {  // rt_adaptive.h ad_var, the selection's own expression
+        for (size_t i = 0; i < npix; i++) {
+            if (var_out) var_out[i] = m[i].y * (1.0f / ((float)(cn[i].y - 1u) * (float)cn[i].x));
+            if (lum_out) lum_out[i] = m[i].x;
+        }
+        return RT_OK;
     }
     // 1 / ((J - 1) n), n = the frames accumulated
     const float rd = 1.0f / ((float)(c->mom_batches - 1u) * (float)(c->mom_next - 1u));

@@ -26,6 +26,15 @@ static int prepare(rt_context* c, const rt_render_params* p, rt_kparams& K, unsi
         if (rc) return rc;
     }
     first = p->first_frame ? p->first_frame : c->frame;
+    // a non-uniform accumulation (rt_render_adaptive) ends at a render of
+    // frame 1; no uniform render can continue it
+    if (c->ad_live) {
+        if (first != 1u)
+            return fail(c, RT_ERR_UNSUPPORTED,
+                        "the accumulation is non-uniform (rt_render_adaptive): a uniform render cannot continue it "
+                        "(first_frame %u; 1 restarts)", first);
+        c->ad_live = false;
+    }
     if ((unsigned long long)first + (unsigned)p->samples > 0xffffffffull)
         return fail(c, RT_ERR_INVALID_ARGUMENT, "frame counter overflow");
     if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));

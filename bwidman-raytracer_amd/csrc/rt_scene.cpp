@@ -19,6 +19,7 @@
 
 struct float4;  // rt_layout.h names them in pointer members only; no HIP header here
 struct float2;
+struct uint2;
 #include "rt_layout.h"
 
 namespace {

@@ -14,6 +14,8 @@
 //               [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]
 //               [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]
 //               [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]
+//               [--adaptive TOL] [--adaptive-after 4] [--adaptive-radius R] [--adaptive-floor F]
+//               [--min-frames N] [--max-frames N]
 //
 // --keys: comma-separated steps KEY[+KEY...]*FRAMES (keys W A S D SPACE
 // LEFT_SHIFT LEFT RIGHT UP DOWN ESCAPE; an empty key list holds nothing);
@@ -48,6 +50,15 @@
 // rt_denoise_var (N levels; --sigma-lum, --min-batches, --sigma-normal and
 // --sigma-plane replace the fields of rt_denoise_var_params_default()); it
 // cannot be combined with --denoise (and so not with --temporal's filter).
+// --adaptive TOL turns the tracking on and, after the first --adaptive-after
+// (default 4) uniform render calls of an accumulation, makes every later call
+// of the frame loop an rt_render_adaptive call with the loop's frames per call:
+// only the pixels whose window (--adaptive-radius) is noisier than TOL times
+// its mean luminance (plus --adaptive-floor) get the frames; --min-frames and
+// --max-frames force and cap per-pixel frame counts.  It prints the mean
+// frames per pixel and the last call's selected share; --aov PREFIX also
+// writes PREFIX_count (n_p over the largest n_p).  It cannot be combined with
+// --denoise, --denoise-var, --temporal, --precision fast or --gpus above 1.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -74,7 +85,9 @@ static const char* kUsage =
     "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n"
     "                   [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]\n"
     "                   [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]\n"
-    "                   [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]\n";
+    "                   [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]\n"
+    "                   [--adaptive TOL] [--adaptive-after 4] [--adaptive-radius R] [--adaptive-floor F]\n"
+    "                   [--min-frames N] [--max-frames N]\n";
 
 struct KeyStep {
     unsigned keys;
@@ -140,6 +153,9 @@ int main(int argc, char** argv) {
     std::string aov;
     bool moments = false, denoise_var = false;
     rt_denoise_var_params dv = rt_denoise_var_params_default();
+    bool adaptive = false;
+    int adaptive_after = 4;
+    rt_adaptive_params ad = rt_adaptive_params_default();
     for (int i = 1; i < argc; i++) {
         auto next = [&](void) -> const char* { return i + 1 < argc ? argv[++i] : ""; };
         if (!std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h")) {
@@ -197,6 +213,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--plane-tol")) tp.plane_tol = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--aov")) aov = next();
         else if (!std::strcmp(argv[i], "--moments")) moments = true;
+        else if (!std::strcmp(argv[i], "--adaptive")) {
+            adaptive = moments = true;
+            ad.tolerance = (float)std::atof(next());
+        }
+        else if (!std::strcmp(argv[i], "--adaptive-after")) adaptive_after = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--adaptive-radius")) ad.radius = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--adaptive-floor")) ad.lum_floor = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--min-frames")) ad.min_frames = (unsigned)std::strtoul(next(), nullptr, 10);
+        else if (!std::strcmp(argv[i], "--max-frames")) ad.max_frames = (unsigned)std::strtoul(next(), nullptr, 10);
         else {
             std::fprintf(stderr, "unknown option %s\n%s", argv[i], kUsage);
             return 2;
@@ -204,6 +229,16 @@ int main(int argc, char** argv) {
     }
     if (denoise && denoise_var) {
         std::fprintf(stderr, "--denoise and --denoise-var cannot be combined: one filter writes the frame\n");
+        return 2;
+    }
+    if (adaptive && (denoise || denoise_var || temporal || precision == RT_PRECISION_REFERENCE_FAST || gpus > 1)) {
+        std::fprintf(stderr,
+                     "--adaptive cannot be combined with --denoise, --denoise-var, --temporal, --precision fast or "
+                     "--gpus above 1: the filters and the fast mode take one frame count for all pixels\n");
+        return 2;
+    }
+    if (adaptive && adaptive_after < 2) {
+        std::fprintf(stderr, "--adaptive-after must be at least 2: the selection needs two tracked batches\n");
         return 2;
     }
     std::vector<KeyStep> steps;
@@ -277,12 +312,24 @@ int main(int argc, char** argv) {
     int frame_count = 0;
     size_t step = 0;
     int step_left = steps.empty() ? 0 : steps[0].frames;
+    int calls = 0;  // render calls of the current accumulation
+    rt_adaptive_stats ast{};
+    bool ast_valid = false;
     for (int done = 0; done < frames;) {  // Main.cu:471-496
         const int n = std::min(per_call, frames - done);
         auto t0 = clk::now();
-        rc = gpus == 1 ? rt_render(ctx, width, height, n, rgba.data())
-                       : rt_render_multi(ctxs.data(), gpus, width, height, n, rgba.data());
-        if (rc) return die(ctx, rc, "rt_render");
+        if (rt_frame_counter(ctx) == 1u) calls = 0;  // the accumulation restarts (controls())
+        if (adaptive && calls >= adaptive_after) {
+            ad.samples = n;
+            if ((rc = rt_render_adaptive(ctx, &ad, -1, rgba.data(), nullptr, &ast))) return die(ctx, rc, "rt_render_adaptive");
+            ast_valid = true;
+        } else {
+            rc = gpus == 1 ? rt_render(ctx, width, height, n, rgba.data())
+                           : rt_render_multi(ctxs.data(), gpus, width, height, n, rgba.data());
+            if (rc) return die(ctx, rc, "rt_render");
+            ast_valid = false;
+        }
+        calls++;
         done += n;
         const double frame_s = std::chrono::duration<double>(clk::now() - t0).count();
         if (temporal) {
@@ -360,6 +407,16 @@ int main(int argc, char** argv) {
         }
         std::printf("\n");
     }
+    std::vector<uint32_t> counts;
+    if (adaptive) {
+        const size_t npix = (size_t)width * height;
+        counts.resize(npix);
+        if ((rc = rt_get_counts(ctx, counts.data(), nullptr))) return die(ctx, rc, "rt_get_counts");
+        double total = 0.0;
+        for (const uint32_t c : counts) total += c;
+        std::printf("adaptive: mean %.2f frames per pixel, last call selected %.1f %%\n", total / (double)npix,
+                    ast_valid ? 100.0 * (double)ast.selected / (double)npix : 0.0);
+    }
     if (!aov.empty()) {
         const size_t npix = (size_t)width * height;
         std::vector<float> albedo(npix * 3), normal(npix * 3), depth(npix);
@@ -372,18 +429,21 @@ int main(int argc, char** argv) {
         const bool ppm = out.size() > 4 && out.compare(out.size() - 4, 4, ".ppm") == 0;
         auto u8 = [](float v) { return (uint8_t)(v >= 1.0f ? 255 : v > 0.0f ? (int)(v * 255.0f + 0.5f) : 0); };
         std::vector<uint8_t> img(npix * 4);
-        for (int k = 0; k < (moments ? 4 : 3); k++) {
+        uint32_t cmax = 1;
+        for (const uint32_t c : counts) cmax = std::max(cmax, c);
+        for (int k = 0; k < (adaptive ? 5 : moments ? 4 : 3); k++) {
             for (size_t i = 0; i < npix; i++) {
-                const float se = k == 3 ? std::sqrt(var[i]) : 0.0f;
+                const float se = k == 3 ? std::sqrt(var[i]) : k == 4 ? (float)counts[i] / (float)cmax : 0.0f;
                 for (int ch = 0; ch < 3; ch++)
                     img[4 * i + ch] = k == 0   ? u8(albedo[3 * i + ch])
                                       : k == 1 ? u8(normal[3 * i + ch] * 0.5f + 0.5f)
                                       : k == 2 ? u8(1.0f / (1.0f + depth[i]))
-                                               : u8(se / (1.0f + se));
+                                      : k == 3 ? u8(se / (1.0f + se))
+                                               : u8(se);
                 img[4 * i + 3] = 255;
             }
             const std::string name =
-                aov + (k == 0 ? "_albedo" : k == 1 ? "_normal" : k == 2 ? "_depth" : "_var") + (ppm ? ".ppm" : ".png");
+                aov + (k == 0 ? "_albedo" : k == 1 ? "_normal" : k == 2 ? "_depth" : k == 3 ? "_var" : "_count") + (ppm ? ".ppm" : ".png");
             if (!(ppm ? bwrt::write_ppm(name, width, height, img.data()) : bwrt::write_png(name, width, height, img.data()))) {
                 std::fprintf(stderr, "cannot write %s\n", name.c_str());
                 return 1;

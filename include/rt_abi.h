@@ -24,8 +24,9 @@
  *    cross the ABI.  rt_last_error() gives a human-readable message.
  *  - One context = one GPU (HIP device) and one pixel-row shard.  A context
  *    must be used by one host thread at a time.  All calls except
- *    rt_render_device()/rt_denoise_device()/rt_denoise_var_device()/
- *    rt_temporal_device()/rt_deinterleave_rows_device() are synchronous.
+ *    rt_render_device()/rt_render_adaptive_device()/rt_denoise_device()/
+ *    rt_denoise_var_device()/rt_temporal_device()/
+ *    rt_deinterleave_rows_device() are synchronous.
  *  - Output RGBA8 buffers are row-major, row 0 = BOTTOM of the screen
  *    (the reference draws texcoord (0,0) at the bottom-left, Main.cu:358).
  *  - Semantics of one "sample" (progressive frame) follow the reference
@@ -48,7 +49,9 @@
  *                       instead of the highest priority), BWRT_DEINT_BLOCKS,
  *                       BWRT_PRECISION=fast|exact,
  *                       BWRT_DENOISE_KERNEL=direct|tiled (filter kernel variant,
- *                       rt_denoise and rt_denoise_var)
+ *                       rt_denoise and rt_denoise_var),
+ *                       BWRT_ADAPTIVE_KERNEL=simple|queued (list render kernel of
+ *                       rt_render_adaptive on brute-force scenes)
  *      at rt_set_scene: BWRT_BVH_MIN, BWRT_BVH_LEAF, BWRT_BVH_CT, BWRT_BVH_SBVH,
  *                       BWRT_BVH_REFS, BWRT_BVH_ALPHA, BWRT_BVH_ORDER_MASK,
  *                       BWRT_BVH_N16, BWRT_NO_CULL, BWRT_BVH_STATS (report)
@@ -193,7 +196,7 @@ RT_API void rt_destroy(rt_context* ctx);
  * renders on the CPU, and every entry point behaves on it as on a GPU
  * context (rt_set_scene, rt_init_rand, rt_render, rt_render_ex, rt_controls,
  * rt_get_state / rt_set_state, ...; rt_last_kernel_ms gives the last render's
- * wall time) except rt_render_device, rt_denoise_device, rt_denoise_var_device,
+ * wall time) except rt_render_device, rt_render_adaptive_device, rt_denoise_device, rt_denoise_var_device,
  * rt_temporal_device, rt_render_multi and rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no
  * device memory).
  * Replaces the reference's config-1 CPU path and is the CPU baseline of
@@ -378,7 +381,10 @@ RT_API float rt_last_kernel_ms(rt_context* ctx);
  * launch that was given a sky table (rt_sky_table) ends in "+sky"; "" before
  * the first render and on a CPU context.  A diagnostic of the launch
  * policy (tests assert which kernel a workload runs); valid until the next
- * render on the context.  The reference launches one kernel, Main.cu:342. */
+ * render on the context.  An adaptive call reports its list render kernel:
+ * "rt_render_list_kernel<256,grec>" (queued) or "rt_render_kernel<256,list>"
+ * (one path per lane; ",bvh,list" on BVH scenes).  The reference launches one
+ * kernel, Main.cu:342. */
 RT_API const char* rt_last_kernel_name(const rt_context* ctx);
 
 /* Per-launch kernel timing (default on): every render records a start event
@@ -601,6 +607,84 @@ RT_API int rt_denoise_var_device(rt_context* ctx, const rt_denoise_var_params* p
                                  void* stream);
 /* Duration (ms) of all passes of the last rt_denoise_var call; -1 when unavailable. */
 RT_API float rt_last_denoise_var_ms(rt_context* ctx);
+
+/* ---- variance-driven adaptive sampling ---------------------------------------------
+ * The tracked moments say how noisy each pixel still is; rt_render_adaptive()
+ * spends the next `samples` frames only on the pixels whose neighbourhood has
+ * not converged.  Per pixel q, v_q = M2_q / ((J_q - 1) n_q) estimates the
+ * variance of its mean luminance.  Over the window |dx|, |dy| <= radius
+ * (clipped to the image; taps with a non-finite v or M are skipped; c taps)
+ * a pixel is *hot* when
+ *     sqrt(sum v / c)  >  tolerance * (sum M / c + lum_floor)
+ * evaluated without a division as (sum v) c > (tolerance (sum M + c lum_floor))^2
+ * (csrc/rt_adaptive.h and DESIGN.md section 14 have the exact float
+ * operations; GPU and CPU contexts select the same pixels).  Then
+ *     selected = (max_frames == 0 || n_p + samples <= max_frames) &&
+ *                (n_p < min_frames || hot)
+ * Every pixel owns its RNG stream, so a pixel that has received n_p frames
+ * holds exactly the frameSum, RNG state and RGBA a uniform render stopped at
+ * n_p frames would have given it, on both backends.
+ *
+ * The first adaptive call of an accumulation allocates one {n_p, J_p} pair per
+ * pixel (frames accumulated, moment batches tracked), filled with the
+ * context's counts; nothing is allocated before.  From then on the
+ * accumulation is *non-uniform*, until a render whose first frame is 1,
+ * rt_set_scene, rt_init_rand (also the implicit one), rt_set_state or
+ * rt_set_moments(ctx, 0) (after rt_reset_accumulation, rt_set_camera and a
+ * moving rt_controls the next render starts at frame 1).  While non-uniform:
+ *  - a uniform render that continues (first_frame 0 or any value but 1),
+ *    rt_denoise*, rt_denoise_var*, rt_temporal* and rt_render_multi return
+ *    RT_ERR_UNSUPPORTED (filters that weigh by the counts are future work);
+ *  - rt_get_state and rt_render_aov work as ever; rt_get_variance uses each
+ *    pixel's own J_p and n_p; rt_frame_counter and rt_moments_batches keep
+ *    reporting the uniform base (adaptive calls do not advance them);
+ *  - the counts are not part of rt_get_state / rt_set_state: a non-uniform
+ *    accumulation cannot be checkpointed (rt_set_state ends it).
+ * A context that never calls these entry points behaves bit for bit as before.
+ *
+ * Errors: RT_ERR_NO_SCENE; RT_ERR_INVALID_ARGUMENT when moment tracking is not
+ * live or has fewer than 2 batches, a parameter is out of range or NaN, or a
+ * count could pass 2^32 - 1; RT_ERR_UNSUPPORTED when the context's pixel state
+ * is a row shard (the window needs neighbours), in RT_PRECISION_REFERENCE_FAST
+ * (a list schedule would be a new arithmetic form of that mode, whose results
+ * depend on the schedule), for max_bounces above RT_MAX_BOUNCES, and for the
+ * device variant on a CPU context.  The view is the context's current full
+ * frame: width and height are the context's. */
+#define RT_ADAPTIVE_MAX_RADIUS 4
+typedef struct rt_adaptive_params {
+    int samples;         /* k >= 1: frames added to every selected pixel */
+    float tolerance;     /* > 0: root of the window-mean variance of the mean over window-mean luminance */
+    float lum_floor;     /* >= 0: added to the window-mean luminance */
+    int radius;          /* 0..RT_ADAPTIVE_MAX_RADIUS: window half-width in pixels */
+    unsigned min_frames; /* a pixel with n_p < min_frames is always selected (0: none forced) */
+    unsigned max_frames; /* a pixel with n_p + k > max_frames is never selected (0: no cap) */
+} rt_adaptive_params;
+typedef struct rt_adaptive_stats {
+    long long selected;      /* pixels the last call rendered */
+    long long frames_total;  /* sum of n_p after it */
+    float select_ms, render_ms, resolve_ms;  /* -1 when unavailable (GPU: kernel timing off) */
+} rt_adaptive_stats;
+RT_API rt_adaptive_params rt_adaptive_params_default(void);
+/* Select, render `samples` frames of the selected pixels (max_bounces < 0: the
+ * context's), update their moments and counts, and resolve the whole frame:
+ * RGBA = tone map of frameSum / n_p for every pixel (complete whatever earlier
+ * renders wrote).  rgba_out: w*h*4 bytes or NULL; color_out: w*h*3 floats
+ * (frameSum / n_p) or NULL; stats_out may be NULL.  Synchronous. */
+RT_API int rt_render_adaptive(rt_context* ctx, const rt_adaptive_params* params, int max_bounces,
+                              uint8_t* rgba_out, float* color_out, rt_adaptive_stats* stats_out);
+/* As above with the RGBA into DEVICE memory (w*h*4 bytes, 4-byte aligned, or
+ * NULL) on HIP stream `stream` (NULL = the context's), with rt_render_device's
+ * ordering rules; asynchronous like it.  No host synchronisation happens
+ * inside the call: the list of selected pixels and its length stay on the
+ * device. */
+RT_API int rt_render_adaptive_device(rt_context* ctx, const rt_adaptive_params* params, int max_bounces,
+                                     void* rgba_device, void* stream);
+/* The statistics of the last adaptive call; synchronises on it. */
+RT_API int rt_adaptive_last_stats(rt_context* ctx, rt_adaptive_stats* stats_out);
+/* Per-pixel counts, w*h each, either may be NULL: frames accumulated and moment
+ * batches tracked.  In the uniform state every pixel reports the context's
+ * (frame counter - 1, rt_moments_batches).  Synchronous. */
+RT_API int rt_get_counts(rt_context* ctx, uint32_t* frames_out, uint32_t* batches_out);
 
 RT_API const char* rt_error_string(int status);
 RT_API const char* rt_last_error(const rt_context* ctx);

@@ -1,0 +1,479 @@
+"""Variance-driven adaptive sampling (rt_render_adaptive, rt_get_counts) on the
+CPU backend — no GPU needed.  The GPU kernels compute the same bits
+(tests/test_gpu_adaptive.py compares them with this backend).
+
+The oracle of the whole feature: every pixel owns its RNG stream, so a pixel
+that has received n_p frames holds exactly the frameSum, RNG state and RGBA of
+a uniform render stopped at n_p frames.  The float64 reference of the selection
+and of the per-pixel moments is tests/adaptive_ref.py.
+"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import adaptive_ref as R
+from bwrt import Renderer, abi, scenes
+
+CLI = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bwidman-raytracer_amd", "bin",
+                   "bwrt_render")
+
+START = (2, 2, 2, 2)  # the uniform start of every sequence: 4 calls x 2 frames
+KS = (3, 1, 4)        # frames of the adaptive calls of the replay sequences
+DEFAULTS = dict(tolerance=0.1, lum_floor=0.01, radius=2)
+# (scene, width, height, bounces): the replay cases
+REPLAY = [("07", 67, 45, 4), ("04_box", 64, 36, 3), ("stress", 96, 54, 8)]
+
+# max |var - float64 reference| / (scale + |reference|) and the same for M,
+# scale = the frame's mean luminance, in the non-uniform state.  Measured on the
+# CPU backend over test_pixel_moments_against_float64 (scene 07, 67x45, 4
+# bounces, the 4 x 2 start and adaptive calls of 3, 1 and 4 frames; mean
+# luminance 0.108): M 1.55e-7, var 2.22e-7.  Asserted at 8x, the convention of
+# tests/test_moments.py: a wrong weight or count moves either by O(1).
+AD_BOUND_M = 8 * 1.55e-7
+AD_BOUND_VAR = 8 * 2.22e-7
+
+
+@pytest.fixture(scope="module")
+def cpu(bwrt_lib):
+    r = Renderer.cpu(0, lib=bwrt_lib)
+    yield r
+    r.close()
+
+
+def start(r, scene, w, h, bounces, calls=START):
+    """Scene set, state reseeded, tracking on, the uniform start."""
+    r.set_scene(scene)
+    r.init_rand(w, h)
+    r.set_moments(True)
+    acc = None
+    for i, k in enumerate(calls):
+        _, acc = r.render(w, h, k, bounces, first_frame=1 if i == 0 else 0, want_accum=True)
+    return acc
+
+
+_SNAPS = {}
+
+
+def uniform_snapshots(lib, name, w, h, bounces, upto):
+    """frame count -> (RGBA, RNG state, frameSum) of a CPU context rendering
+    uniformly frame by frame; computed once per case and kept unchanged."""
+    key = (name, w, h, bounces)
+    have = _SNAPS.get(key)
+    if have is None or max(have) < upto:
+        have = {}
+        with Renderer.cpu(0, lib=lib) as u:
+            u.set_scene(scenes.SCENES[name]())
+            for f in range(1, upto + 1):
+                img = u.render(w, h, 1, bounces, first_frame=1 if f == 1 else 0)
+                rng, acc = u.get_state(h, w)
+                for a in (img, rng, acc):
+                    a.setflags(write=False)
+                have[f] = (img, rng, acc)
+        _SNAPS[key] = have
+    return have
+
+
+def adaptive_sequence(r, scene, w, h, bounces, ks=KS, params=DEFAULTS):
+    """The start, then one adaptive call per entry of ks.  Everything a
+    backend comparison needs: stats, counts, state, image, colour, moments."""
+    start(r, scene, w, h, bounces)
+    out = {"stats": [], "took": [], "acc": []}
+    n_before = r.counts(h, w)[0]
+    for k in ks:
+        img, col, st = r.render_adaptive(w, h, bounces, want_color=True, samples=k, **params)
+        n, j = r.counts(h, w)
+        out["stats"].append((st["selected"], st["frames_total"]))
+        out["took"].append(n != n_before)
+        out["acc"].append(r.get_state(h, w)[1])
+        n_before = n
+    out["n"], out["j"] = n, j
+    out["rng"], out["accum"] = r.get_state(h, w)
+    out["rgba"], out["color"] = img, col
+    out["var"], out["lum"] = r.variance(h, w, want_lum=True)
+    return out
+
+
+def check_replay(res, snaps):
+    """Every pixel equals the uniform render stopped at its own frame count."""
+    n = res["n"]
+    for f in np.unique(n):
+        m = n == f
+        img, rng, acc = snaps[int(f)]
+        assert np.array_equal(res["rgba"][m], img[m]), f
+        assert np.array_equal(res["rng"][:, m], rng[:, m]), f
+        assert np.array_equal(res["accum"][m], acc[m], equal_nan=True), f
+    inv = (np.float32(1.0) / n.astype(np.float32))[..., None]
+    assert np.array_equal(res["color"], inv * res["accum"], equal_nan=True)
+
+
+# ---- ABI ------------------------------------------------------------------------
+
+def test_abi_declares_the_entry_points(bwrt_lib):
+    names = {"rt_adaptive_params_default", "rt_render_adaptive", "rt_render_adaptive_device",
+             "rt_adaptive_last_stats", "rt_get_counts"}
+    assert names <= set(abi.declared_functions())
+    for n in names:
+        assert hasattr(bwrt_lib, n)
+    d = bwrt_lib.rt_adaptive_params_default()
+    assert (d.samples, d.radius, d.min_frames, d.max_frames) == (8, 2, 0, 0)
+    assert d.tolerance == np.float32(0.1) and d.lum_floor == np.float32(0.01)
+    assert C.sizeof(abi.AdaptiveParams) == 24 and C.sizeof(abi.AdaptiveStats) == 32
+    assert abi.RT_ADAPTIVE_MAX_RADIUS == 4
+
+
+def test_errors(bwrt_lib):
+    lib = bwrt_lib
+    w, h = 33, 17
+    with Renderer.cpu(2, lib=lib) as r:
+        def call(max_bounces=2, **kw):
+            d = r.adaptive_params(**kw)
+            return lib.rt_render_adaptive(r.ctx, C.byref(d), max_bounces, None, None, None)
+        assert call() == abi.RT_ERR_NO_SCENE
+        r.set_scene(scenes.scene_07())
+        assert call() == abi.RT_ERR_INVALID_ARGUMENT  # no tracking, no state
+        r.render(w, h, 2, 2, first_frame=1)
+        r.render(w, h, 2, 2)
+        assert call() == abi.RT_ERR_INVALID_ARGUMENT  # tracking off
+        r.set_moments(True)
+        r.render(w, h, 2, 2, first_frame=1)
+        assert call() == abi.RT_ERR_INVALID_ARGUMENT  # one batch
+        assert b"2 batches" in lib.rt_last_error(r.ctx)
+        r.render(w, h, 2, 2)
+        for bad in (dict(samples=0), dict(samples=-3), dict(tolerance=0.0), dict(tolerance=-1.0),
+                    dict(tolerance=float("nan")), dict(lum_floor=-0.5), dict(lum_floor=float("nan")),
+                    dict(lum_floor=float("inf")), dict(radius=-1), dict(radius=abi.RT_ADAPTIVE_MAX_RADIUS + 1)):
+            assert call(**bad) == abi.RT_ERR_INVALID_ARGUMENT, bad
+        assert call(max_bounces=abi.RT_MAX_BOUNCES + 1) == abi.RT_ERR_UNSUPPORTED
+        assert lib.rt_render_adaptive(r.ctx, None, 2, None, None, None) == abi.RT_ERR_INVALID_ARGUMENT
+        d = r.adaptive_params()
+        assert lib.rt_render_adaptive_device(r.ctx, C.byref(d), 2, None, None) == abi.RT_ERR_UNSUPPORTED  # CPU context
+        assert not any(x is None for x in r.counts(h, w)) and (r.counts(h, w)[0] == 4).all()  # still uniform
+        # a count that could pass 2^32 - 1: calls that select nothing (max_frames 1) raise only the bound
+        big = 2 ** 31 - 1
+        assert call(samples=big, max_frames=1) == abi.RT_OK
+        assert r.adaptive_stats()["selected"] == 0
+        assert call(samples=big, max_frames=1) == abi.RT_ERR_INVALID_ARGUMENT  # 4 + 2 (2^31 - 1) > 2^32 - 1
+        assert b"overflow" in lib.rt_last_error(r.ctx)
+        # a row shard: the window needs neighbours
+        r.render(w, h, 2, 2, first_frame=1, row_offset=1, row_stride=2)
+        r.render(w, h, 2, 2, row_offset=1, row_stride=2)
+        assert r.moments_batches == 2
+        assert call() == abi.RT_ERR_UNSUPPORTED
+        assert b"row shard" in lib.rt_last_error(r.ctx)
+
+
+def test_non_uniform_state(bwrt_lib):
+    lib = bwrt_lib
+    scene = scenes.scene_07()
+    w, h, mb = 33, 17, 2
+    with Renderer.cpu(2, lib=lib) as r:
+        def go_non_uniform():
+            start(r, scene, w, h, mb)
+            _, st = r.render_adaptive(w, h, mb, samples=2, min_frames=100, max_frames=0)
+            assert st["selected"] == w * h
+        params = r.params(w, h, 1, mb)
+        dn, dv, tp = r.denoise_params(), r.denoise_var_params(), r.temporal_params()
+        go_non_uniform()
+        assert r.frame_counter == 9 and r.moments_batches == 4  # the uniform base, not advanced
+        for first in (0, 9, 11, 2):
+            params.first_frame = first
+            assert lib.rt_render_ex(r.ctx, C.byref(params), None, None) == abi.RT_ERR_UNSUPPORTED, first
+            assert b"non-uniform" in lib.rt_last_error(r.ctx)
+        assert lib.rt_denoise(r.ctx, C.byref(dn), None, None) == abi.RT_ERR_UNSUPPORTED
+        assert lib.rt_denoise_var(r.ctx, C.byref(dv), None, None, None) == abi.RT_ERR_UNSUPPORTED
+        assert lib.rt_temporal(r.ctx, C.byref(tp), None, None, None, None) == abi.RT_ERR_UNSUPPORTED
+        arr = (C.c_void_p * 1)(r.ctx.value)
+        assert lib.rt_render_multi(arr, 1, w, h, 1, None) == abi.RT_ERR_UNSUPPORTED
+        # what keeps working
+        r.get_state(h, w)
+        assert r.render_aov(w, h)["prim"].shape == (h, w)
+        assert np.isfinite(r.variance(h, w)).all()
+        n, j = r.counts(h, w)
+        assert (n == 10).all() and (j == 5).all()
+        # a render of frame 1 ends the state: uniform renders and a filter work again
+        r.render(w, h, 2, mb, first_frame=1)
+        r.render(w, h, 2, mb)
+        assert (r.counts(h, w)[0] == 4).all() and (r.counts(h, w)[1] == 2).all()
+        assert lib.rt_denoise(r.ctx, C.byref(dn), None, None) == abi.RT_OK
+        # the other ends
+        go_non_uniform()
+        r.set_scene(scene)
+        assert r.frame_counter == 1 and (r.counts(h, w)[0] == 0).all()
+        go_non_uniform()
+        r.init_rand(w, h)
+        assert (r.counts(h, w)[0] == 0).all()
+        go_non_uniform()
+        rng, acc = r.get_state(h, w)
+        r.set_state(rng, acc, 9)
+        assert (r.counts(h, w)[0] == 8).all()
+        r.render(w, h, 1, mb)  # continues uniformly
+        assert lib.rt_denoise(r.ctx, C.byref(dn), None, None) == abi.RT_OK
+        go_non_uniform()
+        r.set_moments(False)
+        assert (r.counts(h, w)[0] == 8).all()
+        r.render(w, h, 1, mb)
+        d = r.adaptive_params()
+        assert lib.rt_render_adaptive(r.ctx, C.byref(d), mb, None, None, None) == abi.RT_ERR_INVALID_ARGUMENT
+        # after rt_reset_accumulation the next render starts at frame 1
+        go_non_uniform()
+        r.reset_accumulation()
+        r.render(w, h, 1, mb)
+        assert (r.counts(h, w)[0] == 1).all()
+
+
+# ---- replay: the core test --------------------------------------------------------
+
+@pytest.mark.parametrize("name,w,h,bounces", REPLAY)
+def test_replay(cpu, bwrt_lib, name, w, h, bounces):
+    res = adaptive_sequence(cpu, scenes.SCENES[name](), w, h, bounces)
+    share = res["stats"][0][0] / (w * h)
+    print(f"{name} {w}x{h}: first call selects {100 * share:.1f} %, counts {np.unique(res['n'])}")
+    if name == "stress":
+        assert res["stats"][0][0] > 0  # a list shorter than two waves
+    else:
+        assert 0.2 < share < 0.8  # both selected and unselected pixels
+    check_replay(res, uniform_snapshots(bwrt_lib, name, w, h, bounces, 8 + sum(KS)))
+    # the statistics are the bookkeeping of the calls
+    total = 8 * w * h
+    for (sel, tot), took, k in zip(res["stats"], res["took"], KS):
+        total += k * sel
+        assert sel == took.sum() and tot == total
+    assert res["n"].sum() == total
+    cpu.set_moments(False)
+
+
+def test_select_all_equals_uniform(bwrt_lib):
+    scene = scenes.scene_07()
+    w, h, mb, k = 67, 45, 4, 3
+    with Renderer.cpu(0, lib=bwrt_lib) as a, Renderer.cpu(0, lib=bwrt_lib) as u:
+        start(a, scene, w, h, mb)
+        start(u, scene, w, h, mb)
+        img_a, st = a.render_adaptive(w, h, mb, samples=k, min_frames=1000, **DEFAULTS)
+        img_u = u.render(w, h, k, mb)
+        assert st["selected"] == w * h and st["frames_total"] == (8 + k) * w * h
+        assert np.array_equal(img_a, img_u)
+        for x, y in zip(a.get_state(h, w) + a.variance(h, w, want_lum=True),
+                        u.get_state(h, w) + u.variance(h, w, want_lum=True)):
+            assert np.array_equal(x, y, equal_nan=True)
+
+
+def test_nothing_selected(bwrt_lib):
+    scene = scenes.scene_07()
+    w, h, mb = 67, 45, 4
+    with Renderer.cpu(0, lib=bwrt_lib) as r:
+        start(r, scene, w, h, mb)
+        last = r.render(w, h, 1, mb)
+        before = r.get_state(h, w) + r.variance(h, w, want_lum=True)
+        img, st = r.render_adaptive(w, h, mb, samples=5, tolerance=1e30, lum_floor=0.01, radius=2)
+        assert st["selected"] == 0 and st["frames_total"] == 9 * w * h
+        assert np.array_equal(img, last)
+        for x, y in zip(before, r.get_state(h, w) + r.variance(h, w, want_lum=True)):
+            assert np.array_equal(x, y, equal_nan=True)
+        n, j = r.counts(h, w)
+        assert (n == 9).all() and (j == 5).all()
+
+
+# ---- selection against float64 -------------------------------------------------------
+
+def selection_case(r, scene, w, h, mb, k=2, **params):
+    """(library's selected set, reference's, marginal, taps) of one adaptive
+    call behind the start."""
+    start(r, scene, w, h, mb)
+    var, M = r.variance(h, w, want_lum=True)
+    n0 = r.counts(h, w)[0]
+    r.render_adaptive(w, h, mb, samples=k, **params)
+    got = r.counts(h, w)[0] != n0
+    want, marginal, taps = R.select_ref(var, M, n0, k, **params)
+    return got, want, marginal, taps, (var, M)
+
+
+@pytest.mark.parametrize("name,w,h,mb,params", [
+    ("07", 67, 45, 4, dict(tolerance=0.1, lum_floor=0.01, radius=0)),
+    ("07", 67, 45, 4, dict(tolerance=0.1, lum_floor=0.01, radius=1)),
+    ("07", 67, 45, 4, dict(tolerance=0.25, lum_floor=0.01, radius=2)),
+    ("07", 67, 45, 4, dict(tolerance=0.5, lum_floor=0.0, radius=3)),
+    ("07", 67, 45, 4, dict(tolerance=0.1, lum_floor=0.01, radius=4)),
+    ("07", 5, 3, 4, dict(tolerance=0.1, lum_floor=0.01, radius=4)),  # every window clipped at all four borders
+    ("04_box", 64, 36, 3, dict(tolerance=0.1, lum_floor=0.01, radius=2)),
+    ("07", 333, 187, 4, dict(tolerance=0.1, lum_floor=0.01, radius=2)),
+    ("07", 800, 450, 4, dict(tolerance=0.25, lum_floor=0.01, radius=3)),
+])
+def test_selection_against_float64(cpu, name, w, h, mb, params):
+    got, want, marginal, _, _ = selection_case(cpu, scenes.SCENES[name](), w, h, mb, **params)
+    print(f"{name} {w}x{h} {params}: selected {got.mean():.3f}, marginal {int(marginal.sum())}")
+    assert marginal.mean() <= 0.02
+    assert np.array_equal(got[~marginal], want[~marginal])
+    if w * h > 100:
+        assert 0 < got.sum() < w * h
+    cpu.set_moments(False)
+
+
+def test_selection_skips_non_finite_taps(cpu):
+    """The ABI has no way to write M2, so the non-finite moments come from the
+    scene: the small light of scene 07 with an infinite emittance.  A pixel
+    whose path reaches it in its last batch holds M = inf and M2 = NaN (inf -
+    inf), one that reached it earlier NaN in both.  Those are skipped as taps,
+    and a window without a finite tap selects nothing."""
+    w, h, mb = 67, 45, 4
+    scene = scenes.scene_07()
+    scene.spheres[2].mat.emittance = float("inf")
+    for radius in (0, 2):  # radius 0: a non-finite pixel's window has no tap at all
+        got, want, marginal, taps, (var, M) = selection_case(cpu, scene, w, h, mb, tolerance=0.1, lum_floor=0.01,
+                                                             radius=radius)
+        bad = ~(np.isfinite(var) & np.isfinite(M))
+        print(f"radius {radius}: non-finite pixels {bad.mean():.3f}, windows without a tap {(taps == 0).sum()}, "
+              f"NaN M {np.isnan(M).sum()}, inf M {np.isinf(M).sum()}")
+        assert np.isnan(var[bad]).any() and (np.isinf(M[bad]).any() or np.isnan(M[bad]).any())
+        assert 0.01 < bad.mean() < 0.95
+        if radius == 0:
+            assert np.array_equal(taps == 0, bad)
+        else:
+            assert ((taps > 0) & (taps < np.minimum(taps.max(), 25))).any()
+        assert not got[taps == 0].any()
+        assert marginal.mean() <= 0.02
+        assert np.array_equal(got[~marginal], want[~marginal])
+    cpu.set_moments(False)
+
+
+def test_min_max_frames_precedence(cpu):
+    scene = scenes.scene_07()
+    w, h, mb = 67, 45, 4
+    start(cpu, scene, w, h, mb)
+    cpu.render_adaptive(w, h, mb, samples=3, **DEFAULTS)  # splits the counts: 8 and 11
+    n1 = cpu.counts(h, w)[0]
+    assert set(np.unique(n1)) == {8, 11}
+    # forced below min_frames, whatever the window says; others by the window
+    cpu.render_adaptive(w, h, mb, samples=1, min_frames=9, tolerance=1e30, lum_floor=0.0, radius=2)
+    n2 = cpu.counts(h, w)[0]
+    assert np.array_equal(n2 != n1, n1 == 8)
+    # the cap wins over min_frames: n + k <= max_frames
+    cpu.render_adaptive(w, h, mb, samples=2, min_frames=1000, max_frames=11, **DEFAULTS)
+    n3 = cpu.counts(h, w)[0]
+    assert np.array_equal(n3 != n2, n2 == 9) and set(np.unique(n3)) == {11}
+    cpu.render_adaptive(w, h, mb, samples=1, min_frames=1000, max_frames=11, **DEFAULTS)
+    assert np.array_equal(cpu.counts(h, w)[0], n3) and cpu.adaptive_stats()["selected"] == 0
+    cpu.set_moments(False)
+
+
+# ---- per-pixel moments, thread count, counts, quality -----------------------------------
+
+def test_pixel_moments_against_float64(cpu):
+    scene = scenes.scene_07()
+    w, h, mb = 67, 45, 4
+    cpu.set_scene(scene)
+    cpu.init_rand(w, h)
+    cpu.set_moments(True)
+    snaps, took = [], []
+    for i, k in enumerate(START):
+        snaps.append(cpu.render(w, h, k, mb, first_frame=1 if i == 0 else 0, want_accum=True)[1])
+        took.append(np.ones((h, w), bool))
+    n0 = cpu.counts(h, w)[0]
+    for k in KS:
+        cpu.render_adaptive(w, h, mb, samples=k, **DEFAULTS)
+        n = cpu.counts(h, w)[0]
+        snaps.append(cpu.get_state(h, w)[1])
+        took.append(n != n0)
+        n0 = n
+    var, M = cpu.variance(h, w, want_lum=True)
+    rvar, rM, rn, rJ = R.pixel_moments_ref(snaps, START + KS, took)
+    n, j = cpu.counts(h, w)
+    assert np.array_equal(n, rn) and np.array_equal(j, rJ)
+    assert len(np.unique(n)) >= 4  # pixels with different histories
+    scale = float(rM.mean())
+    e_m = float(np.max(np.abs(M - rM) / (scale + np.abs(rM))))
+    e_v = float(np.max(np.abs(var - rvar) / (scale + np.abs(rvar))))
+    print(f"scale {scale:.4f}: M {e_m:.3e}, var {e_v:.3e}")
+    assert scale > 0.05 and (rvar > 0).mean() > 0.05
+    assert e_m <= AD_BOUND_M
+    assert e_v <= AD_BOUND_VAR
+    cpu.set_moments(False)
+
+
+def test_thread_count_invariance(bwrt_lib):
+    scene = scenes.scene_07()
+    w, h, mb = 67, 45, 4
+    runs = []
+    for threads in (1, 3, 8):
+        with Renderer.cpu(threads, lib=bwrt_lib) as r:
+            runs.append(adaptive_sequence(r, scene, w, h, mb))
+    for other in runs[1:]:
+        assert other["stats"] == runs[0]["stats"]
+        for key in ("n", "j", "rng", "accum", "rgba", "color", "var", "lum"):
+            assert np.array_equal(other[key], runs[0][key], equal_nan=True), key
+
+
+def test_counts_follow_the_calls(cpu):
+    scene = scenes.scene_07()
+    w, h, mb = 67, 45, 4
+    start(cpu, scene, w, h, mb)
+    n, j = cpu.counts(h, w)
+    assert (n == 8).all() and (j == 4).all()  # uniform: the context's counts
+    frames, batches = n.astype(np.int64), j.astype(np.int64)
+    for k in (2, 5, 1):
+        _, st = cpu.render_adaptive(w, h, mb, samples=k, **DEFAULTS)
+        n, j = cpu.counts(h, w)
+        took = n != frames
+        assert st["selected"] == took.sum()
+        frames += k * took
+        batches += took
+        assert np.array_equal(n, frames) and np.array_equal(j, batches)
+        assert st["frames_total"] == frames.sum()
+        assert cpu.adaptive_stats()["selected"] == st["selected"]
+    assert cpu.frame_counter == 9 and cpu.moments_batches == 4
+    cpu.set_moments(False)
+
+
+def mae(a, b):
+    return float(np.abs(a[..., :3].astype(np.int32) - b[..., :3].astype(np.int32)).mean())
+
+
+def test_quality_ordering(bwrt_lib):
+    """The 160x90 sweep case: rounds of the defaults from the 4 x 2 start until
+    the mean count reaches 32 beat the uniform 32-frame render against a
+    2048-frame render (emulated before the implementation: 31.7 against 36.5
+    in 8-bit units).  Only the ordering is asserted."""
+    scene = scenes.scene_07()
+    w, h, mb = 160, 90, 4
+    with Renderer.cpu(0, lib=bwrt_lib) as r:
+        r.set_scene(scene)
+        uniform = None
+        for first in (1, 0):  # 32 frames, then 2016 more
+            truth = r.render(w, h, 32 if first else 2016, mb, first_frame=first)
+            if first:
+                uniform = truth
+        start(r, scene, w, h, mb)
+        mean = 8.0
+        while mean < 32.0:
+            img, st = r.render_adaptive(w, h, mb)
+            assert st["selected"] > 0
+            mean = st["frames_total"] / (w * h)
+    e_a, e_u = mae(img, truth), mae(uniform, truth)
+    print(f"mean count {mean:.1f}: adaptive MAE {e_a:.2f}, uniform 32 frames {e_u:.2f}")
+    assert mean < 40.0
+    assert e_a < e_u
+
+
+# ---- CLI ---------------------------------------------------------------------------
+
+def test_cli_adaptive(tmp_path):
+    out, prefix = tmp_path / "img.ppm", tmp_path / "f"
+    base = [CLI, "--cpu", "2", "--width", "64", "--height", "36", "--frames", "24", "--frames-per-call", "2",
+            "--max-bounces", "3"]
+    res = subprocess.run(base + ["--out", str(out), "--adaptive", "0.1", "--aov", str(prefix)], check=True,
+                         capture_output=True, text=True)
+    line = [ln for ln in res.stdout.splitlines() if ln.startswith("adaptive:")]
+    assert line and "frames per pixel" in line[0] and "selected" in line[0]
+    mean = float(line[0].split()[2])
+    assert 8.0 < mean < 24.0  # fewer frames than the uniform loop spends
+    assert (tmp_path / "f_count.ppm").stat().st_size == out.stat().st_size
+    res = subprocess.run(base + ["--adaptive", "0.1", "--adaptive-after", "6", "--adaptive-radius", "1",
+                                 "--adaptive-floor", "0.02", "--min-frames", "14", "--max-frames", "20"],
+                         check=True, capture_output=True, text=True)
+    mean = float([ln for ln in res.stdout.splitlines() if ln.startswith("adaptive:")][0].split()[2])
+    assert 14.0 <= mean <= 20.0
+    for bad in (["--denoise"], ["--denoise-var"], ["--temporal"], ["--precision", "fast"]):
+        res = subprocess.run(base + ["--adaptive", "0.1"] + bad, capture_output=True, text=True)
+        assert res.returncode == 2 and "--adaptive cannot be combined" in res.stderr, bad
