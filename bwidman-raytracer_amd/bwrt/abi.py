@@ -184,6 +184,8 @@ def _proto(lib):
         "rt_get_moments": (C.c_int, [vp]),
         "rt_moments_batches": (C.c_int, [vp]),
         "rt_get_variance": (C.c_int, [vp, vp, vp]),
+        "rt_set_adaptive_filters": (C.c_int, [vp, C.c_int]),
+        "rt_get_adaptive_filters": (C.c_int, [vp]),
         "rt_adaptive_params_default": (AdaptiveParams, []),
         "rt_render_adaptive": (C.c_int, [vp, P(AdaptiveParams), C.c_int, vp, vp, P(AdaptiveStats)]),
         "rt_render_adaptive_device": (C.c_int, [vp, P(AdaptiveParams), C.c_int, vp, vp]),

@@ -405,6 +405,16 @@ class Renderer:
         self._check(self.lib.rt_get_counts(self.ctx, n.ctypes.data, j.ctypes.data))
         return n, j
 
+    def set_adaptive_filters(self, enable: bool = True):
+        """rt_set_adaptive_filters: let denoise, denoise_var and temporal (and
+        their _device forms) run on a non-uniform accumulation, each pixel
+        with its own frame count; off (the default) they refuse it."""
+        self._check(self.lib.rt_set_adaptive_filters(self.ctx, int(bool(enable))))
+
+    @property
+    def adaptive_filters(self) -> bool:
+        return bool(self.lib.rt_get_adaptive_filters(self.ctx))
+
     # -- checkpoint / resume -----------------------------------------------
     def get_state(self, rows, width):
         rng = np.empty((6, rows, width), dtype=np.uint32)

@@ -23,6 +23,16 @@ RT_HD f3 at_c0(const float* accum, long npix, float inv, long q) {
 }
 RT_HD f3 at_c0(const rt_at_frame& F, long q) { return at_c0(F.accum, (long)F.width * F.height, F.inv, q); }
 
+// Non-uniform state (rt_render_adaptive; cnt[q] = {n_q, J_q}, every n_q >= 2):
+// the input colour of every pass is pixel q's own mean,
+//   inv_q = rt_div(1.0f, (float)n_q);   c0_q = inv_q * frameSum_q  per plane
+// (rt_adaptive.h ad_resolve's colour), wherever the uniform passes read
+// inv * frameSum of a centre or a tap.  With all n_q equal it is at_c0.
+RT_HD float at_inv_cnt(const uint2* cnt, long q) { return rt_div(1.0f, (float)cnt[q].x); }
+RT_HD f3 at_c0_cnt(const float* accum, long npix, const uint2* cnt, long q) {
+    return at_c0(accum, npix, at_inv_cnt(cnt, q), q);
+}
+
 // the geometry terms of a tap: en = dot(n_q - n_p, n_q - n_p) in,
 // ex = (pd pd) ip with pd = dot(n_p, P_q - P_p)
 RT_HD void at_geom(const rt_at_frame& F, f3 np, f3 Pp, f3 nq, f3 Pq, float& en, float& ex) {

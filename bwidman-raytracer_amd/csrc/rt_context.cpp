@@ -447,6 +447,16 @@ int rt_set_kernel_timing(rt_context* c, int enable) {
     return RT_OK;
 }
 
+// Opt-in: the post-render passes on a non-uniform accumulation (rt_post.cpp
+// full_frame_check reads it; it has no other effect)
+int rt_set_adaptive_filters(rt_context* c, int enable) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    c->ad_filters = enable != 0;
+    return RT_OK;
+}
+
+int rt_get_adaptive_filters(const rt_context* c) { return c && c->ad_filters ? 1 : 0; }
+
 int rt_shard_rows(int height, int row_offset, int row_stride) {
     return shard_rows(height, row_offset, row_stride == 0 ? 1 : row_stride);
 }

@@ -286,6 +286,12 @@ struct rt_context {
     // list and {list_n, frame total}.  ad_ev: select / render / update +
     // resolve brackets of the last call, recorded only with kernel timing on.
     bool ad_live = false;
+    // rt_set_adaptive_filters: rt_denoise*, rt_denoise_var* and rt_temporal*
+    // accept the non-uniform state and take every pixel's own count (the
+    // count-aware forms in rt_atrous.h, rt_denoise.h, rt_denoise_var.h,
+    // rt_temporal.h); off, they refuse it.  A uniform accumulation runs the
+    // same kernels either way.
+    bool ad_filters = false;
     unsigned long long ad_max_n = 0;
     int ad_kernel = 0;  // BWRT_ADAPTIVE_KERNEL: 1 simple, 2 queued, 0 = launch policy
     Buf ad_cnt, ad_rows, ad_mask, ad_pop, ad_list, ad_stat, ad_color;

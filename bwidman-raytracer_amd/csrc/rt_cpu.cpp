@@ -303,8 +303,11 @@ void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4
 // One filter level (L.f.step >= 1) or, with L.f.step == 0, the conversion pass
 void rt_cpu_denoise_level(const rt_dn_level& L, int threads) {
     parallel_pixels(L.f.width, L.f.height, threads, [&](int x, int y, long p) {
+        const bool cnt = L.cnt != nullptr;  // the non-uniform state: every pixel's own count
         if (L.f.step == 0)
-            at_store(L.f, p, DnFilter<true>::texel(L, p));
+            at_store(L.f, p, cnt ? DnFilterCnt::texel(L, p) : DnFilter<true>::texel(L, p));
+        else if (L.first && cnt)
+            at_run_direct<DnFilterCnt>(L, x, y);
         else if (L.first)
             at_run_direct<DnFilter<true>>(L, x, y);
         else
@@ -314,7 +317,12 @@ void rt_cpu_denoise_level(const rt_dn_level& L, int threads) {
 
 // The temporal reprojection pass (rt_temporal.h), on the same pool
 void rt_cpu_temporal(const rt_tp_args& T, int threads) {
-    parallel_pixels(T.width, T.height, threads, [&](int x, int y, long) { tp_run_pixel(T, x, y); });
+    parallel_pixels(T.width, T.height, threads, [&](int x, int y, long) {
+        if (T.cnt)
+            tp_run_pixel_cnt(T, x, y);
+        else
+            tp_run_pixel(T, x, y);
+    });
 }
 
 // The luminance moment update of one render call (rt_moments.h), on the same pool
@@ -327,7 +335,7 @@ void rt_cpu_moments(const rt_mom_args& A, int threads) {
 void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads) {
     parallel_pixels(A.f.width, A.f.height, threads, [&](int x, int y, long p) {
         if (stage == 0)
-            at_store(A.f, p, dv_input(A, x, y));
+            at_store(A.f, p, A.cnt ? dv_input_cnt(A, x, y) : dv_input(A, x, y));
         else if (stage == 1)
             A.rs[p] = dv_sigma(A, x, y);
         else

@@ -18,6 +18,10 @@
 //   sum_w += w;  sum_c += w c_q.
 // Result sum_c / sum_w when sum_w > 0, else c_p (a non-finite centre passes
 // through unchanged).
+//
+// Level 0 of a call on the accumulation reads c_q = inv * frameSum_q; in the
+// non-uniform state (L.cnt non-null) c_q = c0_q with the pixel's own count
+// (rt_atrous.h).
 #pragma once
 #include "rt_atrous.h"
 
@@ -25,7 +29,7 @@ namespace {
 
 // the centre and the sums of one pixel; operator() is steps 4-10 of one tap
 struct DnTap {
-    const rt_dn_level& L;
+    const rt_dn_uniform& L;
     f3 cp, np, Pp;
     float w;
     f3 c;
@@ -47,7 +51,7 @@ struct DnTap {
 
 // The filtered colour of pixel (x, y) (fetch: rt_atrous.h)
 template <class Fetch>
-RT_HD f3 dn_pixel(const rt_dn_level& L, int x, int y, const Fetch& fetch) {
+RT_HD f3 dn_pixel(const rt_dn_uniform& L, int x, int y, const Fetch& fetch) {
     float4 cp, ap, bp;
     fetch(0, 0, x, y, cp, ap, bp);
     DnTap t{L, mk(cp.x, cp.y, cp.z), mk(ap.x, ap.y, ap.z), mk(bp.x, bp.y, bp.z), 0.0f, mk(0.0f, 0.0f, 0.0f)};
@@ -60,16 +64,32 @@ RT_HD f3 dn_pixel(const rt_dn_level& L, int x, int y, const Fetch& fetch) {
 // colour reads inv * frameSum
 template <bool FIRST>
 struct DnFilter {
-    using Args = rt_dn_level;
-    static RT_HD float4 texel(const rt_dn_level& L, long q) {
+    using Args = rt_dn_uniform;
+    static RT_HD float4 texel(const rt_dn_uniform& L, long q) {
         if (!FIRST) return L.f.src[q];  // (.w: not read; rt_temporal's source carries the history length there)
         const f3 c = at_c0(L.f, q);
         return make_float4(c.x, c.y, c.z, 0.0f);
     }
     template <class Fetch>
-    static RT_HD void run(const rt_dn_level& L, int x, int y, const Fetch& fetch) {
+    static RT_HD void run(const rt_dn_uniform& L, int x, int y, const Fetch& fetch) {
         const f3 c = dn_pixel(L, x, y, fetch);
         at_store(L.f, (long)y * L.f.width + x, make_float4(c.x, c.y, c.z, 0.0f));
+    }
+};
+
+// Level 0 (and the conversion pass) in the non-uniform state: the colour of
+// every pixel, centre or tap, is its own mean c0_q (rt_atrous.h at_c0_cnt);
+// everything behind the colour word is DnFilter's.  The later levels read
+// colour buffers: DnFilter<false> as ever.
+struct DnFilterCnt {
+    using Args = rt_dn_level;
+    static RT_HD float4 texel(const rt_dn_level& L, long q) {
+        const f3 c = at_c0_cnt(L.f.accum, (long)L.f.width * L.f.height, L.cnt, q);
+        return make_float4(c.x, c.y, c.z, 0.0f);
+    }
+    template <class Fetch>
+    static RT_HD void run(const rt_dn_level& L, int x, int y, const Fetch& fetch) {
+        DnFilter<true>::run(L, x, y, fetch);
     }
 };
 

@@ -18,6 +18,15 @@
 //   l = lum(c_q);  s0 += wn;  s1 += wn l;  s2 += wn (l l)
 // v0 = fmaxf(s2 / s0 - m1 m1, 0), m1 = s1 / s0; 0 unless s0 > 0.
 //
+// Input stage in the non-uniform state (A.cnt non-null, cnt[p] = {n_p, J_p};
+// rt_render_adaptive): the moments of every pixel are current for its own n_p,
+// so the choice is per pixel and one frame mixes both sources.  c0_q is the
+// pixel's own mean (rt_atrous.h at_c0_cnt) for the centre and for every tap of
+// the window.  Tracked (J_p >= min_batches): v0 = ad_var(M2_p, n_p, J_p)
+// (rt_adaptive.h, the selection's and rt_get_variance's expression).  Spatial
+// (otherwise): the estimate above over the count-aware c0_q.  With all counts
+// equal both are the uniform stage's values.
+//
 // Sigma pass, before every level: g = the 3 x 3 unit-step Gaussian of v (1/4
 // centre, 1/8 edges, 1/16 corners; dy outer, dx inner) over the in-image taps
 // with finite v, divided by the sum of their weights;
@@ -33,17 +42,16 @@
 // non-finite colour channel or variance, and a pixel with sum_w not > 0, pass
 // through unchanged.
 #pragma once
+#include "rt_adaptive.h"
 #include "rt_denoise.h"
 #include "rt_moments.h"
 
 namespace {
 
-// Input stage of pixel p = (x, y): {c0, v0}
-RT_HD float4 dv_input(const rt_dv_args& A, int x, int y) {
-    const rt_at_frame& F = A.f;
+// The spatial estimate v0 of pixel p = (x, y); c0(q) is the input colour of tap q
+template <class C0>
+RT_HD float dv_spatial(const rt_at_frame& F, int x, int y, const C0& c0) {
     const long p = (long)y * F.width + x;
-    const f3 c = at_c0(F, p);
-    if (A.tracked) return make_float4(c.x, c.y, c.z, A.mom[p].y * A.rd);
     const float4 ap = F.ga[p], bp = F.gb[p];
     const f3 np = mk(ap.x, ap.y, ap.z), Pp = mk(bp.x, bp.y, bp.z);
     const bool missp = rt_f2i(ap.w) < 0;
@@ -57,7 +65,7 @@ RT_HD float4 dv_input(const rt_dv_args& A, int x, int y) {
             const long q = (long)qy * F.width + qx;
             const float4 aq = F.ga[q];
             if ((rt_f2i(aq.w) < 0) != missp) continue;
-            const f3 cq = at_c0(F, q);
+            const f3 cq = c0(q);
             if (!at_finite(cq.x) || !at_finite(cq.y) || !at_finite(cq.z)) continue;
             const float4 bq = F.gb[q];
             float en, ex;
@@ -74,11 +82,31 @@ RT_HD float4 dv_input(const rt_dv_args& A, int x, int y) {
         const float m1 = rt_div(s1, s0);
         v = fmaxf(rt_div(s2, s0) - m1 * m1, 0.0f);
     }
-    return make_float4(c.x, c.y, c.z, v);
+    return v;
+}
+
+// Input stage of pixel p = (x, y): {c0, v0}
+RT_HD float4 dv_input(const rt_dv_uniform& A, int x, int y) {
+    const rt_at_frame& F = A.f;
+    const long p = (long)y * F.width + x;
+    const f3 c = at_c0(F, p);
+    if (A.tracked) return make_float4(c.x, c.y, c.z, A.mom[p].y * A.rd);
+    return make_float4(c.x, c.y, c.z, dv_spatial(F, x, y, [&](long q) { return at_c0(F, q); }));
+}
+
+// The same in the non-uniform state: the pixel's own choice between the two
+// sources, every colour with its pixel's count
+RT_HD float4 dv_input_cnt(const rt_dv_args& A, int x, int y) {
+    const rt_at_frame& F = A.f;
+    const long npix = (long)F.width * F.height, p = (long)y * F.width + x;
+    const uint2 cn = A.cnt[p];
+    const f3 c = at_c0(F.accum, npix, rt_div(1.0f, (float)cn.x), p);
+    if (cn.y >= A.min_batches) return make_float4(c.x, c.y, c.z, ad_var(A.mom[p].y, cn.x, cn.y));
+    return make_float4(c.x, c.y, c.z, dv_spatial(F, x, y, [&](long q) { return at_c0_cnt(F.accum, npix, A.cnt, q); }));
 }
 
 // Sigma pass of pixel (x, y): the reciprocal luminance sigma from src's .w
-RT_HD float dv_sigma(const rt_dv_args& A, int x, int y) {
+RT_HD float dv_sigma(const rt_dv_uniform& A, int x, int y) {
     const rt_at_frame& F = A.f;
     float sv = 0.0f, sw = 0.0f;
     for (int dy = -1; dy <= 1; dy++) {
@@ -125,7 +153,7 @@ struct DvTap {
 
 // The filtered {colour, variance} of pixel (x, y) (fetch: rt_atrous.h)
 template <class Fetch>
-RT_HD float4 dv_pixel(const rt_dv_args& A, int x, int y, const Fetch& fetch) {
+RT_HD float4 dv_pixel(const rt_dv_uniform& A, int x, int y, const Fetch& fetch) {
     float4 cp, ap, bp;
     fetch(0, 0, x, y, cp, ap, bp);
     if (!at_finite(cp.x) || !at_finite(cp.y) || !at_finite(cp.z) || !at_finite(cp.w)) return cp;
@@ -138,10 +166,10 @@ RT_HD float4 dv_pixel(const rt_dv_args& A, int x, int y, const Fetch& fetch) {
 
 // the filter's level as rt_atrous.h takes it
 struct DvFilter {
-    using Args = rt_dv_args;
-    static RT_HD float4 texel(const rt_dv_args& A, long q) { return A.f.src[q]; }
+    using Args = rt_dv_uniform;
+    static RT_HD float4 texel(const rt_dv_uniform& A, long q) { return A.f.src[q]; }
     template <class Fetch>
-    static RT_HD void run(const rt_dv_args& A, int x, int y, const Fetch& fetch) {
+    static RT_HD void run(const rt_dv_uniform& A, int x, int y, const Fetch& fetch) {
         at_store(A.f, (long)y * A.f.width + x, dv_pixel(A, x, y, fetch));
     }
 };

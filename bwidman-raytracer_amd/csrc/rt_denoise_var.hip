@@ -22,18 +22,28 @@
 namespace {
 
 struct DvOp {  // a one-lane-per-pixel pass over the frame
-    using Args = rt_dv_args;
-    static RT_HD int2 size(const rt_dv_args& A) { return make_int2(A.f.width, A.f.height); }
+    using Args = rt_dv_uniform;
+    static RT_HD int2 size(const rt_dv_uniform& A) { return make_int2(A.f.width, A.f.height); }
 };
 
 struct DvInput : DvOp {
-    static __device__ __forceinline__ void run(const rt_dv_args& A, int x, int y) {
+    static __device__ __forceinline__ void run(const rt_dv_uniform& A, int x, int y) {
         at_store(A.f, (long)y * A.f.width + x, dv_input(A, x, y));
     }
 };
 
-struct DvSigma : DvOp {
+// the input stage in the non-uniform state: a lane branches on its own J_p
+// between the tracked source (count, frameSum, moments of the pixel alone) and
+// the 7 x 7 window, whose taps read their counts beside their frameSum
+struct DvInputCnt : DvOp {
+    using Args = rt_dv_args;
     static __device__ __forceinline__ void run(const rt_dv_args& A, int x, int y) {
+        at_store(A.f, (long)y * A.f.width + x, dv_input_cnt(A, x, y));
+    }
+};
+
+struct DvSigma : DvOp {
+    static __device__ __forceinline__ void run(const rt_dv_uniform& A, int x, int y) {
         A.rs[(long)y * A.f.width + x] = dv_sigma(A, x, y);
     }
 };
@@ -46,6 +56,7 @@ hipError_t rt_launch_denoise_var(const rt_dv_args& A, int stage, bool tiled, hip
     if (stage < 0 || stage > 2) return hipErrorInvalidValue;
     if (stage == 2 && (A.f.step < 1 || A.f.step > 32)) return hipErrorInvalidValue;
     if (stage == 2 && tiled) return at_launch_tiled<DvFilter>(A, stream);
+    if (stage == 0 && A.cnt) return at_launch_pixels<DvInputCnt>(A, stream);
     return stage == 0   ? at_launch_pixels<DvInput>(A, stream)
            : stage == 1 ? at_launch_pixels<DvSigma>(A, stream)
                         : at_launch_pixels<AtDirect<DvFilter>>(A, stream);

@@ -186,17 +186,27 @@ struct rt_at_frame {
     const float4* gb;    //        {P.xyz, depth}
 };
 
+// The argument structs of the post-render passes come in two parts.  The
+// `_uniform` base is what the kernels of a uniform accumulation take (by value,
+// with the tile count behind it: their kernel arguments keep their offsets).
+// The full struct appends the per-pixel counts {n_p, J_p} of the non-uniform
+// state (rt_render_adaptive), which only the count-aware kernels take; null =
+// uniform.
+
 // One level of the denoiser (rt_denoise.h): dst holds {r, g, b, 0}.
-struct rt_dn_level {
+struct rt_dn_uniform {
     rt_at_frame f;
     int first;           // colour in = inv * frameSum (tone_map's first step), else src
     float ic;            // 1 / sigma^2 of the colour term (this level's)
+};
+struct rt_dn_level : rt_dn_uniform {
+    const uint2* cnt;    // `first` reads rt_div(1, n_q) * frameSum_q
 };
 
 // One temporal reprojection pass (rt_temporal.h) over a full width x height
 // frame: the current view's frameSum and guides, the history view's colour,
 // guides and camera, and the pending buffers of the current view.
-struct rt_tp_args {
+struct rt_tp_uniform {
     int width, height;
     int has_history;     // 0: every pixel takes the no-history path (h_* are not read)
     float n;             // (float)(frame counter - 1)
@@ -216,6 +226,9 @@ struct rt_tp_args {
     float4* p_gb;
     unsigned* rgba;      // tone_map(out, 1) when non-null
 };
+struct rt_tp_args : rt_tp_uniform {
+    const uint2* cnt;    // (float)n_p and rt_div(1, (float)n_p) replace n and inv
+};
 
 // One luminance-moment update (rt_moments.h) over the npix pixels of the
 // context's shard: the batch of k frames first .. first + k - 1 that a render
@@ -234,13 +247,19 @@ struct rt_mom_args {
 // One pass of the variance-guided filter (rt_denoise_var.h): the input stage
 // (reads accum, writes dst), a sigma pass (reads src) or a level; src and dst
 // hold {colour, variance}.
-struct rt_dv_args {
+struct rt_dv_uniform {
     rt_at_frame f;
     int tracked;         // input stage: v0 from the tracked moments, else the spatial estimate
     float rd;            // tracked: 1 / ((J - 1) n)
     float sigma_lum;     // sigma pass
     const float2* mom;   // input stage, tracked: {M, M2}
     float* rs;           // reciprocal luminance sigma: the sigma pass writes it, the level reads its centre
+};
+struct rt_dv_args : rt_dv_uniform {
+    // input stage (`tracked` and rd are not read): pixel p is tracked when
+    // J_p >= min_batches, and every tap's colour takes its own count
+    unsigned min_batches;
+    const uint2* cnt;
 };
 
 // The list of an adaptive render (rt_adaptive.h): what the list render kernels

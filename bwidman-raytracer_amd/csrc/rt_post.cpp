@@ -75,11 +75,18 @@ int full_frame_check(rt_context* c, const char* who) {
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the context holds a row shard (offset %d, stride %d): %s needs a full frame", c->row_offset,
                     c->row_stride, who);
-    if (c->ad_live)
+    if (c->ad_live && !c->ad_filters)
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the accumulation is non-uniform (rt_render_adaptive): %s takes one frame count for all pixels", who);
     return RT_OK;
 }
+
+// The counts {n_p, J_p} a pass takes in the non-uniform state (then every
+// pixel's colour is rt_div(1, n_p) * frameSum_p, rt_atrous.h); null = uniform.
+// The adaptive call that wrote them ran inside the render pass, so
+// prepare_frame's order_after_all has ordered the stream behind its update and
+// resolve passes, whatever stream it ran on.
+const uint2* frame_counts(const rt_context* c) { return c->ad_live ? c->ad_cnt.as<uint2>() : nullptr; }
 
 // iterations and sigmas of a filter (`term`: what its first sigma weighs)
 int filter_check(rt_context* c, int iterations, const char* term, float s0, float sn, float sp) {
@@ -171,6 +178,7 @@ int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_t s, un
     rt_dn_level L;
     std::memset(&L, 0, sizeof L);
     fill_frame(c, dp->sigma_normal, dp->sigma_plane, L.f);
+    L.cnt = frame_counts(c);  // (read where `first` is: level 0 and the conversion pass)
     float4* col[2] = {c->dn_col[0].as<float4>(), c->dn_col[1].as<float4>()};
     HIP_TRY(c, c->denoise.begin(s, true));
     const int levels = dp->iterations;
@@ -215,6 +223,14 @@ int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream
     A.tracked = c->mom_live && c->mom_next == c->frame && c->mom_batches >= (unsigned)dp->min_batches;
     if (A.tracked) {
         A.rd = 1.0f / ((float)(c->mom_batches - 1u) * (float)(c->frame - 1u));
+        A.mom = c->mom_m.as<float2>();
+    }
+    // non-uniform: the context's frame and batch counts are the uniform base,
+    // but every pixel's moments are current for its own n_p (the state lives
+    // only while tracking does): the choice is per pixel, J_p >= min_batches
+    if ((A.cnt = frame_counts(c))) {
+        A.tracked = 0;
+        A.min_batches = (unsigned)dp->min_batches;
         A.mom = c->mom_m.as<float2>();
     }
     A.rs = c->dn_rs.as<float>();
@@ -310,6 +326,7 @@ int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_
     T.p_ga = P.ga.as<float4>();
     T.p_gb = P.gb.as<float4>();
     T.rgba = filter ? nullptr : rgba;  // the filter's last level writes it otherwise
+    T.cnt = frame_counts(c);           // non-uniform: they replace n and inv
     HIP_TRY(c, c->temporal.begin(s, true));
     if (c->cpu)
         rt_cpu_temporal(T, c->threads);

@@ -23,6 +23,12 @@
 //       a = n / (len_h + n);  out = hist + a (c_new - hist);  len_out = len_h + n.
 // Stored: pending colour {out, len_out}, a copy of the two guide words, and
 // (optionally) tone_map(out, 1).
+//
+// Non-uniform state (T.cnt non-null, cnt[p] = {n_p, J_p}; rt_render_adaptive):
+// n and inv above are the pixel's own, n = (float)n_p, inv = rt_div(1, n), so
+// c_new is the pixel's mean (rt_atrous.h), len_out = n_p without usable history
+// and a = n_p / (len_h + n_p), len_out = len_h + n_p with one.  A history the
+// pass leaves then carries per-pixel lengths; nothing else changes.
 #pragma once
 #include "rt_atrous.h"
 
@@ -34,10 +40,11 @@ struct TpOut {
 };
 
 // The reprojected colour of pixel p = y * width + x whose guide words are a, b
-RT_HD TpOut tp_pixel(const rt_tp_args& T, int x, int y, long p, float4 a, float4 b) {
+// and which holds n frames (inv = 1 / n)
+RT_HD TpOut tp_pixel(const rt_tp_uniform& T, int x, int y, long p, float4 a, float4 b, float n, float inv) {
     TpOut o;
-    o.c = at_c0(T.accum, (long)T.width * T.height, T.inv, p);
-    o.len = T.n;
+    o.c = at_c0(T.accum, (long)T.width * T.height, inv, p);
+    o.len = n;
     const int prim = rt_f2i(a.w);
     if (!T.has_history || prim < 0) return o;
     if (!(at_finite(o.c.x) && at_finite(o.c.y) && at_finite(o.c.z))) return o;
@@ -87,22 +94,28 @@ RT_HD TpOut tp_pixel(const rt_tp_args& T, int x, int y, long p, float4 a, float4
     if (!(sw > 0.0f)) return o;
     const f3 hist = mk(rt_div(sc.x, sw), rt_div(sc.y, sw), rt_div(sc.z, sw));
     const float len_h = fminf(rt_div(sl, sw), T.max_history);
-    const float al = rt_div(T.n, len_h + T.n);
+    const float al = rt_div(n, len_h + n);
     o.c = mk(hist.x + al * (o.c.x - hist.x), hist.y + al * (o.c.y - hist.y), hist.z + al * (o.c.z - hist.z));
-    o.len = len_h + T.n;
+    o.len = len_h + n;
     return o;
 }
 
 // One pixel of the pass: reproject, then store the pending history of the
 // current view (colour + length, the guide copy) and the RGBA
-RT_HD void tp_run_pixel(const rt_tp_args& T, int x, int y) {
+RT_HD void tp_run_pixel(const rt_tp_uniform& T, int x, int y, float n, float inv) {
     const long p = (long)y * T.width + x;
     const float4 a = T.ga[p], b = T.gb[p];
-    const TpOut o = tp_pixel(T, x, y, p, a, b);
+    const TpOut o = tp_pixel(T, x, y, p, a, b, n, inv);
     T.p_col[p] = make_float4(o.c.x, o.c.y, o.c.z, o.len);
     T.p_ga[p] = a;
     T.p_gb[p] = b;
     if (T.rgba) T.rgba[p] = tone_map(o.c.x, o.c.y, o.c.z, 1u);
+}
+RT_HD void tp_run_pixel(const rt_tp_uniform& T, int x, int y) { tp_run_pixel(T, x, y, T.n, T.inv); }
+// the same in the non-uniform state: the pixel's own count
+RT_HD void tp_run_pixel_cnt(const rt_tp_args& T, int x, int y) {
+    const float nf = (float)T.cnt[(long)y * T.width + x].x;
+    tp_run_pixel(T, x, y, nf, rt_div(1.0f, nf));
 }
 
 }  // namespace

@@ -20,13 +20,20 @@
 namespace {
 
 struct TpPixel {
+    using Args = rt_tp_uniform;
+    static RT_HD int2 size(const rt_tp_uniform& T) { return make_int2(T.width, T.height); }
+    static __device__ __forceinline__ void run(const rt_tp_uniform& T, int x, int y) { tp_run_pixel(T, x, y); }
+};
+
+// the non-uniform state: the lane's count (8 bytes) in place of the uniform n, inv
+struct TpPixelCnt : TpPixel {
     using Args = rt_tp_args;
-    static RT_HD int2 size(const rt_tp_args& T) { return make_int2(T.width, T.height); }
-    static __device__ __forceinline__ void run(const rt_tp_args& T, int x, int y) { tp_run_pixel(T, x, y); }
+    static __device__ __forceinline__ void run(const rt_tp_args& T, int x, int y) { tp_run_pixel_cnt(T, x, y); }
 };
 
 }  // namespace
 
 hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream) {
+    if (T.cnt) return at_launch_pixels<TpPixelCnt>(T, stream);
     return at_launch_pixels<TpPixel>(T, stream);
 }

@@ -59,6 +59,9 @@
 // frames per pixel and the last call's selected share; --aov PREFIX also
 // writes PREFIX_count (n_p over the largest n_p).  It cannot be combined with
 // --denoise, --denoise-var, --temporal, --precision fast or --gpus above 1.
+// --adaptive-filters (rt_set_adaptive_filters) lifts that for --denoise,
+// --denoise-var and --temporal: the passes then take every pixel's own frame
+// count (--precision fast and --gpus above 1 stay refused).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -87,7 +90,7 @@ static const char* kUsage =
     "                   [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]\n"
     "                   [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]\n"
     "                   [--adaptive TOL] [--adaptive-after 4] [--adaptive-radius R] [--adaptive-floor F]\n"
-    "                   [--min-frames N] [--max-frames N]\n";
+    "                   [--min-frames N] [--max-frames N] [--adaptive-filters]\n";
 
 struct KeyStep {
     unsigned keys;
@@ -153,7 +156,7 @@ int main(int argc, char** argv) {
     std::string aov;
     bool moments = false, denoise_var = false;
     rt_denoise_var_params dv = rt_denoise_var_params_default();
-    bool adaptive = false;
+    bool adaptive = false, adaptive_filters = false;
     int adaptive_after = 4;
     rt_adaptive_params ad = rt_adaptive_params_default();
     for (int i = 1; i < argc; i++) {
@@ -217,6 +220,7 @@ int main(int argc, char** argv) {
             adaptive = moments = true;
             ad.tolerance = (float)std::atof(next());
         }
+        else if (!std::strcmp(argv[i], "--adaptive-filters")) adaptive_filters = true;
         else if (!std::strcmp(argv[i], "--adaptive-after")) adaptive_after = std::atoi(next());
         else if (!std::strcmp(argv[i], "--adaptive-radius")) ad.radius = std::atoi(next());
         else if (!std::strcmp(argv[i], "--adaptive-floor")) ad.lum_floor = (float)std::atof(next());
@@ -231,7 +235,8 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--denoise and --denoise-var cannot be combined: one filter writes the frame\n");
         return 2;
     }
-    if (adaptive && (denoise || denoise_var || temporal || precision == RT_PRECISION_REFERENCE_FAST || gpus > 1)) {
+    if (adaptive && (((denoise || denoise_var || temporal) && !adaptive_filters) ||
+                     precision == RT_PRECISION_REFERENCE_FAST || gpus > 1)) {
         std::fprintf(stderr,
                      "--adaptive cannot be combined with --denoise, --denoise-var, --temporal, --precision fast or "
                      "--gpus above 1: the filters and the fast mode take one frame count for all pixels\n");
@@ -304,6 +309,7 @@ int main(int argc, char** argv) {
         if ((rc = rt_set_max_bounces(ctxs[g], max_bounces))) return die(ctxs[g], rc, "rt_set_max_bounces");
         if ((rc = rt_set_background(ctxs[g], bg[0], bg[1], bg[2]))) return die(ctxs[g], rc, "rt_set_background");
         if (moments && (rc = rt_set_moments(ctxs[g], 1))) return die(ctxs[g], rc, "rt_set_moments");
+        if (adaptive_filters && (rc = rt_set_adaptive_filters(ctxs[g], 1))) return die(ctxs[g], rc, "rt_set_adaptive_filters");
     }
     rt_context* ctx = ctxs[0];
     std::vector<uint8_t> rgba((size_t)width * height * 4);
@@ -379,7 +385,10 @@ int main(int argc, char** argv) {
     if (denoise_var) {
         const int batches = rt_moments_batches(ctx);
         if ((rc = rt_denoise_var(ctx, &dv, rgba.data(), nullptr, nullptr))) return die(ctx, rc, "rt_denoise_var");
-        if (batches >= dv.min_batches)
+        if (adaptive && ast_valid)  // non-uniform: each pixel by its own batches
+            std::printf("denoise-var: %d levels, per-pixel variance source (tracked from %d batches), %.3f ms\n",
+                        dv.iterations, dv.min_batches, rt_last_denoise_var_ms(ctx));
+        else if (batches >= dv.min_batches)
             std::printf("denoise-var: %d levels, tracked variance of %d batches, %.3f ms\n", dv.iterations, batches,
                         rt_last_denoise_var_ms(ctx));
         else

@@ -632,9 +632,10 @@ RT_API float rt_last_denoise_var_ms(rt_context* ctx);
  * rt_set_scene, rt_init_rand (also the implicit one), rt_set_state or
  * rt_set_moments(ctx, 0) (after rt_reset_accumulation, rt_set_camera and a
  * moving rt_controls the next render starts at frame 1).  While non-uniform:
- *  - a uniform render that continues (first_frame 0 or any value but 1),
- *    rt_denoise*, rt_denoise_var*, rt_temporal* and rt_render_multi return
- *    RT_ERR_UNSUPPORTED (filters that weigh by the counts are future work);
+ *  - a uniform render that continues (first_frame 0 or any value but 1) and
+ *    rt_render_multi return RT_ERR_UNSUPPORTED;
+ *  - rt_denoise*, rt_denoise_var* and rt_temporal* return RT_ERR_UNSUPPORTED
+ *    unless rt_set_adaptive_filters() (below) is on;
  *  - rt_get_state and rt_render_aov work as ever; rt_get_variance uses each
  *    pixel's own J_p and n_p; rt_frame_counter and rt_moments_batches keep
  *    reporting the uniform base (adaptive calls do not advance them);
@@ -685,6 +686,29 @@ RT_API int rt_adaptive_last_stats(rt_context* ctx, rt_adaptive_stats* stats_out)
  * batches tracked.  In the uniform state every pixel reports the context's
  * (frame counter - 1, rt_moments_batches).  Synchronous. */
 RT_API int rt_get_counts(rt_context* ctx, uint32_t* frames_out, uint32_t* batches_out);
+
+/* Post-render passes on a non-uniform accumulation.  Off
+ * (the default) rt_denoise*, rt_denoise_var* and rt_temporal* refuse the
+ * non-uniform state as described above.  On, they accept it and take every
+ * pixel's own counts {n_p, J_p}:
+ *  - the input colour of every pass, centre or tap, is rt_div(1, n_p) *
+ *    frameSum_p, rt_render_adaptive's color_out (level 0 of rt_denoise and its
+ *    iterations-0 pass, the input stage of rt_denoise_var with every tap of its
+ *    7 x 7 window, rt_temporal's new colour);
+ *  - rt_denoise_var chooses its variance source per pixel: the tracked variance
+ *    M2_p / ((J_p - 1) n_p) (rt_get_variance's value) where J_p >= min_batches,
+ *    the spatial estimate elsewhere, so one frame may mix both;
+ *  - rt_temporal blends and counts with n_p: length n_p without usable history,
+ *    else a = n_p / (len + n_p) and length len + n_p; the history it leaves
+ *    carries per-pixel lengths.
+ * With all counts equal the results are those of the uniform passes bit for
+ * bit, and GPU and CPU contexts agree bit for bit.  No pass writes the
+ * accumulation, the counts or the moments.  The switch has no other effect: a
+ * uniform accumulation runs the same code whatever it says, and uniform renders
+ * that continue a non-uniform accumulation, rt_render_multi, row shards and
+ * RT_PRECISION_REFERENCE_FAST stay unsupported.  It may be changed at any time. */
+RT_API int rt_set_adaptive_filters(rt_context* ctx, int enable);
+RT_API int rt_get_adaptive_filters(const rt_context* ctx);
 
 RT_API const char* rt_error_string(int status);
 RT_API const char* rt_last_error(const rt_context* ctx);
