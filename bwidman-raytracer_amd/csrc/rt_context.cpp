@@ -69,6 +69,17 @@ int quiesce(rt_context* c) {
     return RT_OK;
 }
 
+// The last render (and the passes behind it), on whatever stream it ran,
+// then blocking copies
+int read_settled(rt_context* c, std::initializer_list<HostCopy> copies) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (const int rc = quiesce(c)) return rc;
+    for (const HostCopy& h : copies)
+        if (h.dst) HIP_TRY(c, hipMemcpy(h.dst, h.src, h.bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 // Renders continue each other's RNG / frameSum state, the denoiser and the
 // reprojection read frameSum and share the guides and colour buffers: work
 // of any of the three on stream s waits for the last of each that ran on
@@ -284,11 +295,8 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
     c->scene = std::move(cs);
     c->camera = s->camera;
     c->has_scene = true;
-    c->frame = 1;
-    c->ad_live = false;  // a non-uniform accumulation ends with its scene
-    c->order_stale = true;
-    c->sky_gen++;
-    c->new_view();
+    c->view_changed();
+    c->st.end_nonuniform();  // a non-uniform accumulation ends with its scene
     c->tp_has_hist = c->tp_has_pending = false;  // primitive ids change meaning
     return RT_OK;
 }
@@ -296,10 +304,7 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
 int rt_set_camera(rt_context* c, const rt_camera* cam) {
     if (!c || !cam) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
     c->camera = *cam;
-    c->frame = 1;  // Controls.cuh: any movement sets accumulatedFrames = 1
-    c->order_stale = true;
-    c->sky_gen++;
-    c->new_view();
+    c->view_changed();
     return RT_OK;
 }
 
@@ -406,22 +411,17 @@ int rt_apply_controls(rt_camera* cam, unsigned keys, float dt) {
 int rt_controls(rt_context* c, unsigned keys, float dt) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     const int flags = rt_apply_controls(&c->camera, keys, dt);
-    if (flags > 0 && (flags & RT_CONTROLS_MOVED)) {
-        c->frame = 1;  // accumulatedFrames = 1
-        c->order_stale = true;
-        c->sky_gen++;
-        c->new_view();
-    }
+    if (flags > 0 && (flags & RT_CONTROLS_MOVED)) c->view_changed();
     return flags;
 }
 
 int rt_reset_accumulation(rt_context* c) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    c->frame = 1;
+    c->st.restart();
     return RT_OK;
 }
 
-unsigned rt_frame_counter(const rt_context* c) { return c ? c->frame : 0u; }
+unsigned rt_frame_counter(const rt_context* c) { return c ? c->st.frame() : 0u; }
 
 int rt_set_max_bounces(rt_context* c, int mb) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
@@ -451,11 +451,11 @@ int rt_set_kernel_timing(rt_context* c, int enable) {
 // full_frame_check reads it; it has no other effect)
 int rt_set_adaptive_filters(rt_context* c, int enable) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    c->ad_filters = enable != 0;
+    c->st.set_filters(enable != 0);
     return RT_OK;
 }
 
-int rt_get_adaptive_filters(const rt_context* c) { return c && c->ad_filters ? 1 : 0; }
+int rt_get_adaptive_filters(const rt_context* c) { return c && c->st.filters() ? 1 : 0; }
 
 int rt_shard_rows(int height, int row_offset, int row_stride) {
     return shard_rows(height, row_offset, row_stride == 0 ? 1 : row_stride);
@@ -468,7 +468,7 @@ int rt_init_rand(rt_context* c, int width, int height, int row_offset, int row_s
     const int rows = shard_rows(height, row_offset, row_stride);
     const size_t npix = (size_t)rows * width;
     c->new_view();  // the guides are those of one frame shape
-    c->mom_drop();  // the moments are those of one shard
+    c->st.end_tracking();  // the moments are those of one shard
     if (width != c->tp_w || height != c->tp_h) c->tp_has_hist = c->tp_has_pending = false;
     if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
     int rc = quiesce(c);  // a render on a caller's stream may still use the state
@@ -492,7 +492,7 @@ int rt_init_rand(rt_context* c, int width, int height, int row_offset, int row_s
     c->row_offset = row_offset;
     c->row_stride = row_stride;
     c->rows = rows;
-    c->frame = 1;
+    c->st.restart();
     c->order_stale = true;
     return RT_OK;
 }
@@ -522,16 +522,12 @@ int rt_get_state(rt_context* c, uint32_t* rng, float* accum) {
         if (accum) planes_to_rgb(c->accum.as<float>(), npix, accum);
         return RT_OK;
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const int qrc = quiesce(c);  // the last render, on whatever stream it ran
-    if (qrc) return qrc;
-    if (rng) HIP_TRY(c, hipMemcpy(rng, c->rng.p, npix * 6 * sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (accum) {
-        std::vector<float> planes(npix * 3);
-        HIP_TRY(c, hipMemcpy(planes.data(), c->accum.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        planes_to_rgb(planes.data(), npix, accum);
-    }
+    std::vector<float> planes;
+    if (accum && !try_resize(planes, npix * 3)) return fail(c, RT_ERR_OUT_OF_MEMORY, "host state for %zu pixels", npix);
+    const int rc = read_settled(c, {{rng, c->rng.p, npix * 6 * sizeof(unsigned)},
+                                    {accum ? planes.data() : nullptr, c->accum.p, npix * 3 * sizeof(float)}});
+    if (rc) return rc;
+    if (accum) planes_to_rgb(planes.data(), npix, accum);
     return RT_OK;
 }
 
@@ -543,8 +539,7 @@ int rt_set_state(rt_context* c, const uint32_t* rng, const float* accum, unsigne
     if (c->cpu) {
         if (rng) std::memcpy(c->rng.p, rng, npix * 6 * sizeof(unsigned));
         if (accum) rgb_to_planes(accum, npix, c->accum.as<float>());
-        c->frame = frame_counter;
-        c->mom_drop();
+        c->st.set_frame(frame_counter);
         return RT_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -560,8 +555,7 @@ int rt_set_state(rt_context* c, const uint32_t* rng, const float* accum, unsigne
                                   c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->frame = frame_counter;
-    c->mom_drop();  // frameSum is no longer the sum the moments followed
+    c->st.set_frame(frame_counter);  // frameSum is no longer the sum the moments followed
     return RT_OK;
 }
 

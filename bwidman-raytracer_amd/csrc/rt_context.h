@@ -7,6 +7,7 @@
 //   rt_render_adaptive.cpp  rt_render_adaptive*, rt_get_counts (rt_adaptive.h)
 //   rt_post.cpp     first-hit features, denoiser, temporal reprojection, moment readout
 //   rt_scene.cpp    the scene compiler (rt_scene.h; no HIP, no context)
+//   rt_accum.h      the accumulation's host state and its transition table (no HIP)
 // The render kernels: rt_launch.h declares the launchers of their units
 // (rt_kernels{,_bvh,_fast,_bvh_fast,_shared}.hip); one header per kernel
 // (rt_kernel_simple.h, rt_kernel_sorted.h, rt_kernel_pair.h, rt_kernel_refill.h)
@@ -24,11 +25,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 #include <xmmintrin.h>
 
 #include "../../include/rt_abi.h"
+#include "rt_accum.h"
 #include "rt_launch.h"
 #include "rt_layout.h"
 #include "rt_scene.h"
@@ -230,7 +233,9 @@ struct rt_context {
     int deint_blocks = 0;        // BWRT_DEINT_BLOCKS: cap on the de-interleave grid (0 = one thread per 16 bytes)
     std::string kernel_name;     // the render kernel of the last launch (rt_last_kernel_name)
     int precision = RT_PRECISION_EXACT;  // rt_set_precision (BWRT_PRECISION): which kernels the next render launches
-    unsigned frame = 1;
+    // the frame counter, the moment tracking and the non-uniform state: what
+    // frameSum currently holds (rt_accum.h has the rules)
+    rt_accum_state st;
     int max_bounces = RT_DEFAULT_MAX_BOUNCES;
     int spp_inner = 1;  // samplesPerPixel, Main.cu:27
 
@@ -262,41 +267,21 @@ struct rt_context {
 
     // luminance moment tracking (rt_set_moments): a copy of frameSum before
     // the last tracked batch (3 planes) and {M, M2} per shard pixel, updated
-    // by one pass behind every render call while `mom_live`.  Tracking goes
-    // live at a render whose first frame is 1 and stays live while each render
-    // starts at mom_next, the frame after the last tracked one; mom_batches
-    // counts the tracked render calls (J).  Nothing is allocated before
-    // tracking is on and a render runs.
-    bool mom_on = false, mom_live = false;
-    unsigned mom_batches = 0, mom_next = 0;
+    // by one pass behind every tracked render call (`st`, rt_accum.h).
+    // Nothing is allocated before tracking is on and a render runs.
     Buf mom_prev, mom_m;
-    void mom_drop() {
-        mom_live = false;
-        mom_batches = 0;
-        ad_live = false;  // the counts go with the moments they belong to
-    }
 
-    // adaptive sampling (rt_render_adaptive, rt_adaptive.h).  `ad_live`: the
-    // accumulation is non-uniform, ad_cnt holds {n_p, J_p} per pixel (filled
-    // with the context's counts by the first adaptive call of an accumulation;
-    // nothing is allocated before).  It ends where the moments end, at a
-    // render of frame 1 and at rt_set_scene.  ad_max_n bounds every n_p from
-    // above (host side: the counts themselves stay on the device).  The
-    // selection's scratch: row sums, mask words with their popcounts, the
-    // list and {list_n, frame total}.  ad_ev: select / render / update +
-    // resolve brackets of the last call, recorded only with kernel timing on.
-    bool ad_live = false;
-    // rt_set_adaptive_filters: rt_denoise*, rt_denoise_var* and rt_temporal*
-    // accept the non-uniform state and take every pixel's own count (the
-    // count-aware forms in rt_atrous.h, rt_denoise.h, rt_denoise_var.h,
-    // rt_temporal.h); off, they refuse it.  A uniform accumulation runs the
-    // same kernels either way.
-    bool ad_filters = false;
-    unsigned long long ad_max_n = 0;
+    // adaptive sampling (rt_render_adaptive, rt_adaptive.h).  While `st` is
+    // non-uniform, ad_cnt holds {n_p, J_p} per pixel (filled with the context's
+    // counts by the first adaptive call of an accumulation; nothing is
+    // allocated before).  The selection's scratch: row sums, mask words with
+    // their popcounts, the list and {list_n, frame total}.  ad_ev: select /
+    // render / update + resolve brackets of the last call, recorded only with
+    // kernel timing on.
     int ad_kernel = 0;  // BWRT_ADAPTIVE_KERNEL: 1 simple, 2 queued, 0 = launch policy
     Buf ad_cnt, ad_rows, ad_mask, ad_pop, ad_list, ad_stat, ad_color;
     hipEvent_t ad_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool ad_timed = false, ad_ran = false;
+    bool ad_timed = false;
     float ad_cpu_ms[3] = {-1.0f, -1.0f, -1.0f};
     long long ad_cpu_selected = 0, ad_cpu_total = 0;
 
@@ -334,6 +319,15 @@ struct rt_context {
     void new_view() {
         guides_valid = false;
         view++;
+    }
+    // the scene or the camera changed: the next render restarts the
+    // accumulation (Controls.cuh: any movement sets accumulatedFrames = 1), on
+    // another image than the launch order and the sky table were made for
+    void view_changed() {
+        st.restart();
+        order_stale = true;
+        sky_gen++;
+        new_view();
     }
 };
 
@@ -378,6 +372,24 @@ int order_after_all(rt_context* c, hipStream_t s);
 int ensure_buf(rt_context* c, Buf& b, size_t bytes, const char* host_oom = "host buffer (%zu)", size_t n = 0);
 int shard_rows(int height, int row_offset, int row_stride);
 int shard_check(rt_context* c, int width, int height, int row_offset, int row_stride);  // RT_OK or the failure
+// Host copies of device buffers of a GPU context once no queued work writes
+// them: the context's stream synchronised, quiesce(), then one hipMemcpy per
+// entry with a destination.  Staging memory is the caller's (try_resize).
+struct HostCopy {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+int read_settled(rt_context* c, std::initializer_list<HostCopy> copies);
+template <class T>
+bool try_resize(std::vector<T>& v, size_t n) {  // false: out of host memory
+    try {
+        v.resize(n);
+    } catch (...) {
+        return false;
+    }
+    return true;
+}
 // Camera prelude and compiled scene of a width x height view (shard
 // row_offset, stride, rows) into K; every other field 0 (rt_render.cpp)
 void fill_view(rt_context* c, int width, int height, int row_offset, int stride, int rows, rt_kparams& K);

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <initializer_list>
 
+#include "rt_adaptive.h"
 #include "rt_context.h"
 
 namespace {
@@ -69,13 +70,13 @@ int ensure_guides(rt_context* c, hipStream_t s) {
 // denoiser and the temporal reprojection (`who`) need besides their parameters
 int full_frame_check(rt_context* c, const char* who) {
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
-    if (c->frame < 2u || !c->accum.p)
+    if (c->st.frame() < 2u || !c->accum.p)
         return fail(c, RT_ERR_INVALID_ARGUMENT, "no frame accumulated yet (render first)");
     if (c->row_offset != 0 || c->row_stride > 1)
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the context holds a row shard (offset %d, stride %d): %s needs a full frame", c->row_offset,
                     c->row_stride, who);
-    if (c->ad_live && !c->ad_filters)
+    if (c->st.filters_refuse())
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the accumulation is non-uniform (rt_render_adaptive): %s takes one frame count for all pixels", who);
     return RT_OK;
@@ -86,7 +87,7 @@ int full_frame_check(rt_context* c, const char* who) {
 // The adaptive call that wrote them ran inside the render pass, so
 // prepare_frame's order_after_all has ordered the stream behind its update and
 // resolve passes, whatever stream it ran on.
-const uint2* frame_counts(const rt_context* c) { return c->ad_live ? c->ad_cnt.as<uint2>() : nullptr; }
+const uint2* frame_counts(const rt_context* c) { return c->st.nonuniform() ? c->ad_cnt.as<uint2>() : nullptr; }
 
 // iterations and sigmas of a filter (`term`: what its first sigma weighs)
 int filter_check(rt_context* c, int iterations, const char* term, float s0, float sn, float sp) {
@@ -139,7 +140,7 @@ Need colour_buf(Buf& b) { return {&b, sizeof(float4), "host colour buffers for %
 void fill_frame(const rt_context* c, float sigma_normal, float sigma_plane, rt_at_frame& F) {
     F.width = c->width;
     F.height = c->height;
-    F.inv = 1.0f / (float)(c->frame - 1u);
+    F.inv = 1.0f / (float)c->st.frames();
     F.in = 1.0f / (sigma_normal * sigma_normal);
     F.ip = 1.0f / (sigma_plane * sigma_plane);
     F.accum = c->accum.as<float>();
@@ -220,9 +221,9 @@ int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream
     fill_frame(c, dp->sigma_normal, dp->sigma_plane, A.f);
     A.sigma_lum = dp->sigma_lum;
     // the tracked variance of this very frame, else the spatial estimate
-    A.tracked = c->mom_live && c->mom_next == c->frame && c->mom_batches >= (unsigned)dp->min_batches;
+    A.tracked = c->st.current() && c->st.batches() >= (unsigned)dp->min_batches;
     if (A.tracked) {
-        A.rd = 1.0f / ((float)(c->mom_batches - 1u) * (float)(c->frame - 1u));
+        A.rd = 1.0f / ((float)(c->st.batches() - 1u) * (float)c->st.frames());
         A.mom = c->mom_m.as<float2>();
     }
     // non-uniform: the context's frame and batch counts are the uniform base,
@@ -308,8 +309,8 @@ int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_
     T.width = c->width;
     T.height = c->height;
     T.has_history = c->tp_has_hist ? 1 : 0;
-    T.n = (float)(c->frame - 1u);
-    T.inv = 1.0f / (float)(c->frame - 1u);
+    T.n = (float)c->st.frames();
+    T.inv = 1.0f / (float)c->st.frames();
     T.max_history = tp->max_history;
     T.normal_cos_min = tp->normal_cos_min;
     T.plane_tol = tp->plane_tol;
@@ -512,60 +513,45 @@ float rt_last_temporal_ms(rt_context* c) { return c ? c->temporal.elapsed_ms() :
 
 int rt_set_moments(rt_context* c, int enable) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const bool on = enable != 0;
     // off ends the tracking; on starts not live (a render of frame 1 makes it
     // live), also in mid-accumulation.  The buffers stay for the next use.
-    if (on != c->mom_on) c->mom_drop();
-    c->mom_on = on;
+    c->st.set_tracking(enable != 0);
     return RT_OK;
 }
 
-int rt_get_moments(const rt_context* c) { return c && c->mom_on ? 1 : 0; }
+int rt_get_moments(const rt_context* c) { return c && c->st.tracking() ? 1 : 0; }
 
-int rt_moments_batches(const rt_context* c) { return c && c->mom_live ? (int)c->mom_batches : 0; }
+int rt_moments_batches(const rt_context* c) { return c ? (int)c->st.batches() : 0; }
 
 int rt_get_variance(rt_context* c, float* var_out, float* lum_out) {
     const HostFpEnv fp;
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (!c->mom_live || c->mom_batches < 2u)
+    const unsigned J = c->st.batches();
+    if (J < 2u)
         return fail(c, RT_ERR_INVALID_ARGUMENT,
                     "no variance yet: moment tracking %s, %u batches (needs rt_set_moments and two render calls "
                     "of one accumulation)",
-                    c->mom_live ? "live" : "not live", c->mom_live ? c->mom_batches : 0u);
+                    J ? "live" : "not live", J);
     const size_t npix = (size_t)c->rows * c->width;
     const float2* m = c->mom_m.as<float2>();
-    const uint2* cn = c->ad_live ? c->ad_cnt.as<uint2>() : nullptr;  // non-uniform: each pixel's own {n_p, J_p}
+    const uint2* cn = frame_counts(c);  // non-uniform: each pixel's own {n_p, J_p}
     std::vector<float2> host;
     std::vector<uint2> host_cn;
     if (!c->cpu) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        try {
-            host.resize(npix);
-            if (cn) host_cn.resize(npix);
-        } catch (...) {
+        if (!try_resize(host, npix) || (cn && !try_resize(host_cn, npix)))
             return fail(c, RT_ERR_OUT_OF_MEMORY, "host moments for %zu pixels", npix);
-        }
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        const int rc = quiesce(c);  // the last render (and its update pass), on whatever stream it ran
+        // behind the last render (and its update pass), on whatever stream it ran
+        const int rc = read_settled(c, {{host.data(), m, npix * sizeof(float2)},
+                                        {cn ? host_cn.data() : nullptr, cn, npix * sizeof(uint2)}});
         if (rc) return rc;
-        HIP_TRY(c, hipMemcpy(host.data(), m, npix * sizeof(float2), hipMemcpyDeviceToHost));
         m = host.data();
-        if (cn) {
-            HIP_TRY(c, hipMemcpy(host_cn.data(), cn, npix * sizeof(uint2), hipMemcpyDeviceToHost));
-            cn = host_cn.data();
-        }
+        if (cn) cn = host_cn.data();
     }
-    if (cn) {  // rt_adaptive.h ad_var, the selection's own expression
-        for (size_t i = 0; i < npix; i++) {
-            if (var_out) var_out[i] = m[i].y * (1.0f / ((float)(cn[i].y - 1u) * (float)cn[i].x));
-            if (lum_out) lum_out[i] = m[i].x;
-        }
-        return RT_OK;
-    }
-    // 1 / ((J - 1) n), n = the frames accumulated
-    const float rd = 1.0f / ((float)(c->mom_batches - 1u) * (float)(c->mom_next - 1u));
+    // M2 / ((J - 1) n): the selection's own expression, n the frames accumulated
+    const uint2 uniform = make_uint2(c->st.tracked_frames(), J);
     for (size_t i = 0; i < npix; i++) {
-        if (var_out) var_out[i] = m[i].y * rd;
+        const uint2 nj = cn ? cn[i] : uniform;
+        if (var_out) var_out[i] = ad_var(m[i].y, nj.x, nj.y);
         if (lum_out) lum_out[i] = m[i].x;
     }
     return RT_OK;

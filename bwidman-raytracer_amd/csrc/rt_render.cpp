@@ -25,18 +25,16 @@ static int prepare(rt_context* c, const rt_render_params* p, rt_kparams& K, unsi
         int rc = rt_init_rand(c, p->width, p->height, p->row_offset, stride);
         if (rc) return rc;
     }
-    first = p->first_frame ? p->first_frame : c->frame;
     // a non-uniform accumulation (rt_render_adaptive) ends at a render of
     // frame 1; no uniform render can continue it
-    if (c->ad_live) {
-        if (first != 1u)
+    switch (c->st.uniform_start(p->first_frame, p->samples, first)) {
+        case rt_accum_state::Start::nonuniform:
             return fail(c, RT_ERR_UNSUPPORTED,
                         "the accumulation is non-uniform (rt_render_adaptive): a uniform render cannot continue it "
                         "(first_frame %u; 1 restarts)", first);
-        c->ad_live = false;
+        case rt_accum_state::Start::overflow: return fail(c, RT_ERR_INVALID_ARGUMENT, "frame counter overflow");
+        case rt_accum_state::Start::ok: break;
     }
-    if ((unsigned long long)first + (unsigned)p->samples > 0xffffffffull)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "frame counter overflow");
     if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
 
     fill_view(c, p->width, p->height, p->row_offset, stride, c->rows, K);
@@ -106,22 +104,17 @@ void fill_view(rt_context* c, int width, int height, int row_offset, int stride,
 }
 
 // Luminance moment tracking (rt_set_moments, rt_moments.h) of the call that
-// renders frames first .. first + samples - 1: whether it is tracked (`run`),
-// its buffers and the arguments of its update pass.  Tracking goes live at a
-// render that starts the accumulation and stays live while every render
-// starts at the frame after the last tracked one; any other render ends it.
+// renders frames first .. first + samples - 1: whether it is tracked (`run`;
+// rt_accum.h steps 4 and 5), its buffers and the arguments of its update pass.
 static int moments_prepare(rt_context* c, unsigned first, int samples, rt_mom_args& A, bool& run) {
-    run = c->mom_on && (first == 1u || (c->mom_live && first == c->mom_next));
-    if (!run) {
-        c->mom_drop();
-        return RT_OK;
-    }
+    run = c->st.uniform_track(first);
+    if (!run) return RT_OK;
     const size_t npix = (size_t)c->rows * c->width;
     const char* oom = "host moments for %zu pixels";
     int rc = ensure_buf(c, c->mom_prev, npix * 3 * sizeof(float), oom, npix);
     if (!rc) rc = ensure_buf(c, c->mom_m, npix * sizeof(float2), oom, npix);
     if (rc) {
-        c->mom_drop();
+        c->st.end_tracking();
         return rc;
     }
     const HostFpEnv fp;
@@ -134,13 +127,6 @@ static int moments_prepare(rt_context* c, unsigned first, int samples, rt_mom_ar
     A.prev = c->mom_prev.as<float>();
     A.mom = c->mom_m.as<float2>();
     return RT_OK;
-}
-
-static void moments_commit(rt_context* c, unsigned first, int samples) {
-    if (first == 1u) c->mom_batches = 0;
-    c->mom_live = true;
-    c->mom_batches++;
-    c->mom_next = first + (unsigned)samples;
 }
 
 // The CPU backend's render: rt_cpu.cpp over the host state, synchronous
@@ -156,12 +142,9 @@ static int cpu_render(rt_context* c, const rt_render_params* p, int threads, uin
     if ((rc = moments_prepare(c, first, p->samples, MA, track))) return rc;
     (void)c->render.begin(nullptr, true);
     rt_cpu_render(K, threads > 0 ? threads : c->threads);
-    if (track) {
-        rt_cpu_moments(MA, threads > 0 ? threads : c->threads);
-        moments_commit(c, first, p->samples);
-    }
+    if (track) rt_cpu_moments(MA, threads > 0 ? threads : c->threads);
     (void)c->render.end(nullptr);
-    c->frame = first + (unsigned)p->samples;  // Main.cu:480 accumulatedFrames++
+    c->st.uniform_done(first, p->samples, track);
     if (rgba_out) std::memcpy(rgba_out, c->rgba.p, npix * 4);
     if (accum_out) planes_to_rgb(c->accum.as<float>(), npix, accum_out);
     return RT_OK;
@@ -324,7 +307,7 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
         (void)hipFree(stamps);
     }
     if (e != hipSuccess) {
-        c->mom_drop();
+        c->st.end_tracking();
         return hip_fail(c, e, "rt_render_kernel launch");
     }
     // the moment update of this call's batch: behind the render kernel on the
@@ -334,13 +317,15 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     if (track) {
         e = rt_launch_moments(MA, s);
         if (e != hipSuccess) {
-            c->mom_drop();
+            c->st.end_tracking();
             return hip_fail(c, e, "rt_moments_kernel launch");
         }
-        moments_commit(c, first, samples);
     }
-    HIP_TRY(c, c->render.end(s));
-    c->frame = first + (unsigned)samples;  // Main.cu:480 accumulatedFrames++
+    if ((e = c->render.end(s)) != hipSuccess) {  // both kernels are queued: frameSum moved on
+        c->st.end_tracking();
+        return hip_fail(c, e, "c->render.end(s)");
+    }
+    c->st.uniform_done(first, samples, track);
     return RT_OK;
 }
 

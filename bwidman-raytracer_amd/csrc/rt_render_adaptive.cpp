@@ -33,14 +33,19 @@ int params_check(rt_context* c, const rt_adaptive_params* p, int& max_bounces) {
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the context holds a row shard (offset %d, stride %d): the selection window needs a full frame",
                     c->row_offset, c->row_stride);
-    if (!c->mom_live || c->mom_batches < 2u || !c->rng.p)
+    const rt_accum_state& st = c->st;
+    if (st.batches() < 2u || !c->rng.p)
         return fail(c, RT_ERR_INVALID_ARGUMENT,
                     "rt_render_adaptive needs live moment tracking with at least 2 batches (rt_set_moments and two "
                     "render calls of one accumulation): tracking %s, %u batches",
-                    c->mom_live ? "live" : "not live", c->mom_live ? c->mom_batches : 0u);
-    const unsigned long long base = c->ad_live ? c->ad_max_n : (unsigned long long)(c->mom_next - 1u);
-    // (ad_max_n bounds every n_p, and J_p <= n_p: a batch has at least one frame)
-    if (base + (unsigned)p->samples > 0xffffffffull) return fail(c, RT_ERR_INVALID_ARGUMENT, "frame count overflow");
+                    st.batches() ? "live" : "not live", st.batches());
+    if (!st.current())
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "rt_render_adaptive: the tracked moments continue at frame %u but the frame counter is %u (the "
+                    "accumulation was restarted by a scene, camera or reset call): render first",
+                    st.tracked_frames() + 1u, st.frame());
+    if (st.adaptive_base() + (unsigned)p->samples > 0xffffffffull)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "frame count overflow");
     return RT_OK;
 }
 
@@ -58,7 +63,7 @@ int setup(rt_context* c, const rt_adaptive_params* p, rt_ad_args& A, bool& fresh
     if (!rc) rc = ensure_buf(c, c->ad_list, npix * sizeof(int), oom, npix);
     if (!rc) rc = ensure_buf(c, c->ad_stat, 16, oom, npix);
     if (rc) return rc;
-    fresh = !c->ad_live;
+    fresh = !c->st.nonuniform();
     std::memset(&A, 0, sizeof A);
     A.width = c->width;
     A.height = c->height;
@@ -98,13 +103,6 @@ void kparams(rt_context* c, int samples, int max_bounces, rt_kparams& K) {
     K.rgba = nullptr;  // the resolve pass writes the image
 }
 
-void commit(rt_context* c, const rt_adaptive_params* p, bool fresh) {
-    if (fresh) c->ad_max_n = (unsigned long long)(c->mom_next - 1u);
-    c->ad_max_n += (unsigned)p->samples;
-    c->ad_live = true;
-    c->ad_ran = true;
-}
-
 int cpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, float* color) {
     const HostFpEnv fp;
     rt_ad_args A;
@@ -113,7 +111,7 @@ int cpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, fl
     A.rgba = c->rgba.as<unsigned>();
     A.color = color;
     if (fresh) {
-        const uint2 v = make_uint2(c->mom_next - 1u, c->mom_batches);
+        const uint2 v = make_uint2(c->st.tracked_frames(), c->st.batches());
         for (long i = 0; i < A.npix; i++) A.cnt[i] = v;
         *A.total = (unsigned long long)A.npix * v.x;
     }
@@ -135,7 +133,7 @@ int cpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, fl
     c->ad_cpu_ms[2] = ms(t2, t3);
     c->ad_cpu_selected = (long long)*A.list_n;
     c->ad_cpu_total = (long long)*A.total;
-    commit(c, p, fresh);
+    c->st.adaptive_done(p->samples);
     return RT_OK;
 }
 
@@ -166,7 +164,7 @@ int gpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, un
     c->ad_timed = false;
     if (timed) HIP_TRY(c, hipEventRecord(c->ad_ev[0], s));
     hipError_t e = hipSuccess;
-    if (fresh) e = rt_launch_adaptive_fill(A.cnt, A.total, A.npix, c->mom_next - 1u, c->mom_batches, s);
+    if (fresh) e = rt_launch_adaptive_fill(A.cnt, A.total, A.npix, c->st.tracked_frames(), c->st.batches(), s);
     if (e == hipSuccess) e = rt_launch_adaptive(A, 0, s);
     if (e == hipSuccess) e = rt_launch_adaptive(A, 1, s);
     if (e == hipSuccess && timed) e = hipEventRecord(c->ad_ev[1], s);
@@ -179,19 +177,19 @@ int gpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, un
     if (e == hipSuccess && timed) e = hipEventRecord(c->ad_ev[3], s);
     if (e != hipSuccess) {
         // what ran is unknown: the moments and counts no longer describe frameSum
-        c->mom_drop();
+        c->st.end_tracking();
         (void)c->render.end(s);
         return hip_fail(c, e, "rt_render_adaptive launch");
     }
     HIP_TRY(c, c->render.end(s));
     c->ad_timed = timed;
-    commit(c, p, fresh);
+    c->st.adaptive_done(p->samples);
     return RT_OK;
 }
 
 int read_stats(rt_context* c, rt_adaptive_stats* st) {
     if (!c || !st) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (!c->ad_live || !c->ad_ran) return fail(c, RT_ERR_INVALID_ARGUMENT, "no adaptive call in this accumulation");
+    if (!c->st.nonuniform()) return fail(c, RT_ERR_INVALID_ARGUMENT, "no adaptive call in this accumulation");
     if (c->cpu) {
         st->selected = c->ad_cpu_selected;
         st->frames_total = c->ad_cpu_total;
@@ -200,11 +198,8 @@ int read_stats(rt_context* c, rt_adaptive_stats* st) {
         st->resolve_ms = c->ad_cpu_ms[2];
         return RT_OK;
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (const int rc = quiesce(c)) return rc;
     unsigned long long h[2] = {0, 0};
-    HIP_TRY(c, hipMemcpy(h, c->ad_stat.p, sizeof h, hipMemcpyDeviceToHost));
+    if (const int rc = read_settled(c, {{h, c->ad_stat.p, sizeof h}})) return rc;
     st->frames_total = (long long)h[0];
     st->selected = (long long)(unsigned)h[1];
     st->select_ms = st->render_ms = st->resolve_ms = -1.0f;
@@ -270,8 +265,8 @@ int rt_get_counts(rt_context* c, uint32_t* frames_out, uint32_t* batches_out) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (!c->rng.p) return fail(c, RT_ERR_INVALID_ARGUMENT, "no shard state (render or rt_init_rand first)");
     const size_t npix = (size_t)c->rows * c->width;
-    if (!c->ad_live) {  // uniform: the context's counts
-        const uint32_t n = c->frame - 1u, J = c->mom_live ? c->mom_batches : 0u;
+    if (!c->st.nonuniform()) {  // uniform: the context's counts
+        const uint32_t n = c->st.frames(), J = c->st.batches();
         for (size_t i = 0; i < npix; i++) {
             if (frames_out) frames_out[i] = n;
             if (batches_out) batches_out[i] = J;
@@ -281,15 +276,8 @@ int rt_get_counts(rt_context* c, uint32_t* frames_out, uint32_t* batches_out) {
     const uint2* cn = c->ad_cnt.as<uint2>();
     std::vector<uint2> host;
     if (!c->cpu) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        try {
-            host.resize(npix);
-        } catch (...) {
-            return fail(c, RT_ERR_OUT_OF_MEMORY, "host counts for %zu pixels", npix);
-        }
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (const int rc = quiesce(c)) return rc;
-        HIP_TRY(c, hipMemcpy(host.data(), cn, npix * sizeof(uint2), hipMemcpyDeviceToHost));
+        if (!try_resize(host, npix)) return fail(c, RT_ERR_OUT_OF_MEMORY, "host counts for %zu pixels", npix);
+        if (const int rc = read_settled(c, {{host.data(), cn, npix * sizeof(uint2)}})) return rc;
         cn = host.data();
     }
     for (size_t i = 0; i < npix; i++) {

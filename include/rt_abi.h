@@ -644,7 +644,10 @@ RT_API float rt_last_denoise_var_ms(rt_context* ctx);
  * A context that never calls these entry points behaves bit for bit as before.
  *
  * Errors: RT_ERR_NO_SCENE; RT_ERR_INVALID_ARGUMENT when moment tracking is not
- * live or has fewer than 2 batches, a parameter is out of range or NaN, or a
+ * live or has fewer than 2 batches, when the accumulation was restarted
+ * (rt_reset_accumulation, rt_set_camera, a moving rt_controls, rt_set_scene)
+ * and nothing rendered since (the moments describe the old one: render first;
+ * nothing is touched), a parameter is out of range or NaN, or a
  * count could pass 2^32 - 1; RT_ERR_UNSUPPORTED when the context's pixel state
  * is a row shard (the window needs neighbours), in RT_PRECISION_REFERENCE_FAST
  * (a list schedule would be a new arithmetic form of that mode, whose results

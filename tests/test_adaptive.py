@@ -224,6 +224,66 @@ def test_non_uniform_state(bwrt_lib):
         assert (r.counts(h, w)[0] == 1).all()
 
 
+RESTARTS = {
+    "reset_accumulation": lambda r, scene: r.reset_accumulation(),
+    "set_camera": lambda r, scene: r.set_camera(scene.camera),
+    "controls": lambda r, scene: r.controls(["LEFT"], 0.05),
+    "set_scene": lambda r, scene: r.set_scene(scene),
+}
+
+
+def report(r, w, h):
+    """What the context says about its accumulation."""
+    return r.get_state(h, w) + r.counts(h, w) + (np.array([r.frame_counter, r.moments_batches]),)
+
+
+def refused_after_restart(lib, make, restart, non_uniform, adaptive, w=33, h=17, mb=2):
+    """After a call that restarts the accumulation without a render, the
+    tracked moments describe the old frameSum, not the accumulation the frame
+    counter reports: `adaptive(r, params)` (a status) refuses and changes
+    nothing; behind a render of frame 1 and one more it works again, and equals
+    a fresh context `make()` bit for bit."""
+    scene = scenes.scene_07()
+    with make() as r:
+        start(r, scene, w, h, mb)
+        if non_uniform:
+            r.render_adaptive(w, h, mb, samples=2, **DEFAULTS)
+        RESTARTS[restart](r, scene)
+        assert r.frame_counter == 1 and r.moments_batches == 4
+        before = report(r, w, h)
+        assert adaptive(r, r.adaptive_params(samples=2, **DEFAULTS)) == abi.RT_ERR_INVALID_ARGUMENT
+        assert b"render first" in lib.rt_last_error(r.ctx)
+        for x, y in zip(before, report(r, w, h)):
+            assert np.array_equal(x, y, equal_nan=True)
+        rng, acc = r.get_state(h, w)
+
+        def again(c):
+            c.render(w, h, 2, mb)  # frame 1: the restart
+            c.render(w, h, 2, mb)
+            img, col, st = c.render_adaptive(w, h, mb, want_color=True, samples=2, **DEFAULTS)
+            return (img, col, np.array([st["selected"], st["frames_total"]])) + report(c, w, h) + \
+                c.variance(h, w, want_lum=True)
+        got = again(r)
+    with make() as f:
+        f.set_scene(scene)
+        RESTARTS[restart](f, scene)  # (the camera it leaves)
+        f.init_rand(w, h)
+        f.set_state(rng, acc, 1)
+        f.set_moments(True)
+        want = again(f)
+    assert 0 < got[2][0] < w * h
+    for x, y in zip(got, want):
+        assert np.array_equal(x, y, equal_nan=True)
+
+
+@pytest.mark.parametrize("non_uniform", [False, True])
+@pytest.mark.parametrize("restart", sorted(RESTARTS))
+def test_adaptive_call_refused_after_a_restart(bwrt_lib, restart, non_uniform):
+    lib = bwrt_lib
+    refused_after_restart(lib, lambda: Renderer.cpu(2, lib=lib), restart, non_uniform,
+                          lambda r, d: lib.rt_render_adaptive(r.ctx, C.byref(d), 2, None, None, None))
+
+
 # ---- replay: the core test --------------------------------------------------------
 
 @pytest.mark.parametrize("name,w,h,bounces", REPLAY)

@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from bwrt import Renderer, abi, scenes
-from test_adaptive import DEFAULTS, KS, START, adaptive_sequence, start
+import lifecycle_trace
+from test_adaptive import DEFAULTS, KS, RESTARTS, START, adaptive_sequence, refused_after_restart, start
 
 pytestmark = pytest.mark.gpu
 
@@ -233,3 +234,28 @@ def test_errors_and_state_on_the_gpu(bwrt_lib):
         g.render(w, h, 2, mb, first_frame=1)  # ends the state
         g.render(w, h, 2, mb)
         assert lib.rt_denoise(g.ctx, C.byref(dn), None, None) == abi.RT_OK
+
+
+@pytest.mark.parametrize("own_stream", [False, True])
+def test_device_call_refused_after_a_restart(bwrt_lib, own_stream):
+    """tests/test_adaptive.py's case for rt_render_adaptive_device, from the
+    tracked uniform and from the non-uniform state."""
+    import torch
+    lib = bwrt_lib
+    stream = torch.cuda.Stream()
+    sp = None if own_stream else stream.cuda_stream
+    for i, restart in enumerate(sorted(RESTARTS)):
+        refused_after_restart(lib, lambda: Renderer(0, lib=lib), restart, bool(i & 1),
+                              lambda r, d: lib.rt_render_adaptive_device(r.ctx, C.byref(d), 2, None, sp))
+    stream.synchronize()
+
+
+def test_lifecycle_trace_equals_cpu(bwrt_lib):
+    """The seeded call sequences of tests/lifecycle_trace.py through launch(),
+    the GPU adaptive call and the device readbacks: every record equals the CPU
+    context's of the same library."""
+    for seed in lifecycle_trace.SEEDS:
+        got = lifecycle_trace.trace(bwrt_lib, seed, gpu=True)
+        want = lifecycle_trace.trace(bwrt_lib, seed)
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert a == b, (seed, i)
