@@ -8,7 +8,9 @@ rows.  Frames (spp) are never split: a pixel's RNG stream is sequential across
 frames.  After the render the ranks exchange ONE message: a gather of
 equal-size RGBA8 row blocks (padded to ceil(H/G) rows) to rank 0 over
 RCCL/xGMI, and rank 0 de-interleaves the blocks into the image (a HIP kernel
-on the GPU path).
+on the GPU path).  The filters need more than the image: gather_frame sends
+every rank's frameSum (and moments) rows the same way and assembles them into
+one full frame on rank 0 (rt_export_shard / rt_assemble).
 """
 from __future__ import annotations
 
@@ -81,3 +83,43 @@ def gather_rows(local_block, plan: ShardPlan, out=None, group=None, dst: int = 0
     else:
         dist.gather(local_block, gather_list=list(out.unbind(0)) if root else None, dst=dst, group=group)
     return out if root else None
+
+
+def gather_frame(renderer, plan: ShardPlan, width: int, planes: int = 3, group=None, dst: int = 0, stream=None):
+    """This rank's row shard into the assembled frame of rank `dst`
+    (rt_export_shard -> gather_rows -> rt_assemble): afterwards `dst`'s
+    denoise, denoise_var and temporal run on the whole frame as on one
+    renderer that rendered all of it.  planes 3 = frameSum, 5 = with the
+    tracked moments (every rank tracking, in step).  Every rank must have
+    rendered the same frames.  Returns True on `dst`, False elsewhere.
+
+    A GPU renderer exports, gathers (RCCL) and assembles on `stream` (a
+    torch.cuda.Stream; None = torch's current one) without a host
+    synchronisation; a CPU renderer goes through host tensors (gloo)."""
+    import torch
+    import torch.distributed as dist
+    rps = plan.rows_per_shard
+    root = (dist.get_rank(group) if group is not None else dist.get_rank()) == dst
+    if renderer.is_cpu:
+        block = torch.zeros((planes, rps, width), dtype=torch.float32)
+        frames = batches = 0
+        if plan.rows > 0:  # (a rank beyond the image height sends padding only)
+            arr, frames, batches = renderer.export_shard(rps, width, planes)
+            block.copy_(torch.from_numpy(arr))
+        gathered = gather_rows(block, plan, group=group, dst=dst)
+        if root:
+            renderer.assemble(gathered.numpy(), frames, batches)
+        return root
+    dev = torch.device("cuda", renderer.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        frames = batches = 0
+        if plan.rows > 0:
+            block = torch.empty((planes, rps, width), dtype=torch.float32, device=dev)
+            frames, batches = renderer.export_shard_device(block.data_ptr(), rps, planes, s.cuda_stream)
+        else:
+            block = torch.zeros((planes, rps, width), dtype=torch.float32, device=dev)
+        gathered = gather_rows(block, plan, group=group, dst=dst)
+        if root:
+            renderer.assemble_device(gathered.data_ptr(), plan.world, rps, planes, frames, batches, s.cuda_stream)
+    return root

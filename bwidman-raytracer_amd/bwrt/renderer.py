@@ -415,6 +415,63 @@ class Renderer:
     def adaptive_filters(self) -> bool:
         return bool(self.lib.rt_get_adaptive_filters(self.ctx))
 
+    # -- row shards into one frame: the assembled frame -------------------------
+    def export_shard(self, rows_per_shard, width, planes=3):
+        """rt_export_shard: this context's block, (planes, rows_per_shard,
+        width) float32 — R, G, B of frameSum (then M, M2 with planes=5), the
+        shard's rows first, zero rows after them — and the (frames, batches)
+        it stands for."""
+        block = np.empty((planes, rows_per_shard, width), np.float32)
+        n, j = C.c_uint(), C.c_uint()
+        self._check(self.lib.rt_export_shard(self.ctx, rows_per_shard, planes, block.ctypes.data, C.byref(n),
+                                             C.byref(j)))
+        return block, n.value, j.value
+
+    def export_shard_device(self, block_ptr: int, rows_per_shard, planes=3, stream_ptr: int | None = None):
+        """rt_export_shard_device: the block into device memory on a stream
+        (asynchronous; after the last render, and the next render after it).
+        Returns (frames, batches)."""
+        n, j = C.c_uint(), C.c_uint()
+        self._check(self.lib.rt_export_shard_device(self.ctx, rows_per_shard, planes, block_ptr, stream_ptr,
+                                                    C.byref(n), C.byref(j)))
+        return n.value, j.value
+
+    def assemble(self, gathered, frames, batches=0):
+        """rt_assemble: make the assembled frame from `gathered`, (shards,
+        planes, rows_per_shard, width) float32 on the host: block r holds rows
+        r, r + shards, ...  denoise, denoise_var and temporal on a renderer
+        whose own state is a row shard then read it, with its frames / batches."""
+        g = np.ascontiguousarray(gathered, dtype=np.float32)
+        shards, planes, rps, _ = g.shape
+        self._check(self.lib.rt_assemble(self.ctx, g.ctypes.data, shards, rps, planes, frames, batches))
+
+    def assemble_device(self, gathered_ptr: int, shards, rows_per_shard, planes, frames, batches=0,
+                        stream_ptr: int | None = None):
+        """rt_assemble_device: the same from device memory on a stream
+        (asynchronous; ordered against the passes that read the assembled frame)."""
+        self._check(self.lib.rt_assemble_device(self.ctx, gathered_ptr, shards, rows_per_shard, planes, frames,
+                                                batches, stream_ptr))
+
+    def assembled(self):
+        """rt_assembled: (frames, batches) of the current assembled frame, or None."""
+        n, j = C.c_uint(), C.c_uint()
+        return (n.value, j.value) if self.lib.rt_assembled(self.ctx, C.byref(n), C.byref(j)) else None
+
+    def get_assembled(self, width, height, want_moments=False):
+        """rt_get_assembled: the assembled frameSum as (H, W, 3) float32 (as
+        get_state's), with want_moments also {M, M2} as (H, W, 2)."""
+        acc = np.empty((height, width, 3), np.float32)
+        mom = np.empty((height, width, 2), np.float32) if want_moments else None
+        self._check(self.lib.rt_get_assembled(self.ctx, acc.ctypes.data, mom.ctypes.data if want_moments else None))
+        return (acc, mom) if want_moments else acc
+
+    def assemble_drop(self):
+        """rt_assemble_drop: forget the assembled frame."""
+        self._check(self.lib.rt_assemble_drop(self.ctx))
+
+    def last_assemble_ms(self) -> float:
+        return self.lib.rt_last_assemble_ms(self.ctx)
+
     # -- checkpoint / resume -----------------------------------------------
     def get_state(self, rows, width):
         rng = np.empty((6, rows, width), dtype=np.uint32)
@@ -444,3 +501,17 @@ def render_multi(renderers, width: int, height: int, samples: int) -> np.ndarray
     if rc != abi.RT_OK:
         renderers[0]._check(rc)
     return out
+
+
+def assemble_multi(renderers, planes: int = 0, dst: int = 0):
+    """rt_assemble_multi, beside render_multi: every Renderer exports its row
+    shard, renderers[dst] assembles them, and its denoise / denoise_var /
+    temporal then run on the whole frame.  planes 3, 5 (with the moments), or
+    0 = 5 when every renderer's moments are current.  Returns the (frames,
+    batches) of the assembled frame."""
+    lib = renderers[0].lib
+    arr = (C.c_void_p * len(renderers))(*[r.ctx.value for r in renderers])
+    rc = lib.rt_assemble_multi(arr, len(renderers), planes, dst)
+    if rc != abi.RT_OK:
+        renderers[dst if 0 <= dst < len(renderers) else 0]._check(rc)
+    return renderers[dst].assembled()

@@ -65,7 +65,8 @@ int hip_fail(rt_context* c, hipError_t e, const char* what) {
 int quiesce(rt_context* c) {
     if (c->cpu) return RT_OK;
     HIP_TRY(c, c->render.flush());
-    for (Pass* p : {&c->denoise, &c->temporal, &c->denoise_var, &c->render}) HIP_TRY(c, p->sync());
+    for (Pass* p : {&c->denoise, &c->temporal, &c->denoise_var, &c->xport, &c->assemble, &c->render})
+        HIP_TRY(c, p->sync());
     return RT_OK;
 }
 
@@ -81,11 +82,13 @@ int read_settled(rt_context* c, std::initializer_list<HostCopy> copies) {
 }
 
 // Renders continue each other's RNG / frameSum state, the denoiser and the
-// reprojection read frameSum and share the guides and colour buffers: work
-// of any of the three on stream s waits for the last of each that ran on
-// another stream (no host sync)
+// reprojection read frameSum and share the guides and colour buffers, an
+// export reads frameSum and the moments, an assembly writes the frame the
+// full-frame passes read: work of any of them on stream s waits for the last
+// of each that ran on another stream (no host sync)
 int order_after_all(rt_context* c, hipStream_t s) {
-    for (Pass* p : {&c->render, &c->denoise, &c->temporal, &c->denoise_var}) HIP_TRY(c, p->wait_on(s));
+    for (Pass* p : {&c->render, &c->denoise, &c->temporal, &c->denoise_var, &c->xport, &c->assemble})
+        HIP_TRY(c, p->wait_on(s));
     return RT_OK;
 }
 
@@ -210,6 +213,7 @@ int rt_create_cpu(int threads, rt_context** out) {
     rt_context* c = new rt_context();
     c->cpu = true;
     c->render.host = c->denoise.host = c->temporal.host = c->denoise_var.host = true;
+    c->xport.host = c->assemble.host = true;
     c->device = -1;
     c->threads = threads > 0 ? threads : rt_cpu_threads();
     *out = c;
@@ -244,7 +248,7 @@ void rt_destroy(rt_context* c) {
         (void)hipSetDevice(c->device);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
         c->render.pending = false;  // its launch is done: the stream is synchronised
-        for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var}) {
+        for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var, &c->xport, &c->assemble}) {
             (void)p->sync();
             p->destroy();
         }
@@ -505,7 +509,8 @@ int rt_synchronize(rt_context* c) {
     // marks the last render (later renders on a caller's stream wait on it)
     HIP_TRY(c, c->render.flush());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var}) HIP_TRY(c, p->sync());
+    for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var, &c->xport, &c->assemble})
+        HIP_TRY(c, p->sync());
     return RT_OK;
 }
 

@@ -6,6 +6,7 @@
 //   rt_render.cpp   prepare, fill_view, launch, rt_render*, multi-GPU, de-interleave
 //   rt_render_adaptive.cpp  rt_render_adaptive*, rt_get_counts (rt_adaptive.h)
 //   rt_post.cpp     first-hit features, denoiser, temporal reprojection, moment readout
+//   rt_gather.cpp   rt_export_shard, rt_assemble*, the assembled frame (rt_assemble.h)
 //   rt_scene.cpp    the scene compiler (rt_scene.h; no HIP, no context)
 //   rt_accum.h      the accumulation's host state and its transition table (no HIP)
 // The render kernels: rt_launch.h declares the launchers of their units
@@ -15,7 +16,8 @@
 // The post-render passes' kernels and arithmetic: rt_atrous.h (what the filters
 // and the reprojection share, host and device), rt_atrous_tile.h (the pixel and
 // the LDS-tiled kernel with their launchers, device only), then one header and
-// one unit each: rt_denoise, rt_denoise_var, rt_temporal, rt_moments.
+// one unit each: rt_denoise, rt_denoise_var, rt_temporal, rt_moments; rt_assemble
+// (the copies behind rt_export_shard and rt_assemble).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -52,6 +54,8 @@ void rt_cpu_denoise_level(const rt_dn_level& L, int threads);
 void rt_cpu_temporal(const rt_tp_args& T, int threads);
 void rt_cpu_moments(const rt_mom_args& A, int threads);
 void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads);
+void rt_cpu_export_shard(const rt_asm_args& A, int threads);
+void rt_cpu_assemble(const rt_asm_args& A, int threads);
 // a-trous filter (rt_denoise.hip)
 hipError_t rt_launch_denoise_level(const rt_dn_level& L, bool tiled, hipStream_t stream);
 // temporal reprojection (rt_temporal.hip)
@@ -60,6 +64,9 @@ hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream);
 hipError_t rt_launch_moments(const rt_mom_args& A, hipStream_t stream);
 // variance-guided filter (rt_denoise_var.hip): stage 0 input, 1 sigma pass, 2 level
 hipError_t rt_launch_denoise_var(const rt_dv_args& A, int stage, bool tiled, hipStream_t stream);
+// a shard's block and the assembled frame (rt_assemble.hip); max_blocks > 0 caps the grid
+hipError_t rt_launch_export_shard(const rt_asm_args& A, int max_blocks, hipStream_t stream);
+hipError_t rt_launch_assemble(const rt_asm_args& A, int max_blocks, hipStream_t stream);
 // adaptive sampling (rt_adaptive.hip): the count fill; stage 0 row sums, 1 column
 // sums + test + scan + scatter, 2 the listed pixels' moment update, 3 resolve
 hipError_t rt_launch_adaptive_fill(uint2* cnt, unsigned long long* total, long npix, unsigned n, unsigned J,
@@ -184,8 +191,12 @@ struct rt_context {
     // colour buffers.  temporal: the reprojection pass, likewise; its events
     // are created by the first temporal call.  denoise_var: the
     // variance-guided filter, which shares the guides and colour buffers with
-    // the denoiser; its events are created by its first call.
-    Pass render, aux, denoise, temporal, denoise_var;
+    // the denoiser; its events are created by its first call.  xport: the
+    // last rt_export_shard, which reads frameSum and the moments (the next
+    // render waits for it).  assemble: the last rt_assemble, which writes the
+    // assembled frame the three full-frame passes read.  Both create their
+    // events on first use.
+    Pass render, aux, denoise, temporal, denoise_var, xport, assemble;
     // CPU backend (rt_create_cpu): host buffers, and the scalar fallback of
     // rt_cpu.cpp instead of the kernels
     bool cpu = false;
@@ -270,6 +281,28 @@ struct rt_context {
     // by one pass behind every tracked render call (`st`, rt_accum.h).
     // Nothing is allocated before tracking is on and a render runs.
     Buf mom_prev, mom_m;
+
+    // assembled frame (rt_assemble): a full-frame
+    // snapshot {frameSum, optionally {M, M2}, n, J} de-interleaved from the
+    // ranks' gathered blocks, which the full-frame passes read when the
+    // context's own pixel state is a row shard.  It is current while the view,
+    // the width and the height are those of its assembly.  as_block: this
+    // context's exported block, as_gather: the gathered blocks (staging of the
+    // host forms and of rt_assemble_multi).  Nothing is allocated before the
+    // first call.
+    struct Assembled {
+        Buf sum, mom;
+        bool made = false;
+        int planes = 0, width = 0, height = 0;
+        unsigned frames = 0, batches = 0;
+        unsigned long long view = 0;
+    };
+    Assembled as;
+    Buf as_block, as_gather;
+    bool assembled_current() const {
+        return as.made && as.view == view && as.width == width && as.height == height;
+    }
+    bool holds_shard() const { return row_offset != 0 || row_stride > 1; }
 
     // adaptive sampling (rt_render_adaptive, rt_adaptive.h).  While `st` is
     // non-uniform, ad_cnt holds {n_p, J_p} per pixel (filled with the context's
@@ -360,8 +393,9 @@ int hip_fail(rt_context* c, hipError_t e, const char* what);
         if (_e != hipSuccess) return hip_fail(ctx, _e, #expr); \
     } while (0)
 
-// Host-side wait for every pass that uses the shard state (render, denoise,
-// temporal, variance-guided denoise), on whatever streams they ran; no-op on a CPU context
+// Host-side wait for every pass that uses the shard state or the assembled
+// frame (render, denoise, temporal, variance-guided denoise, export, assembly),
+// on whatever streams they ran; no-op on a CPU context
 int quiesce(rt_context* c);
 // Order stream s after the same passes (no host sync)
 int order_after_all(rt_context* c, hipStream_t s);

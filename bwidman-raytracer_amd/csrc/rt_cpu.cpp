@@ -343,6 +343,19 @@ void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads) {
     });
 }
 
+// ---- a shard's block and the assembled frame on the host (rt_assemble.h) --------
+#include "rt_assemble.h"
+
+// The 4-byte items of the kernels, on the same pool: every item writes only its
+// own words, so the result does not depend on the thread count
+void rt_cpu_export_shard(const rt_asm_args& A, int threads) {
+    parallel_items(asm_items(A, A.rows_per_shard, 1), threads, [&](long q) { asm_export_item<1>(A, q); });
+}
+
+void rt_cpu_assemble(const rt_asm_args& A, int threads) {
+    parallel_items(asm_items(A, A.rows, 1), threads, [&](long q) { asm_assemble_item<1>(A, q); });
+}
+
 // ---- adaptive sampling on the host (rt_adaptive.h) -----------------------------
 #include "rt_adaptive.h"
 

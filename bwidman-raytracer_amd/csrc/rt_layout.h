@@ -244,6 +244,30 @@ struct rt_mom_args {
     float2* mom;         // {M, M2}: weighted mean of the batch luminances and sum of k_j (l_j - mean)^2
 };
 
+// One export or assembly pass (rt_assemble.h; rt_export_shard, rt_assemble).
+// A context's BLOCK is `planes` planes of rows_per_shard * width floats:
+// planes 0..2 are R, G, B of its frameSum, and with planes == 5 planes 3 and 4
+// are M and M2 of its tracked moments.  A plane holds the shard's rows in
+// shard order (row j is image row row_offset + j * row_stride), then padding
+// rows up to rows_per_shard, which export zero-fills and assembly never reads.
+// GATHERED is `shards` consecutive blocks, block r = rows r, r + shards, ...
+// (the layout of rt_deinterleave_rows_device and bwrt.dist.gather_rows).  The
+// assembled frame has frameSum's full-frame layout: with r = y % shards and
+// j = y / shards,
+//   sum[k * width * height + y * width + x]
+//       = gathered[((r * planes + k) * rows_per_shard + j) * width + x]    k < 3
+//   mom[y * width + x] = {the same with k = 3, with k = 4}
+struct rt_asm_args {
+    int width;
+    int rows;            // export: the shard's rows; assembly: the frame's height
+    int shards;          // assembly: blocks in `gathered` (export: 1)
+    int rows_per_shard;  // rows of one block plane (>= the shard's rows; shards * it >= height)
+    int planes;          // 3 or 5
+    float* sum;          // frameSum, 3 planes of rows * width: export reads it, assembly writes it
+    float2* mom;         // {M, M2} per pixel, likewise; only with 5 planes
+    float* block;        // export writes the block; assembly reads `gathered` here
+};
+
 // One pass of the variance-guided filter (rt_denoise_var.h): the input stage
 // (reads accum, writes dst), a sigma pass (reads src) or a level; src and dst
 // hold {colour, variance}.

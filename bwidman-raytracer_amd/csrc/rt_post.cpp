@@ -49,7 +49,8 @@ int read_back(rt_context* c, size_t npix, uint8_t* rgba_out, const Buf* color, f
 }
 
 // The guides of the context's current full frame, recomputed when stale (on
-// stream s for a GPU context: part of the denoise call that needs them)
+// stream s for a GPU context: part of the denoise call that needs them).  Always
+// of the full width x height view, whatever rows the context's own state holds.
 int ensure_guides(rt_context* c, hipStream_t s) {
     if (c->guides_valid) return RT_OK;
     rt_kparams K;
@@ -66,16 +67,42 @@ int ensure_guides(rt_context* c, hipStream_t s) {
     return RT_OK;
 }
 
-// A scene, an accumulated frame and a full-frame pixel state: what the
-// denoiser and the temporal reprojection (`who`) need besides their parameters
+// Which frame a full-frame pass reads.  A context whose
+// pixel state is the full frame reads its own accumulation and never consults
+// an assembled frame: a stale snapshot cannot replace newer data.  A context
+// that holds a row shard reads its assembled frame (rt_assemble) while that is
+// current: its planes, its n and, with 5 planes, its moments and J.
+struct FrameSrc {
+    const float* sum;    // frameSum, 3 planes of width * height
+    const float2* mom;   // {M, M2} per pixel (read only when `tracked`)
+    unsigned frames;     // n
+    unsigned batches;    // J
+    bool tracked;        // mom describes this very frame
+};
+bool reads_assembled(const rt_context* c) { return c->holds_shard() && c->assembled_current(); }
+FrameSrc frame_src(const rt_context* c) {
+    if (reads_assembled(c)) {
+        const bool mom = c->as.planes == 5;
+        return {c->as.sum.as<float>(), mom ? c->as.mom.as<float2>() : nullptr, c->as.frames, mom ? c->as.batches : 0u,
+                mom};
+    }
+    return {c->accum.as<float>(), c->mom_m.as<float2>(), c->st.frames(), c->st.batches(), c->st.current()};
+}
+
+// A scene, an accumulated frame and a full-frame pixel state (or a current
+// assembled frame on a shard context): what the denoiser and the temporal
+// reprojection (`who`) need besides their parameters
 int full_frame_check(rt_context* c, const char* who) {
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    if (reads_assembled(c)) return RT_OK;  // a snapshot with its own n >= 1 (a shard is never non-uniform)
+    const char* shard = "the context holds a row shard (offset %d, stride %d): %s needs a full frame%s";
+    // (a stale assembled frame is reported whatever the shard's own frame counter says)
+    if (c->holds_shard() && c->as.made)
+        return fail(c, RT_ERR_UNSUPPORTED, shard, c->row_offset, c->row_stride, who,
+                    " (its assembled frame is stale: the view or the frame shape changed since rt_assemble)");
     if (c->st.frame() < 2u || !c->accum.p)
         return fail(c, RT_ERR_INVALID_ARGUMENT, "no frame accumulated yet (render first)");
-    if (c->row_offset != 0 || c->row_stride > 1)
-        return fail(c, RT_ERR_UNSUPPORTED,
-                    "the context holds a row shard (offset %d, stride %d): %s needs a full frame", c->row_offset,
-                    c->row_stride, who);
+    if (c->holds_shard()) return fail(c, RT_ERR_UNSUPPORTED, shard, c->row_offset, c->row_stride, who, "");
     if (c->st.filters_refuse())
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the accumulation is non-uniform (rt_render_adaptive): %s takes one frame count for all pixels", who);
@@ -140,10 +167,11 @@ Need colour_buf(Buf& b) { return {&b, sizeof(float4), "host colour buffers for %
 void fill_frame(const rt_context* c, float sigma_normal, float sigma_plane, rt_at_frame& F) {
     F.width = c->width;
     F.height = c->height;
-    F.inv = 1.0f / (float)c->st.frames();
+    const FrameSrc src = frame_src(c);
+    F.inv = 1.0f / (float)src.frames;
     F.in = 1.0f / (sigma_normal * sigma_normal);
     F.ip = 1.0f / (sigma_plane * sigma_plane);
-    F.accum = c->accum.as<float>();
+    F.accum = src.sum;
     F.ga = c->guide_a.as<float4>();
     F.gb = c->guide_b.as<float4>();
 }
@@ -221,10 +249,11 @@ int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream
     fill_frame(c, dp->sigma_normal, dp->sigma_plane, A.f);
     A.sigma_lum = dp->sigma_lum;
     // the tracked variance of this very frame, else the spatial estimate
-    A.tracked = c->st.current() && c->st.batches() >= (unsigned)dp->min_batches;
+    const FrameSrc src = frame_src(c);
+    A.tracked = src.tracked && src.batches >= (unsigned)dp->min_batches;
     if (A.tracked) {
-        A.rd = 1.0f / ((float)(c->st.batches() - 1u) * (float)c->st.frames());
-        A.mom = c->mom_m.as<float2>();
+        A.rd = 1.0f / ((float)(src.batches - 1u) * (float)src.frames);
+        A.mom = src.mom;
     }
     // non-uniform: the context's frame and batch counts are the uniform base,
     // but every pixel's moments are current for its own n_p (the state lives
@@ -309,15 +338,16 @@ int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_
     T.width = c->width;
     T.height = c->height;
     T.has_history = c->tp_has_hist ? 1 : 0;
-    T.n = (float)c->st.frames();
-    T.inv = 1.0f / (float)c->st.frames();
+    const FrameSrc src = frame_src(c);
+    T.n = (float)src.frames;
+    T.inv = 1.0f / (float)src.frames;
     T.max_history = tp->max_history;
     T.normal_cos_min = tp->normal_cos_min;
     T.plane_tol = tp->plane_tol;
     std::memcpy(T.h_cam, H.cam_pos, sizeof T.h_cam);
     std::memcpy(T.h_rot, H.rot, sizeof T.h_rot);
     T.h_screen_z = H.screen_z;
-    T.accum = c->accum.as<float>();
+    T.accum = src.sum;
     T.ga = c->guide_a.as<float4>();
     T.gb = c->guide_b.as<float4>();
     T.h_col = H.col.as<float4>();

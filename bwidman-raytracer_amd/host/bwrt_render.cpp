@@ -21,7 +21,11 @@
 // LEFT_SHIFT LEFT RIGHT UP DOWN ESCAPE; an empty key list holds nothing);
 // the timeline repeats its last step.  ESCAPE ends the loop like
 // glfwSetWindowShouldClose.  --gpus N renders every frame across N contexts
-// (devices device..device+N-1, modulo the visible count) with rt_render_multi.
+// (devices device..device+N-1, modulo the visible count) with rt_render_multi;
+// before every --denoise, --denoise-var or --temporal call the contexts' row
+// shards are assembled into one frame on context 0 (rt_assemble_multi, with the
+// moments for --denoise-var), which that call then reads, and the assembly's
+// duration is printed.
 // --cpu renders on the library's scalar C++ CPU fallback instead (THREADS
 // host threads, 0 or omitted = all; BASELINE config 1's "scalar C++ CPU
 // path").  --spp sets samplesPerPixel (Main.cu:27; the in-frame loop keeps
@@ -31,13 +35,13 @@
 // only; the default, exact, is bit-identical to the CPU fallback).
 // --denoise [N] filters the final frame with rt_denoise (N a-trous levels,
 // default rt_denoise_params_default(); the --sigma-* flags replace its
-// sigmas): the file from --out is then the denoised frame (one context only).
+// sigmas): the file from --out is then the denoised frame.
 // --temporal calls rt_temporal after every render call, before controls(): a
 // view's accumulated colour is kept when the keys move the camera and is
 // reprojected into the next view (--max-history, --normal-cos and --plane-tol
 // replace the fields of rt_temporal_params_default()).  The file from --out is
 // then the temporal frame of the last render call, filtered when --denoise is
-// also given (one context only).
+// also given.
 // --aov PREFIX writes the first-hit feature buffers (rt_render_aov) as
 // PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5) and PREFIX_depth (1 / (1 +
 // depth), a miss black) images in --out's format (PNG without --out).
@@ -58,7 +62,8 @@
 // --max-frames force and cap per-pixel frame counts.  It prints the mean
 // frames per pixel and the last call's selected share; --aov PREFIX also
 // writes PREFIX_count (n_p over the largest n_p).  It cannot be combined with
-// --denoise, --denoise-var, --temporal, --precision fast or --gpus above 1.
+// --denoise, --denoise-var, --temporal, --precision fast or --gpus above 1
+// (adaptive sampling needs the whole frame on one context).
 // --adaptive-filters (rt_set_adaptive_filters) lifts that for --denoise,
 // --denoise-var and --temporal: the passes then take every pixel's own frame
 // count (--precision fast and --gpus above 1 stay refused).
@@ -90,7 +95,10 @@ static const char* kUsage =
     "                   [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]\n"
     "                   [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]\n"
     "                   [--adaptive TOL] [--adaptive-after 4] [--adaptive-radius R] [--adaptive-floor F]\n"
-    "                   [--min-frames N] [--max-frames N] [--adaptive-filters]\n";
+    "                   [--min-frames N] [--max-frames N] [--adaptive-filters]\n"
+    "  --gpus N with --denoise, --denoise-var or --temporal: the contexts' row shards are assembled\n"
+    "  on context 0 (rt_assemble_multi) before each filter call; --moments (the readout) and --adaptive\n"
+    "  need --gpus 1\n";
 
 struct KeyStep {
     unsigned keys;
@@ -154,7 +162,7 @@ int main(int argc, char** argv) {
     bool temporal = false;
     rt_temporal_params tp = rt_temporal_params_default();
     std::string aov;
-    bool moments = false, denoise_var = false;
+    bool moments = false, moments_readout = false, denoise_var = false;
     rt_denoise_var_params dv = rt_denoise_var_params_default();
     bool adaptive = false, adaptive_filters = false;
     int adaptive_after = 4;
@@ -215,7 +223,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--normal-cos")) tp.normal_cos_min = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--plane-tol")) tp.plane_tol = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--aov")) aov = next();
-        else if (!std::strcmp(argv[i], "--moments")) moments = true;
+        else if (!std::strcmp(argv[i], "--moments")) moments = moments_readout = true;
         else if (!std::strcmp(argv[i], "--adaptive")) {
             adaptive = moments = true;
             ad.tolerance = (float)std::atof(next());
@@ -284,12 +292,8 @@ int main(int argc, char** argv) {
     if (!dump.empty() || (!save.empty() && frames <= 0)) return 0;
 
     if (gpus < 1 || cpu_threads >= 0) gpus = 1;
-    if (temporal && gpus != 1) {
-        std::fprintf(stderr, "--temporal needs one context (a frame gathered from several GPUs is not reprojected)\n");
-        return 2;
-    }
-    if (moments && gpus != 1) {
-        std::fprintf(stderr, "--moments needs one context (each GPU of a gathered frame tracks its own rows)\n");
+    if (moments_readout && gpus != 1) {
+        std::fprintf(stderr, "--moments needs --gpus 1 (each GPU of a gathered frame tracks its own rows)\n");
         return 2;
     }
     const int ndev = cpu_threads >= 0 ? 1 : rt_device_count() > 0 ? rt_device_count() : 1;
@@ -321,6 +325,13 @@ int main(int argc, char** argv) {
     int calls = 0;  // render calls of the current accumulation
     rt_adaptive_stats ast{};
     bool ast_valid = false;
+    // several contexts: their row shards into one frame on context 0, which the next filter call reads
+    auto assemble = [&](int planes) -> int {
+        if (gpus == 1) return RT_OK;
+        const int arc = rt_assemble_multi(ctxs.data(), gpus, planes, 0);
+        if (arc == RT_OK) std::printf("assemble: %d shards, %.3f ms\n", gpus, rt_last_assemble_ms(ctx));
+        return arc;
+    };
     for (int done = 0; done < frames;) {  // Main.cu:471-496
         const int n = std::min(per_call, frames - done);
         auto t0 = clk::now();
@@ -342,6 +353,7 @@ int main(int argc, char** argv) {
             // before controls() restarts the accumulation.  The call after the
             // last render gives the frame that is written (filtered with --denoise)
             const bool last = done == frames || (!steps.empty() && (steps[step].keys & RT_KEY_ESCAPE));
+            if ((rc = assemble(3))) return die(ctx, rc, "rt_assemble_multi");
             rc = rt_temporal(ctx, &tp, last && denoise ? &dn : nullptr, last ? rgba.data() : nullptr, nullptr, nullptr);
             if (rc) return die(ctx, rc, "rt_temporal");
             if (last) {
@@ -375,15 +387,13 @@ int main(int argc, char** argv) {
         if (quit) break;
     }
     if (denoise && !temporal) {
-        if (gpus != 1) {
-            std::fprintf(stderr, "--denoise needs one context (a frame gathered from several GPUs is not denoised)\n");
-            return 2;
-        }
+        if ((rc = assemble(3))) return die(ctx, rc, "rt_assemble_multi");
         if ((rc = rt_denoise(ctx, &dn, rgba.data(), nullptr))) return die(ctx, rc, "rt_denoise");
         std::printf("denoise: %d levels, %.3f ms\n", dn.iterations, rt_last_denoise_ms(ctx));
     }
     if (denoise_var) {
         const int batches = rt_moments_batches(ctx);
+        if ((rc = assemble(0))) return die(ctx, rc, "rt_assemble_multi");
         if ((rc = rt_denoise_var(ctx, &dv, rgba.data(), nullptr, nullptr))) return die(ctx, rc, "rt_denoise_var");
         if (adaptive && ast_valid)  // non-uniform: each pixel by its own batches
             std::printf("denoise-var: %d levels, per-pixel variance source (tracked from %d batches), %.3f ms\n",
@@ -396,7 +406,9 @@ int main(int argc, char** argv) {
                         batches, dv.min_batches, rt_last_denoise_var_ms(ctx));
     }
     std::vector<float> var;  // of the mean luminance, per pixel
-    if (moments) {
+    // (several contexts: --denoise-var tracks the moments without the readout; each holds its own rows)
+    const bool moments_out = moments && gpus == 1;
+    if (moments_out) {
         const int batches = rt_moments_batches(ctx);
         std::printf("moments: %d batches", batches);
         if (batches >= 2 || !aov.empty()) {
@@ -440,7 +452,7 @@ int main(int argc, char** argv) {
         std::vector<uint8_t> img(npix * 4);
         uint32_t cmax = 1;
         for (const uint32_t c : counts) cmax = std::max(cmax, c);
-        for (int k = 0; k < (adaptive ? 5 : moments ? 4 : 3); k++) {
+        for (int k = 0; k < (adaptive ? 5 : moments_out ? 4 : 3); k++) {
             for (size_t i = 0; i < npix; i++) {
                 const float se = k == 3 ? std::sqrt(var[i]) : k == 4 ? (float)counts[i] / (float)cmax : 0.0f;
                 for (int ch = 0; ch < 3; ch++)

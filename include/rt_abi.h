@@ -472,7 +472,9 @@ RT_API rt_denoise_params rt_denoise_params_default(void);
  * iterations out of range, a sigma <= 0 or NaN, or no frame accumulated yet
  * (frame counter < 2); RT_ERR_NO_SCENE; RT_ERR_UNSUPPORTED: the context's
  * pixel state is a row shard (row_offset != 0 or row_stride > 1: the
- * neighbours of its rows live on other contexts). */
+ * neighbours of its rows live on other contexts) and it has no current
+ * assembled frame (rt_assemble below: with one, the filter reads that frame and
+ * its frame count instead; the same holds for rt_denoise_var and rt_temporal). */
 RT_API int rt_denoise(rt_context* ctx, const rt_denoise_params* params,
                       uint8_t* rgba_out, float* color_out);
 /* As above into DEVICE memory (w*h*4 bytes, 4-byte aligned, or NULL) on HIP
@@ -712,6 +714,96 @@ RT_API int rt_get_counts(rt_context* ctx, uint32_t* frames_out, uint32_t* batche
  * RT_PRECISION_REFERENCE_FAST stay unsupported.  It may be changed at any time. */
 RT_API int rt_set_adaptive_filters(rt_context* ctx, int enable);
 RT_API int rt_get_adaptive_filters(const rt_context* ctx);
+
+/* ---- row shards into one frame: the assembled frame ----------------------------
+ *   A frame rendered as row shards by several contexts
+ * (rt_render_multi, one process per rank) has the neighbours of every row on
+ * another context, so rt_denoise*, rt_denoise_var* and rt_temporal* refuse a
+ * shard context.  An ASSEMBLED FRAME lifts that: a full-frame snapshot
+ * {frameSum, optionally the moments {M, M2}, n, J} that one context keeps,
+ * de-interleaved from the ranks' gathered blocks.  While it is current, the
+ * three passes on a context whose own pixel state is a row shard read it
+ * instead, with its n (and, with moments, its J): bit for bit what a single
+ * context that rendered the whole frame gives.  A context whose pixel state is
+ * the full frame always reads its own accumulation, whatever was assembled.
+ * Nothing here has a counterpart in the reference (one GPU, Main.cu:342).
+ *
+ * Block layout, the contract between ranks.  A context's BLOCK is `planes`
+ * planes of rows_per_shard * width floats; planes = 3: R, G, B of frameSum;
+ * planes = 5: the same, then M, then M2.  A plane holds the shard's rows in
+ * shard order (row j = image row row_offset + j * row_stride) followed by
+ * padding rows up to rows_per_shard: export zero-fills them, assembly never
+ * reads them.  GATHERED is `shards` consecutive blocks, block r = rows r,
+ * r + shards, ... (rt_deinterleave_rows_device's layout).  With r = y % shards
+ * and j = y / shards, plane k of the assembled frameSum at pixel y * width + x
+ * is gathered[((r * planes + k) * rows_per_shard + j) * width + x], and the
+ * assembled moments of that pixel are {plane 3, plane 4}. */
+
+/* Write the context's block and report the frames accumulated (frame counter -
+ * 1) and the tracked batches (either may be NULL).  block: host memory,
+ * planes * rows_per_shard * width floats; GPU and CPU contexts; synchronous.
+ * RT_ERR_INVALID_ARGUMENT: a null pointer, planes not 3 or 5, rows_per_shard
+ * below the shard's rows, no frame accumulated yet, or planes == 5 while the
+ * tracked moments do not describe the accumulation (tracking off, or not live
+ * up to the frame counter); RT_ERR_UNSUPPORTED: a non-uniform accumulation. */
+RT_API int rt_export_shard(rt_context* ctx, int rows_per_shard, int planes, float* block,
+                           unsigned* frames_out, unsigned* batches_out);
+/* As above into DEVICE memory (4-byte aligned; 16 bytes per lane when width % 4
+ * == 0 and the pointer is 16-byte aligned) on HIP stream `stream` (NULL = the
+ * context's): ordered after the context's last render and its moment update,
+ * and the context's next render after it, whatever streams they use; no host
+ * synchronisation.  CPU context: RT_ERR_UNSUPPORTED. */
+RT_API int rt_export_shard_device(rt_context* ctx, int rows_per_shard, int planes, void* block_device,
+                                  void* stream, unsigned* frames_out, unsigned* batches_out);
+
+/* Make the context's assembled frame for its current view from `gathered`
+ * (host memory; GPU and CPU contexts; synchronous): width and height are the
+ * context's, `frames` is the snapshot's n and `batches` its J (used only with
+ * 5 planes).  shards == 1 is accepted (a world of one rank takes the same
+ * path).  Buffers are allocated on first use.  RT_ERR_NO_SCENE;
+ * RT_ERR_INVALID_ARGUMENT: a null pointer, no frame shape yet (render or
+ * rt_init_rand first), planes not 3 or 5, shards < 1, rows_per_shard * shards
+ * < height, frames < 1.  A refused call leaves an earlier assembled frame as
+ * it was. */
+RT_API int rt_assemble(rt_context* ctx, const float* gathered, int shards, int rows_per_shard, int planes,
+                       unsigned frames, unsigned batches);
+/* As above from DEVICE memory (4-byte aligned) on HIP stream `stream` (NULL =
+ * the context's), without host synchronisation: ordered after every earlier
+ * pass that reads the assembled frame (denoise, variance-guided denoise,
+ * temporal), and those passes after it, whatever streams they use.  The caller
+ * orders the gather between export and assembly, as with
+ * rt_deinterleave_rows_device.  CPU context: RT_ERR_UNSUPPORTED. */
+RT_API int rt_assemble_device(rt_context* ctx, const void* gathered_device, int shards, int rows_per_shard,
+                              int planes, unsigned frames, unsigned batches, void* stream);
+
+/* The one-process companion of rt_render_multi: every context with rows
+ * exports its block on its own stream, the blocks are copied to ctxs[dst]'s
+ * device, ctxs[dst] assembles them; synchronises before returning.  planes: 3,
+ * 5, or 0 = 5 if every context's moments are current (with equal batches) and
+ * 3 otherwise.  The contexts must be all GPU or all CPU contexts, distinct,
+ * hold shards i (mod n) of one width x height, and have equal frame counters
+ * (and equal batches with 5 planes); anything else is RT_ERR_INVALID_ARGUMENT
+ * and nothing is touched.  Contexts beyond the image height are skipped. */
+RT_API int rt_assemble_multi(rt_context* const* ctxs, int n, int planes, int dst);
+
+/* 1 while an assembled frame is CURRENT (then *frames_out and *batches_out,
+ * either may be NULL, get its n and J), else 0.  Current: one was made, and the
+ * context's view, width and height are those of its assembly: rt_set_scene,
+ * rt_set_camera, a moving rt_controls and a change of the frame shape end it;
+ * rt_reset_accumulation and further renders do not (a snapshot with its own
+ * n).  A shard context whose assembled frame is not current is refused by the
+ * three passes with RT_ERR_UNSUPPORTED, as one that never assembled. */
+RT_API int rt_assembled(const rt_context* ctx, unsigned* frames_out, unsigned* batches_out);
+/* Host readout of the last assembled frame (tests, checkpoints): accum_rgb
+ * w*h*3 floats interleaved r,g,b as rt_get_state's, moments w*h*2 floats {M,
+ * M2} per pixel; either may be NULL.  RT_ERR_INVALID_ARGUMENT: none was made,
+ * or moments asked of a 3-plane frame. */
+RT_API int rt_get_assembled(rt_context* ctx, float* accum_rgb, float* moments);
+/* Forget the assembled frame; its buffers stay allocated. */
+RT_API int rt_assemble_drop(rt_context* ctx);
+/* Duration (ms) of the last assembly (HIP events on its stream; wall time on
+ * a CPU context); -1 when unavailable. */
+RT_API float rt_last_assemble_ms(rt_context* ctx);
 
 RT_API const char* rt_error_string(int status);
 RT_API const char* rt_last_error(const rt_context* ctx);
