@@ -205,17 +205,21 @@ class Renderer:
                                                          stream_ptr))
 
     # -- first-hit features and the denoiser --------------------------------
-    def render_aov(self, width, height, row_offset=0, row_stride=1):
+    def render_aov(self, width, height, row_offset=0, row_stride=1, only=None):
         """rt_render_aov: the first-hit feature buffers of a shard as a dict of
         arrays: "albedo", "normal" (rows, width, 3) float32, "depth" (rows,
-        width) float32 (+inf on a miss), "prim" (rows, width) int32 (-1)."""
+        width) float32 (+inf on a miss), "prim" (rows, width) int32 (-1).
+        `only`: the names to compute; the call gets NULL for the others."""
         rows = self.lib.rt_shard_rows(height, row_offset, row_stride)
-        out = {"albedo": np.empty((rows, width, 3), np.float32), "normal": np.empty((rows, width, 3), np.float32),
-               "depth": np.empty((rows, width), np.float32), "prim": np.empty((rows, width), np.int32)}
+        shapes = {"albedo": ((rows, width, 3), np.float32), "normal": ((rows, width, 3), np.float32),
+                  "depth": ((rows, width), np.float32), "prim": ((rows, width), np.int32)}
+        names = list(shapes) if only is None else [only] if isinstance(only, str) else list(only)
+        if not names or set(names) - set(shapes):
+            raise ValueError(f"only={only!r}: expected names out of {list(shapes)}")
+        out = {k: np.empty(*shapes[k]) for k in shapes if k in names}
+        ptr = [out[k].ctypes.data if k in out else None for k in ("albedo", "normal", "depth", "prim")]
         p = self.params(width, height, 1, 0, 0, row_offset, row_stride)
-        self._check(self.lib.rt_render_aov(self.ctx, C.byref(p), out["albedo"].ctypes.data,
-                                           out["normal"].ctypes.data, out["depth"].ctypes.data,
-                                           out["prim"].ctypes.data))
+        self._check(self.lib.rt_render_aov(self.ctx, C.byref(p), *ptr))
         return out
 
     def denoise_params(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None):

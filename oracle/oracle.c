@@ -415,25 +415,51 @@ void orc_set_background(float r, float g, float b) { g_background = v3(r, g, b);
 static int g_spp = 1;
 void orc_set_samples_per_pixel(int n) { g_spp = n > 0 ? n : 1; }
 
-static vec3 trace_path(ray3 in, const orc_scene* sc, uint32_t st[6], int bounces,
-                       int max_bounces, unsigned long long* queries) { /* Main.cu:208-272 */
-    vec3 out = g_background;                                          /* backgroundColor */
-    if (bounces > max_bounces) return out;
-    (*queries)++;
-    hit_info closest = hit_init();
+/* Main.cu:214-234: the closest hit of one ray, the reference's loop over the
+ * index i with sphere i, plane i, triangle i and quad i interleaved.  Every
+ * test accepts nearZero < t <= closest (an equal distance replaces the hit, so
+ * of primitives at one distance the last one tested wins) and overwrites
+ * *closest; `which` records the primitive of the last accepted hit (the
+ * reference keeps only its HitInfo; the recording changes no arithmetic).
+ * Both trace_path and orc_first_hit_rows call this one loop. */
+typedef struct { int kind, index; } hit_prim;  /* ORC_KIND_*, index in its array; {-1, -1}: none */
+
+static int closest_hit(const ray3* in, const orc_scene* sc, hit_info* closest, hit_prim* which) {
+    *closest = hit_init();                                            /* :214 */
+    which->kind = ORC_KIND_MISS;
+    which->index = -1;
     int n = sc->sphere_count;                                         /* :217 */
     if (sc->plane_count > n) n = sc->plane_count;
     if (sc->triangle_count > n) n = sc->triangle_count;
     if (sc->quad_count > n) n = sc->quad_count;
     int hit = 0;
     for (int i = 0; i < n; i++) {                                     /* :221-234 */
-        if (i < sc->sphere_count) hit |= sphere_hit(&in, &sc->spheres[i], &closest);
-        if (i < sc->plane_count) hit |= plane_hit(&in, &sc->planes[i], &closest);
+        int h[4] = {0, 0, 0, 0};
+        if (i < sc->sphere_count) h[ORC_KIND_SPHERE] = sphere_hit(in, &sc->spheres[i], closest);
+        if (i < sc->plane_count) h[ORC_KIND_PLANE] = plane_hit(in, &sc->planes[i], closest);
         if (i < sc->triangle_count)
-            hit |= polygon_hit(&in, sc->triangles[i].vertices, 3, &sc->triangles[i].mat, &closest);
+            h[ORC_KIND_TRIANGLE] =
+                polygon_hit(in, sc->triangles[i].vertices, 3, &sc->triangles[i].mat, closest);
         if (i < sc->quad_count)
-            hit |= polygon_hit(&in, sc->quads[i].vertices, 4, &sc->quads[i].mat, &closest);
+            h[ORC_KIND_QUAD] = polygon_hit(in, sc->quads[i].vertices, 4, &sc->quads[i].mat, closest);
+        for (int k = 0; k < 4; k++)                                    /* in the order tested */
+            if (h[k]) {
+                hit = 1;
+                which->kind = k;
+                which->index = i;
+            }
     }
+    return hit;
+}
+
+static vec3 trace_path(ray3 in, const orc_scene* sc, uint32_t st[6], int bounces,
+                       int max_bounces, unsigned long long* queries) { /* Main.cu:208-272 */
+    vec3 out = g_background;                                          /* backgroundColor */
+    if (bounces > max_bounces) return out;
+    (*queries)++;
+    hit_info closest;
+    hit_prim which;
+    int hit = closest_hit(&in, sc, &closest, &which);                 /* :214-234 */
     if (hit) {                                                        /* :237-269 */
         vec3 emitted = scale(closest.mat.emittance, closest.mat.albedo);
         vec3 scatter, brdf;
@@ -467,20 +493,9 @@ static vec3 trace_path_forward(ray3 in, const orc_scene* sc, uint32_t st[6], int
     for (int bounces = 0;; bounces++) {
         if (bounces > max_bounces) return add(acc, mulv(T, g_background));
         (*queries)++;
-        hit_info closest = hit_init();
-        int n = sc->sphere_count;
-        if (sc->plane_count > n) n = sc->plane_count;
-        if (sc->triangle_count > n) n = sc->triangle_count;
-        if (sc->quad_count > n) n = sc->quad_count;
-        int hit = 0;
-        for (int i = 0; i < n; i++) {
-            if (i < sc->sphere_count) hit |= sphere_hit(&in, &sc->spheres[i], &closest);
-            if (i < sc->plane_count) hit |= plane_hit(&in, &sc->planes[i], &closest);
-            if (i < sc->triangle_count)
-                hit |= polygon_hit(&in, sc->triangles[i].vertices, 3, &sc->triangles[i].mat, &closest);
-            if (i < sc->quad_count)
-                hit |= polygon_hit(&in, sc->quads[i].vertices, 4, &sc->quads[i].mat, &closest);
-        }
+        hit_info closest;
+        hit_prim which;
+        int hit = closest_hit(&in, sc, &closest, &which);
         if (!hit) return add(acc, mulv(T, g_background));
         acc = add(acc, mulv(T, scale(closest.mat.emittance, closest.mat.albedo)));
         vec3 scatter, brdf;
@@ -524,6 +539,31 @@ static uint8_t to_u8(float v) {                                       /* Main.cu
     return (uint8_t)r;
 }
 
+/* The camera prelude shared by orc_render_rows and orc_first_hit_rows: the
+ * host part (Main.cu:336-338: screen distance, rotLeft * rotUp) and the
+ * un-jittered primary ray of pixel (x, y) (Main.cu:287-290). */
+typedef struct { float screen_z; mat3 rot; } view3;
+
+static view3 camera_view(const orc_scene* sc, int width) {            /* Main.cu:336-338 */
+    view3 v;
+    v.screen_z = -(float)(width / 2) / tanf(sc->camera.fov / 2.0f);
+    mat3 rl = rot_y(sc->camera.angle[0]);
+    mat3 ru = rot_x(sc->camera.angle[1]);
+    v.rot = matmul(&rl, &ru);
+    return v;
+}
+
+static ray3 primary_ray(const orc_scene* sc, const view3* v, int x, int y, int width, int height) {
+#if ORC_MUTANT == 2
+    vec3 pix = v3((float)(x - width / 2) + 0.5f, (float)(y - height / 2) + 0.5f, v->screen_z);
+#else
+    vec3 pix = v3((float)(x - width / 2), (float)(y - height / 2), v->screen_z);
+#endif
+    pix = matvec(&v->rot, pix);                                       /* :288 */
+    ray3 cam = {sc->camera.position, normalize3(pix)};
+    return cam;
+}
+
 int orc_render_rows(const orc_scene* sc, int width, int height, int row_offset,
                     int row_stride, int rows, unsigned first_frame, int passes,
                     int max_bounces, uint32_t* rng, float* accum, uint8_t* rgba,
@@ -531,11 +571,7 @@ int orc_render_rows(const orc_scene* sc, int width, int height, int row_offset,
     if (!sc || width <= 0 || height <= 0 || rows < 0 || row_stride <= 0 || row_offset < 0 ||
         passes < 0 || max_bounces < 0 || !rng || !accum || first_frame == 0)
         return -1;
-    /* host prelude, Main.cu:336-338 */
-    const float screen_z = -(float)(width / 2) / tanf(sc->camera.fov / 2.0f);
-    mat3 rl = rot_y(sc->camera.angle[0]);
-    mat3 ru = rot_x(sc->camera.angle[1]);
-    mat3 rot = matmul(&rl, &ru);
+    const view3 view = camera_view(sc, width);
     /* Main.cu:291: 0.001 * (windowWidth / 1000), double then float */
 #if ORC_MUTANT == 1
     const float jitter = (float)(0.001 * (width / 1000.0));
@@ -562,13 +598,7 @@ int orc_render_rows(const orc_scene* sc, int width, int height, int row_offset,
             vec3 sum = v3(accum[3 * p], accum[3 * p + 1], accum[3 * p + 2]);
             unsigned frame = first_frame;
             for (int f = 0; f < passes; f++, frame++) {
-#if ORC_MUTANT == 2
-                vec3 pix = v3((float)(x - width / 2) + 0.5f, (float)(y - height / 2) + 0.5f, screen_z);
-#else
-                vec3 pix = v3((float)(x - width / 2), (float)(y - height / 2), screen_z);
-#endif
-                pix = matvec(&rot, pix);                              /* :288 */
-                ray3 cam = {sc->camera.position, normalize3(pix)};
+                ray3 cam = primary_ray(sc, &view, x, y, width, height);
                 cam.direction = add(cam.direction,
                                     scale(jitter, random_direction(st, cam.direction)));
                 cam.direction = normalize3(cam.direction);            /* :292 */
@@ -603,6 +633,48 @@ int orc_render_rows(const orc_scene* sc, int width, int height, int row_offset,
     }
     g_queries = q_total;
     g_paths = p_total;
+    return 0;
+}
+
+/* The first hit of the un-jittered primary ray of every shard pixel: the
+ * camera prelude and the closest-hit loop of the renders, no RNG draw. */
+int orc_first_hit_rows(const orc_scene* sc, int width, int height, int row_offset, int row_stride,
+                       int rows, int32_t* kind, int32_t* index, float* distance,
+                       float* intersection, float* raw_normal, float* unit_normal, float* albedo) {
+    if (!sc || width <= 0 || height <= 0 || rows < 0 || row_stride <= 0 || row_offset < 0 ||
+        !kind || !index || !distance || !intersection || !raw_normal || !unit_normal || !albedo)
+        return -1;
+    const view3 view = camera_view(sc, width);
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 1)
+#endif
+    for (int j = 0; j < rows; j++) {
+        const int y = row_offset + j * row_stride;
+        for (int x = 0; x < width; x++) {
+            const size_t p = (size_t)j * width + x;
+            const ray3 cam = primary_ray(sc, &view, x, y, width, height);
+            hit_info closest;
+            hit_prim which;
+            vec3 unit = v3(0, 0, 0), alb = g_background;
+            if (closest_hit(&cam, sc, &closest, &which)) {
+                /* a sphere's normal is normalised where it is formed
+                 * (Intersection.cuh:60); a plane's and a polygon's is the raw
+                 * cross product (:104), normalised here once */
+                unit = which.kind == ORC_KIND_SPHERE ? closest.normal : normalize3(closest.normal);
+                alb = closest.mat.albedo;
+            }
+            kind[p] = which.kind;
+            index[p] = which.index;
+            distance[p] = closest.distance;
+            const vec3 out[4] = {closest.intersection, closest.normal, unit, alb};
+            float* const dst[4] = {intersection, raw_normal, unit_normal, albedo};
+            for (int k = 0; k < 4; k++) {
+                dst[k][3 * p] = out[k].x;
+                dst[k][3 * p + 1] = out[k].y;
+                dst[k][3 * p + 2] = out[k].z;
+            }
+        }
+    }
     return 0;
 }
 

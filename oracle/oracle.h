@@ -67,8 +67,29 @@ int orc_render_rows(const orc_scene* scene, int width, int height,
                     uint32_t* rng, float* accum, uint8_t* rgba,
                     int init_rng, int threads);
 
+/* The first hit of the un-jittered primary ray (the camera ray of
+ * Main.cu:287-290 before its jitter, no RNG draw) of every shard pixel
+ * p = j*width + x, through the same camera prelude and the same closest-hit
+ * loop (Main.cu:214-234) as orc_render_rows: the plain reference of the
+ * product's first-hit feature buffers (rt_render_aov).  All outputs required:
+ *   kind, index:  which primitive made the last accepted hit (ORC_KIND_*, its
+ *                 index in its own array); ORC_KIND_MISS, -1 on a miss
+ *   distance:     HitInfo.distance (INFINITY on a miss; may be inf or NaN on
+ *                 a hit when the scene's scale overflows the tests)
+ *   intersection, raw_normal: HitInfo.intersection / .normal, 3 floats each
+ *                 (the normal is unit for a sphere, cross(d0, d1) otherwise)
+ *   unit_normal:  raw_normal for a sphere, normalize(raw_normal) otherwise
+ *   albedo:       the hit material's albedo; backgroundColor on a miss
+ * On a miss intersection and both normals are 0.  Returns 0 or -1. */
+enum { ORC_KIND_MISS = -1, ORC_KIND_SPHERE = 0, ORC_KIND_PLANE = 1, ORC_KIND_TRIANGLE = 2, ORC_KIND_QUAD = 3 };
+int orc_first_hit_rows(const orc_scene* scene, int width, int height,
+                       int row_offset, int row_stride, int rows,
+                       int32_t* kind, int32_t* index, float* distance,
+                       float* intersection, float* raw_normal, float* unit_normal,
+                       float* albedo);
+
 /* backgroundColor (Main.cu:27; {0,0,0} in the reference build) used by the
- * next orc_render_rows calls. */
+ * next orc_render_rows / orc_first_hit_rows calls. */
 void orc_set_background(float r, float g, float b);
 
 /* samplesPerPixel (Main.cu:27; 1 in the reference build): the in-frame loop

@@ -44,6 +44,8 @@ def lib():
                                       C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_int]
         L.orc_render_rows.restype = C.c_int
+        L.orc_first_hit_rows.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 7
+        L.orc_first_hit_rows.restype = C.c_int
         L.orc_set_background.argtypes = [C.c_float, C.c_float, C.c_float]
         L.orc_set_background.restype = None
         L.orc_set_samples_per_pixel.argtypes = [C.c_int]
@@ -116,6 +118,35 @@ def render_image(scene, width, height, passes, max_bounces, row_offset=0, row_st
     st = OracleState(width, height, row_offset, row_stride)
     render(scene, st, passes, max_bounces, first_frame=1, threads=threads)
     return st
+
+
+KIND_MISS, KIND_SPHERE, KIND_PLANE, KIND_TRIANGLE, KIND_QUAD = -1, 0, 1, 2, 3
+
+
+def first_hit(scene, width, height, row_offset=0, row_stride=1, background=(0.0, 0.0, 0.0)):
+    """orc_first_hit_rows: the first hit of every shard pixel's un-jittered
+    primary ray, as a dict of arrays shaped like Renderer.render_aov's —
+    "albedo", "normal" (the unit normal) (rows, width, 3) float32, "depth"
+    (rows, width) float32, "prim" (rows, width) int32 in the product's
+    numbering: spheres first, then planes, triangles and quads.  A miss gives
+    prim -1, depth +inf, normal 0 and albedo = `background`.  Beside them the
+    oracle's own record: "kind" (KIND_*), "index" (in the primitive's own
+    array), "point" (the intersection) and "raw_normal"."""
+    rows = len(range(row_offset, height, row_stride))
+    kind = np.empty((rows, width), np.int32)
+    index = np.empty((rows, width), np.int32)
+    depth = np.empty((rows, width), np.float32)
+    point, raw, unit, albedo = (np.empty((rows, width, 3), np.float32) for _ in range(4))
+    lib().orc_set_background(*[float(c) for c in background])
+    rc = lib().orc_first_hit_rows(C.cast(scene.ptr(), C.c_void_p), width, height, row_offset, row_stride, rows,
+                                  *[a.ctypes.data for a in (kind, index, depth, point, raw, unit, albedo)])
+    if rc != 0:
+        raise ValueError("orc_first_hit_rows: bad arguments")
+    ns, npl, nt, _ = scene.counts
+    base = np.array([0, ns, ns + npl, ns + npl + nt], np.int32)
+    prim = np.where(kind < 0, np.int32(-1), base[np.maximum(kind, 0)] + index).astype(np.int32)
+    return {"albedo": albedo, "normal": unit, "depth": depth, "prim": prim,
+            "kind": kind, "index": index, "point": point, "raw_normal": raw}
 
 
 def last_counters():
