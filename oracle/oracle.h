@@ -7,14 +7,21 @@
  * thing measured or shipped.  The product (libbwrt.so) does not link it and
  * has no CPU fallback.
  *
- * Parity pinning: the reference cannot be built here
- * (its kernel needs CUDA headers — cuda_runtime.h, curand_kernel.h,
- * host_defines.h — that the image lacks), so this restatement is pinned by
- * the reference's own rendered outputs: Renders/01_red_circle.png (disc
- * geometry) and Renders/07_specular_BRDF.png (converged image, block means),
- * through fixtures under tests/golden/.  The exact cuRAND stream and the
- * nvcc --use_fast_math transcendentals are NOT pinnable (parity unpinned for
- * those two aspects; statistical parity only).
+ * Parity pinning, two ways:
+ *  - to the reference's own source text: Main.cu and its headers compile
+ *    unmodified as host C++ over this project's stand-in CUDA / GLFW headers
+ *    (recipe oracle/ref/ -> oracle/_ref/libreftext.so, never committed), and
+ *    tests/test_reference_text.py holds this restatement — and the product's
+ *    CPU fallback — bit for bit to that library, every ORC_MUTANT rejected.
+ *    Under the stand-ins' assumptions: float min / max are fminf / fmaxf, the
+ *    device sin / cos / atan are orc_sinf / orc_cosf / orc_atanf below,
+ *    curand_init / curand are orc_curand_init / orc_curand below;
+ *  - to the reference's rendered outputs: Renders/01_red_circle.png (disc
+ *    geometry) and Renders/07_specular_BRDF.png (converged image, block
+ *    means), through fixtures under tests/golden/.
+ * The exact cuRAND stream and the nvcc --use_fast_math transcendentals are NOT
+ * pinned by either (both sides of the first comparison share this file's
+ * restatement of them; statistical parity only, through the PNGs).
  */
 #ifndef BWRT_ORACLE_H
 #define BWRT_ORACLE_H

@@ -44,6 +44,27 @@ def _random_scene(seed):
     return scenes.Scene(cam, sph, pln, tri, quads, name=f"random{seed}")
 
 
+def guard_scene(roughness=1e20, base=scenes.scene_04_box):
+    """The scene on which the reference's `if (isnan(g)) return 1` guard
+    (Main.cu:139) decides pixels: `base` (04_box: spheres, a plane and mirror
+    quads) with every material's roughness set to `roughness`.  At 1e20
+    roughness^2 overflows to +inf (so does inf itself).  On a plane or polygon
+    whose un-normalised normal is longer than 1, v.n can exceed 1, tanTheta
+    clamps to 0 (Main.cu:116) and inf * 0 * 0 makes G1 and so g NaN: with the
+    guard the specular weight is 1 and the frame stays finite; without it
+    about half the pixels of the frame go NaN."""
+    s = base()
+    for arr, n in zip((s.spheres, s.planes, s.triangles, s.quads), s.counts):
+        for i in range(n):
+            arr[i].mat.roughness = roughness
+    s.name = f"guard_{s.name}_{roughness:g}"
+    return s
+
+
+def guard_scene_inf():
+    return guard_scene(float("inf"))
+
+
 def _scaled(scene, k):
     """The same scene with every coordinate (camera, primitives) times k."""
     for arr, n in zip((scene.spheres, scene.planes, scene.triangles, scene.quads), scene.counts):

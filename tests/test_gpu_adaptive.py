@@ -71,6 +71,17 @@ def test_max_bounces(bwrt_lib, bounces, kernel):
     both(bwrt_lib, scenes.scene_07(), 67, 45, bounces, kernel=kernel)
 
 
+def test_guard_scene(bwrt_lib):
+    """The scene on which the reference's isnan(g) guard (Main.cu:139) decides
+    half the pixels (scenegen.guard_scene; tests/test_reference_text.py pins the
+    CPU backend on it to the reference's own text): a list kernel that lost the
+    guard would leave NaN in frameSum where the CPU backend has none."""
+    from scenegen import guard_scene
+    got, _ = both(bwrt_lib, guard_scene(), 160, 90, 4, kernel="rt_render_list_kernel<256")
+    assert np.isfinite(got["accum"]).all()
+    assert got["stats"][0][0] > 0  # the list kernels did run
+
+
 def test_samples_per_pixel(bwrt_lib):
     both(bwrt_lib, scenes.scene_07(), 67, 45, 4, kernel="rt_render_kernel<256,list>", spp=2)
 

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from bwrt import scenes
-from scenegen import _random_scene, _scaled
+from scenegen import _random_scene, _scaled, guard_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -946,6 +946,60 @@ def test_simple_kernel_ab_reference(bwrt_lib, oracle, monkeypatch, name):
     scene = {"07": scenes.scene_07, "04_box": scenes.scene_04_box}[name]()
     try:
         img, st = run_pair(r, oracle, scene, 200, 113, 3, 5)
+        assert np.array_equal(img, st.rgba)
+        same_state(r, st)
+    finally:
+        r.close()
+
+
+# The isnan(g) guard of specularWeight (Main.cu:139) decides a pixel only on a
+# scene that makes g NaN; scenegen.guard_scene is one (roughness^2 = inf times a
+# tanTheta clamped to 0 on the box's planes and quads: about half the pixels of
+# this frame without the guard, tests/test_reference_text.py mutant 6).  No
+# other scene of the suite can tell a kernel that lost the guard, so it runs
+# through every kernel that has the path arithmetic.
+# (id, knobs read at rt_create, scene options read at rt_set_scene, max_bounces, kernel name prefix)
+GUARD_KERNELS = [
+    ("policy", {}, {}, 4, None),
+    ("pair", {"BWRT_SPREAD": 1}, {}, 4, "rt_render_pair_kernel<"),
+    ("sorted", {"BWRT_SPREAD": 0}, {}, 4, "rt_render_sorted_kernel<"),
+    ("grec64", {"BWRT_GREC": 1, "BWRT_BLOCK": 64}, {}, 4, "rt_render_sorted_kernel<64,grec"),
+    ("grec256", {"BWRT_GREC": 1, "BWRT_BLOCK": 256}, {}, 4, "rt_render_sorted_kernel<256,grec"),
+    ("simple", {"BWRT_KERNEL": "simple"}, {}, 4, "rt_render_kernel<"),
+    ("bvh_refill", {}, {"BWRT_BVH_MIN": 1}, 4, "rt_render_bvh_refill_kernel<"),
+    ("policy_deep_records", {}, {}, 6, None),
+]
+_guard_states = {}
+
+
+def _guard_oracle(oracle, roughness, mb):
+    """The oracle's 160x90, 3-frame render of the guard scene: once per
+    (roughness, bounce limit), shared and read-only."""
+    key = (roughness, mb)
+    if key not in _guard_states:
+        st = oracle.render_image(guard_scene(roughness), 160, 90, 3, mb)
+        for a in (st.rng, st.accum, st.rgba):
+            a.setflags(write=False)
+        _guard_states[key] = st
+    return _guard_states[key]
+
+
+@pytest.mark.parametrize("roughness", [1e20, float("inf")])
+@pytest.mark.parametrize("cid,env,scene_env,mb,kernel", GUARD_KERNELS, ids=[c[0] for c in GUARD_KERNELS])
+def test_isnan_guard_scene(bwrt_lib, oracle, monkeypatch, cid, env, scene_env, mb, kernel, roughness):
+    st = _guard_oracle(oracle, roughness, mb)
+    assert np.isfinite(st.accum).all()  # with the guard, no pixel goes NaN
+    r = _fresh_renderer(bwrt_lib, monkeypatch, **env)
+    try:
+        for k, v in scene_env.items():
+            monkeypatch.setenv(k, str(v))
+        r.set_scene(guard_scene(roughness))
+        for k in scene_env:
+            monkeypatch.delenv(k)
+        r.init_rand(160, 90)
+        img = r.render(160, 90, 3, mb, first_frame=1)
+        if kernel:
+            assert_kernel(r, kernel)
         assert np.array_equal(img, st.rgba)
         same_state(r, st)
     finally:

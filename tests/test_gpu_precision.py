@@ -16,6 +16,7 @@ import pytest
 
 import sky_cases
 from bwrt import Renderer, scenes
+from scenegen import guard_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -25,7 +26,8 @@ WITHIN_1LSB_MIN = 0.995
 MEAN_ABS_MAX = 0.25
 
 SCENES = {"07": scenes.scene_07, "04_box": scenes.scene_04_box, "stress": scenes.stress_scene,
-          "07_yaw_pitch": lambda: sky_cases.with_camera(scenes.scene_07(), 0.5, 0.3)}
+          "07_yaw_pitch": lambda: sky_cases.with_camera(scenes.scene_07(), 0.5, 0.3),
+          "guard": guard_scene}
 
 
 @functools.lru_cache(maxsize=None)
@@ -82,12 +84,23 @@ CASES = [
      {"BWRT_SPREAD": 0, "BWRT_SKY": 1, "BWRT_ORDER_PERIOD": 2}, "rt_render_sorted_kernel<"),
     # the box's shared edges (exact ties in EXACT) through the BVH
     ("bvh_forced_box", "04_box", 320, 180, 4, 5, 0, 1, {}, "rt_render_bvh_refill_kernel<"),
+    # the scene on which the isnan(g) guard decides half the pixels (scenegen.guard_scene): the fast
+    # twins must keep the guard, so no pixel of the frame may be non-finite: the policy's kernel, the
+    # sorted kernel with global records, the simple kernel and the BVH refill kernel
+    ("isnan_guard", "guard", 160, 90, 3, 4, 0, 1, {}, None),
+    ("isnan_guard_sorted", "guard", 160, 90, 3, 4, 0, 1, {"BWRT_SPREAD": 0, "BWRT_GREC": 1}, "rt_render_sorted_kernel<"),
+    ("isnan_guard_simple", "guard", 160, 90, 3, 4, 0, 1, {"BWRT_KERNEL": "simple"}, "rt_render_kernel<"),
+    ("isnan_guard_bvh", "guard", 160, 90, 3, 4, 0, 1, {}, "rt_render_bvh_refill_kernel<"),
 ]
 # what a case needs beyond its launch knobs: the frames of each render call, the background, the
 # scene-compile options (read at rt_set_scene) and the end of the last launch's kernel name
 EXTRA = {
     "sky_order_second_launch": {"split": (3, 5), "background": sky_cases.BG, "ends": "+sky"},
     "bvh_forced_box": {"scene_env": {"BWRT_BVH_MIN": 1}},
+    "isnan_guard": {"finite": True},
+    "isnan_guard_sorted": {"finite": True},
+    "isnan_guard_simple": {"finite": True},
+    "isnan_guard_bvh": {"finite": True, "scene_env": {"BWRT_BVH_MIN": 1}},
 }
 
 
@@ -113,10 +126,14 @@ def test_fast_within_tolerance(bwrt_lib, monkeypatch, cid, name, w, h, spp, mb, 
         for i, n in enumerate(split or (spp,)):
             img = r.render(w, h, n, mb, first_frame=1 if i == 0 else 0, row_offset=off, row_stride=stride)
         kernel = r.last_kernel_name()
-        rng, _ = r.get_state(st.rows, st.width)
+        rng, acc = r.get_state(st.rows, st.width)
     finally:
         r.close()
     assert img.shape == st.rgba.shape
+    if extra.get("finite"):
+        bad = int((~np.isfinite(acc)).any(-1).sum())
+        print(f"\nFASTSTAT {cid}: non-finite pixels {bad} (exact oracle: {int((~np.isfinite(st.accum)).any(-1).sum())})")
+        assert bad == 0, bad
     within, mean = _stats(img, st)
     desync = float((rng != st.rng).any(0).mean())
     print(f"\nFASTSTAT {cid}: kernel {kernel} within_1lsb {within * 100:.4f} % mean_abs {mean:.5f} LSB "
