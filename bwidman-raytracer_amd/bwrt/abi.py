@@ -191,6 +191,12 @@ def _proto(lib):
         "rt_render_adaptive_device": (C.c_int, [vp, P(AdaptiveParams), C.c_int, vp, vp]),
         "rt_adaptive_last_stats": (C.c_int, [vp, P(AdaptiveStats)]),
         "rt_get_counts": (C.c_int, [vp, vp, vp]),
+        "rt_adaptive_export_rows": (C.c_int, [vp, P(AdaptiveParams), C.c_int, vp]),
+        "rt_adaptive_export_rows_device": (C.c_int, [vp, P(AdaptiveParams), C.c_int, vp, vp]),
+        "rt_render_adaptive_shard": (C.c_int, [vp, P(AdaptiveParams), C.c_int, vp, C.c_int, C.c_int, vp, vp,
+                                               P(AdaptiveStats)]),
+        "rt_render_adaptive_shard_device": (C.c_int, [vp, P(AdaptiveParams), C.c_int, vp, C.c_int, C.c_int, vp, vp]),
+        "rt_render_adaptive_multi": (C.c_int, [P(vp), C.c_int, P(AdaptiveParams), C.c_int, vp, P(AdaptiveStats)]),
         "rt_export_shard": (C.c_int, [vp, C.c_int, C.c_int, vp, P(C.c_uint), P(C.c_uint)]),
         "rt_export_shard_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, P(C.c_uint), P(C.c_uint)]),
         "rt_assemble": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint]),

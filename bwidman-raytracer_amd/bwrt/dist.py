@@ -123,3 +123,54 @@ def gather_frame(renderer, plan: ShardPlan, width: int, planes: int = 3, group=N
         if root:
             renderer.assemble_device(gathered.data_ptr(), plan.world, rps, planes, frames, batches, s.cuda_stream)
     return root
+
+
+def render_adaptive(renderer, plan: ShardPlan, width: int, max_bounces: int = -1, group=None, stream=None, **params):
+    """One adaptive call across the ranks' row shards:
+    rt_adaptive_export_rows -> all_gather -> rt_render_adaptive_shard.  Only
+    the window's row sums cross ranks, 12 bytes per frame pixel to every rank;
+    afterwards the ranks hold, interleaved, the counts, frameSum and RNG state
+    of one renderer that ran render_adaptive on the whole frame.  `params` are
+    Renderer.adaptive_params() fields.  A rank with no rows contributes a zero
+    block and skips phase 2.
+
+    A CPU renderer goes through host tensors (gloo) and returns (RGBA8 rows,
+    stats), or None without rows.  A GPU renderer exports, gathers (RCCL) and
+    renders on `stream` (a torch.cuda.Stream; None = torch's current one)
+    without a host synchronisation and returns its RGBA8 rows as a uint8 device
+    tensor (rows, width, 4), or None without rows."""
+    import torch
+    import torch.distributed as dist
+    rps = plan.rows_per_shard
+    if renderer.is_cpu:
+        block = torch.zeros((3, rps, width), dtype=torch.float32)
+        if plan.rows > 0:
+            block.copy_(torch.from_numpy(renderer.adaptive_export_rows(rps, width, **params)))
+        gathered = torch.empty((plan.world, 3, rps, width), dtype=torch.float32)
+        # (float32 tensors are copied as bytes: plane 2's integers and any float's bits survive)
+        dist.all_gather(list(gathered.unbind(0)), block, group=group)
+        if plan.rows == 0:
+            return None
+        return renderer.render_adaptive_shard(gathered.numpy(), plan.rows, width, max_bounces, **params)
+    dev = torch.device("cuda", renderer.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        if plan.rows > 0:
+            block = torch.empty((3, rps, width), dtype=torch.float32, device=dev)
+            renderer.adaptive_export_rows_device(block.data_ptr(), rps, s.cuda_stream, **params)
+        else:
+            block = torch.zeros((3, rps, width), dtype=torch.float32, device=dev)
+        gathered = torch.empty((plan.world, 3, rps, width), dtype=torch.float32, device=dev)
+        if dist.get_backend(group) == "gloo":
+            # rehearsal of the GPU path over gloo: stage through the host
+            host = torch.empty(gathered.shape, dtype=torch.float32)
+            dist.all_gather(list(host.unbind(0)), block.cpu(), group=group)
+            gathered.copy_(host)
+        else:
+            dist.all_gather_into_tensor(gathered, block, group=group)
+        if plan.rows == 0:
+            return None
+        rgba = torch.empty((plan.rows, width, 4), dtype=torch.uint8, device=dev)
+        renderer.render_adaptive_shard_device(gathered.data_ptr(), plan.world, rps, rgba.data_ptr(), s.cuda_stream,
+                                              max_bounces, **params)
+    return rgba

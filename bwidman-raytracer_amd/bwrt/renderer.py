@@ -409,6 +409,50 @@ class Renderer:
         self._check(self.lib.rt_get_counts(self.ctx, n.ctypes.data, j.ctypes.data))
         return n, j
 
+    # -- adaptive sampling on row shards (two phases around an all-gather) -------
+    def adaptive_export_rows(self, rows_per_shard, width, **params):
+        """rt_adaptive_export_rows, phase 1: the window's row sums of this
+        context's own rows, a (3, rows_per_shard, width) float32 block — sum v,
+        sum M, and the tap counts as int32 bits (block[2].view(np.int32)) — the
+        shard's rows first, zero rows after them.  Changes nothing of the
+        accumulation; `params` as render_adaptive's (the radius matters)."""
+        d = self.adaptive_params(**params)
+        block = np.empty((3, rows_per_shard, width), np.float32)
+        self._check(self.lib.rt_adaptive_export_rows(self.ctx, C.byref(d), rows_per_shard, block.ctypes.data))
+        return block
+
+    def adaptive_export_rows_device(self, block_ptr: int, rows_per_shard, stream_ptr: int | None = None, **params):
+        """rt_adaptive_export_rows_device: the block into device memory on a
+        stream (asynchronous, ordered like export_shard_device)."""
+        d = self.adaptive_params(**params)
+        self._check(self.lib.rt_adaptive_export_rows_device(self.ctx, C.byref(d), rows_per_shard, block_ptr, stream_ptr))
+
+    def render_adaptive_shard(self, gathered, rows, width, max_bounces=-1, want_color=False, **params):
+        """rt_render_adaptive_shard, phase 2: select this context's rows from
+        `gathered`, (shards, 3, rows_per_shard, width) float32 on the host
+        (block r = rows r, r + shards, ...), then render, update and resolve
+        them.  Returns the shard's `rows` rows in shard order like
+        render_adaptive: (RGBA8, stats) or (RGBA8, colour, stats)."""
+        d = self.adaptive_params(**params)
+        g = np.ascontiguousarray(gathered, dtype=np.float32)
+        shards, _, rps, _ = g.shape
+        out = np.empty((rows, width, 4), np.uint8)
+        col = np.empty((rows, width, 3), np.float32) if want_color else None
+        st = abi.AdaptiveStats()
+        self._check(self.lib.rt_render_adaptive_shard(self.ctx, C.byref(d), max_bounces, g.ctypes.data, shards, rps,
+                                                      out.ctypes.data, col.ctypes.data if col is not None else None,
+                                                      C.byref(st)))
+        return (out, col, self._stats(st)) if want_color else (out, self._stats(st))
+
+    def render_adaptive_shard_device(self, gathered_ptr: int, shards, rows_per_shard, rgba_ptr: int | None = None,
+                                     stream_ptr: int | None = None, max_bounces=-1, **params):
+        """rt_render_adaptive_shard_device: phase 2 from device memory with its
+        RGBA8 rows into device memory on a stream (asynchronous, no host
+        synchronisation; the caller orders the gather before it)."""
+        d = self.adaptive_params(**params)
+        self._check(self.lib.rt_render_adaptive_shard_device(self.ctx, C.byref(d), max_bounces, gathered_ptr, shards,
+                                                             rows_per_shard, rgba_ptr, stream_ptr))
+
     def set_adaptive_filters(self, enable: bool = True):
         """rt_set_adaptive_filters: let denoise, denoise_var and temporal (and
         their _device forms) run on a non-uniform accumulation, each pixel
@@ -519,3 +563,19 @@ def assemble_multi(renderers, planes: int = 0, dst: int = 0):
     if rc != abi.RT_OK:
         renderers[dst if 0 <= dst < len(renderers) else 0]._check(rc)
     return renderers[dst].assembled()
+
+
+def render_adaptive_multi(renderers, width: int, height: int, max_bounces=-1, **params):
+    """rt_render_adaptive_multi, beside render_multi: one adaptive call across
+    the Renderers' row shards (export the row sums, copy every block to every
+    renderer, select, render, resolve).  Returns ((H, W, 4) uint8 with row 0 =
+    bottom, stats dict: selected and frames_total summed, stage times maxima)."""
+    lib = renderers[0].lib
+    arr = (C.c_void_p * len(renderers))(*[r.ctx.value for r in renderers])
+    d = renderers[0].adaptive_params(**params)
+    out = np.empty((height, width, 4), np.uint8)
+    st = abi.AdaptiveStats()
+    rc = lib.rt_render_adaptive_multi(arr, len(renderers), C.byref(d), max_bounces, out.ctypes.data, C.byref(st))
+    if rc != abi.RT_OK:
+        renderers[0]._check(rc)
+    return out, Renderer._stats(st)

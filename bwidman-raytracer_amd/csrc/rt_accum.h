@@ -8,7 +8,9 @@
 // accumulated), the tracking switch, live / batches / next (tracking follows
 // the accumulation, over `batches` render calls, up to frame next - 1), the
 // non-uniform flag (the context's ad_cnt holds {n_p, J_p} per pixel) with
-// max_n >= every n_p, and the filter switch (rt_set_adaptive_filters).
+// max_n >= every n_p, the filter switch (rt_set_adaptive_filters), and the
+// radius of the current row-sum export (rt_adaptive_export_rows, the first
+// phase of an adaptive call on row shards; -1: none).
 //
 //   event                                  effect
 //   rt_set_scene (on success)              frame 1; non-uniform ends; tracking untouched
@@ -32,6 +34,11 @@
 //   adaptive call done                     first of an accumulation: max_n = next - 1; then
 //                                          max_n += samples; non-uniform; frame, batches, next unchanged
 //   adaptive launch failure                tracking and non-uniform end
+//   row-sum export done                    the export is current, with its radius; nothing else
+//
+// The row-sum export describes the moments and counts it was made from: it ends
+// with every restart (scene, camera, reset), with the tracking, with a uniform
+// render that is not refused and with an adaptive call.
 //
 // "Tracking ends" always takes the non-uniform state with it: the counts go
 // with the moments they belong to.  Between a restart (frame 1) and the next
@@ -46,6 +53,7 @@ class rt_accum_state {
     unsigned batches_ = 0, next_ = 0;
     bool nonuniform_ = false, filters_ = false;
     unsigned long long max_n_ = 0;
+    int export_radius_ = -1;
 
 public:
     // ---- queries ---------------------------------------------------------------
@@ -62,14 +70,20 @@ public:
     // no n_p exceeds it: what an adaptive call's `samples` must not carry past 2^32 - 1
     // (J_p <= n_p: a batch has at least one frame)
     unsigned long long adaptive_base() const { return nonuniform_ ? max_n_ : (unsigned long long)(next_ - 1u); }
+    // the context's last row-sum export, made with `radius`, still describes the moments and counts
+    bool export_current(int radius) const { return export_radius_ >= 0 && export_radius_ == radius && current(); }
 
     // ---- transitions -----------------------------------------------------------
-    void restart() { frame_ = 1; }
+    void restart() {
+        frame_ = 1;
+        export_radius_ = -1;
+    }
     void end_nonuniform() { nonuniform_ = false; }
     void end_tracking() {
         live_ = false;
         batches_ = 0;
         nonuniform_ = false;
+        export_radius_ = -1;
     }
     void set_frame(unsigned fc) {
         frame_ = fc;
@@ -88,7 +102,9 @@ public:
         first = first_frame ? first_frame : frame_;
         if (nonuniform_ && first != 1u) return Start::nonuniform;
         nonuniform_ = false;
-        return (unsigned long long)first + (unsigned)samples > 0xffffffffull ? Start::overflow : Start::ok;
+        if ((unsigned long long)first + (unsigned)samples > 0xffffffffull) return Start::overflow;
+        export_radius_ = -1;
+        return Start::ok;
     }
     bool uniform_track(unsigned first) {
         const bool track = switch_ && (first == 1u || (live_ && first == next_));
@@ -105,5 +121,7 @@ public:
     void adaptive_done(int samples) {
         max_n_ = adaptive_base() + (unsigned)samples;
         nonuniform_ = true;
+        export_radius_ = -1;
     }
+    void export_done(int radius) { export_radius_ = radius; }
 };

@@ -74,6 +74,42 @@ RT_HD bool ad_selected(const rt_ad_args& A, int x, int y, long p) {
     return c > 0 && (sv * cf) > (b * b);
 }
 
+// ad_selected for pixel x of shard row j (p = j * width + x in the shard; image
+// row y = row_offset + j * shards): the same clauses in the same order, n_p from
+// the shard's own counts, the column taps in increasing image y from the ranks'
+// gathered row sums (rt_layout.h, rt_ad_shard_args) — the same float additions,
+// so the shards select, interleaved, what one full-frame context selects.  The
+// block and the row inside it advance per tap without a division: one division
+// per pixel, wave-uniform on the device (the kernel hands in a uniform j).
+RT_HD bool ad_selected_shard(const rt_ad_shard_args& S, int x, int j, long p) {
+    const rt_ad_args& A = S.A;
+    const unsigned n = A.cnt[p].x;
+    if (A.max_frames != 0u && (unsigned long long)n + (unsigned)A.k > A.max_frames) return false;
+    if (n < A.min_frames) return true;
+    float sv = 0.0f, sm = 0.0f;
+    int c = 0;
+    const int y = S.row_offset + j * S.shards;
+    const int y0 = y - A.radius < 0 ? 0 : y - A.radius;
+    const int y1 = y + A.radius >= S.image_height ? S.image_height - 1 : y + A.radius;
+    const long plane = (long)S.rows_per_shard * A.width;
+    const int* taps = reinterpret_cast<const int*>(S.gathered);  // plane 2 holds integers
+    int qj = y0 / S.shards;       // the tap row's row inside its block
+    int r = y0 - qj * S.shards;   // and its block
+    for (int qy = y0; qy <= y1; qy++) {
+        const long q = ((long)r * 3 * S.rows_per_shard + qj) * A.width + x;
+        sv = sv + S.gathered[q];
+        sm = sm + S.gathered[q + plane];
+        c += taps[q + 2 * plane];
+        if (++r == S.shards) {
+            r = 0;
+            qj++;
+        }
+    }
+    const float cf = (float)c;
+    const float b = A.tolerance * (sm + cf * A.lum_floor);
+    return c > 0 && (sv * cf) > (b * b);
+}
+
 // the moment step of listed pixel p behind its k new frames (rt_moments.h's
 // with the pixel's own weight), and its counts
 RT_HD void ad_update(const rt_ad_args& A, long p) {

@@ -11,6 +11,11 @@
 // ballot) with its popcount, one workgroup scans the popcounts, and the scatter
 // writes pixel indices in ascending order — no atomic decides a position, so
 // the list is the same every time.
+//
+// On a row shard the row sums go into the context's
+// block for the ranks' all-gather (rt_launch_adaptive_rows_block) and the test
+// reads its column taps from the gathered blocks (rt_launch_adaptive_shard);
+// scan, scatter, update and resolve are the same kernels over the shard's rows.
 #include <hip/hip_runtime.h>
 
 #include "rt_adaptive.h"
@@ -111,6 +116,36 @@ __global__ void __launch_bounds__(256) rt_adaptive_resolve_kernel(const rt_ad_ar
     if (p < A.npix) ad_resolve(A, p);
 }
 
+// rt_adaptive_test_kernel on a row shard: one wave per mask word of a shard
+// row, the column taps from the ranks' gathered row sums (ad_selected_shard).
+// The word index goes through readfirstlane, so the shard row, the image row
+// and every tap row's block and row inside it (one division by `shards` per
+// wave, then increments) are scalar: a lane adds its x and loads.
+__global__ void __launch_bounds__(256) rt_adaptive_test_shard_kernel(const rt_ad_shard_args S) {
+    const rt_ad_args& A = S.A;
+    const long wl = ((long)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const long nwords = (long)A.words_per_row * A.height;
+    if (wl >= nwords) return;  // wave-uniform
+    const int wi = __builtin_amdgcn_readfirstlane((int)wl);  // nwords <= npix < 2^31
+    const int j = wi / A.words_per_row;
+    const int x = (wi - j * A.words_per_row) * 64 + (int)(threadIdx.x & 63);
+    const bool sel = x < A.width && ad_selected_shard(S, x, j, (long)j * A.width + x);
+    const unsigned long long m = __ballot(sel);
+    if ((threadIdx.x & 63) == 0) {
+        A.mask[wi] = m;
+        A.pop[wi] = (unsigned)__popcll(m);
+    }
+}
+
+// the padding rows of a row-sum block: words used .. plane - 1 of each of its 3 planes
+__global__ void __launch_bounds__(256) rt_adaptive_pad_kernel(unsigned* block, long used, long plane) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long pad = plane - used;
+    if (i >= 3 * pad) return;
+    const long k = i / pad;
+    block[k * plane + used + (i - k * pad)] = 0u;
+}
+
 unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -137,5 +172,30 @@ hipError_t rt_launch_adaptive(const rt_ad_args& A, int stage, hipStream_t stream
     } else {
         hipLaunchKernelGGL(rt_adaptive_resolve_kernel, dim3(blocks_of(A.npix)), dim3(256), 0, stream, A);
     }
+    return hipGetLastError();
+}
+
+// The row sums of a shard's own rows (A.rowv / rowm / rowc aimed at the planes
+// of its block of `plane` words each, A.height = its rows), then the block's
+// padding rows
+hipError_t rt_launch_adaptive_rows_block(const rt_ad_args& A, long plane, hipStream_t stream) {
+    if (A.npix <= 0 || A.npix > 0x7fffffffl || !A.cnt || !A.rowv || plane < A.npix) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rt_adaptive_rows_kernel, dim3(blocks_of(A.npix)), dim3(256), 0, stream, A);
+    if (plane > A.npix)
+        hipLaunchKernelGGL(rt_adaptive_pad_kernel, dim3(blocks_of(3 * (plane - A.npix))), dim3(256), 0, stream,
+                           reinterpret_cast<unsigned*>(A.rowv), A.npix, plane);
+    return hipGetLastError();
+}
+
+// stage 1 of a shard: the sharded test, then the scan and the scatter as ever
+hipError_t rt_launch_adaptive_shard(const rt_ad_shard_args& S, hipStream_t stream) {
+    const rt_ad_args& A = S.A;
+    if (A.npix <= 0 || A.npix > 0x7fffffffl || !A.cnt || !S.gathered || S.shards < 1 ||
+        (long)S.rows_per_shard * S.shards < S.image_height || S.row_offset + (long)(A.height - 1) * S.shards >= S.image_height)
+        return hipErrorInvalidValue;
+    const long nwords = (long)A.words_per_row * A.height;
+    hipLaunchKernelGGL(rt_adaptive_test_shard_kernel, dim3(blocks_of(nwords * 64)), dim3(256), 0, stream, S);
+    hipLaunchKernelGGL(rt_adaptive_scan_kernel, dim3(1), dim3(1024), 0, stream, A);
+    hipLaunchKernelGGL(rt_adaptive_scatter_kernel, dim3(blocks_of(nwords * 64)), dim3(256), 0, stream, A);
     return hipGetLastError();
 }

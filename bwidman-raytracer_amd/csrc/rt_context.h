@@ -45,6 +45,10 @@ int rt_cpu_render(const rt_kparams& K, int threads);
 // adaptive sampling on the host (rt_adaptive.h): selection into A.list /
 // *A.list_n, the listed pixels' frames, their update, the resolve pass
 void rt_cpu_adaptive_select(const rt_ad_args& A, int threads);
+// on row shards: the row sums of the shard's rows into its block, and the
+// selection from the gathered blocks
+void rt_cpu_adaptive_rows_block(const rt_ad_args& A, long plane, int threads);
+void rt_cpu_adaptive_select_shard(const rt_ad_shard_args& S, int threads);
 void rt_cpu_adaptive_render(const rt_kparams& K, const rt_ad_args& A, int threads);
 void rt_cpu_adaptive_finish(const rt_ad_args& A, int threads);
 void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride);
@@ -72,6 +76,11 @@ hipError_t rt_launch_assemble(const rt_asm_args& A, int max_blocks, hipStream_t 
 hipError_t rt_launch_adaptive_fill(uint2* cnt, unsigned long long* total, long npix, unsigned n, unsigned J,
                                    hipStream_t stream);
 hipError_t rt_launch_adaptive(const rt_ad_args& A, int stage, hipStream_t stream);
+// adaptive sampling on row shards: the row sums of a shard's rows into its block
+// (planes of `plane` words, padding rows zeroed), and stage 1 with the column
+// taps from the gathered blocks
+hipError_t rt_launch_adaptive_rows_block(const rt_ad_args& A, long plane, hipStream_t stream);
+hipError_t rt_launch_adaptive_shard(const rt_ad_shard_args& S, hipStream_t stream);
 
 // ---- buffers -------------------------------------------------------------------
 // Device memory on a GPU context, host memory on a CPU context (ensure_buf);
@@ -313,6 +322,11 @@ struct rt_context {
     // kernel timing on.
     int ad_kernel = 0;  // BWRT_ADAPTIVE_KERNEL: 1 simple, 2 queued, 0 = launch policy
     Buf ad_cnt, ad_rows, ad_mask, ad_pop, ad_list, ad_stat, ad_color;
+    // on row shards (rt_adaptive_export_rows, rt_render_adaptive_shard): this
+    // context's row-sum block and the gathered blocks, staging of the host
+    // forms and of rt_render_adaptive_multi.  Whether the last export is still
+    // current is `st`'s to say.
+    Buf ad_block, ad_gather;
     hipEvent_t ad_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool ad_timed = false;
     float ad_cpu_ms[3] = {-1.0f, -1.0f, -1.0f};

@@ -373,6 +373,27 @@ void rt_cpu_adaptive_select(const rt_ad_args& A, int threads) {
     *A.total = *A.total + (unsigned long long)n * (unsigned)A.k;
 }
 
+// A shard's row sums into its block, padding rows zeroed
+void rt_cpu_adaptive_rows_block(const rt_ad_args& A, long plane, int threads) {
+    parallel_pixels(A.width, A.height, threads, [&](int x, int y, long p) { ad_row_sums(A, x, y, p); });
+    for (int k = 0; k < 3; k++)
+        for (long i = A.npix; i < plane; i++) A.rowv[k * plane + i] = 0.0f;  // (+0.0f: all bits zero, plane 2's int 0 too)
+}
+
+// The selection of a shard from the gathered blocks: every pixel's flag depends
+// on that pixel alone, the list is made by one thread in ascending order
+void rt_cpu_adaptive_select_shard(const rt_ad_shard_args& S, int threads) {
+    const rt_ad_args& A = S.A;
+    std::vector<unsigned char> flags((size_t)A.npix);
+    parallel_pixels(A.width, A.height, threads,
+                    [&](int x, int j, long p) { flags[(size_t)p] = ad_selected_shard(S, x, j, p) ? 1 : 0; });
+    unsigned n = 0;
+    for (long p = 0; p < A.npix; p++)
+        if (flags[(size_t)p]) A.list[n++] = (int)p;
+    *A.list_n = n;
+    *A.total = *A.total + (unsigned long long)n * (unsigned)A.k;
+}
+
 // A.k more frames of every listed pixel, each from its own frame count
 void rt_cpu_adaptive_render(const rt_kparams& K, const rt_ad_args& A, int threads) {
     parallel_items((long)*A.list_n, threads, [&](long i) {

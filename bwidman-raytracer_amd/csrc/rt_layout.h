@@ -322,3 +322,20 @@ struct rt_ad_args {
     unsigned* rgba;          // resolve: tone_map(frameSum, n_p) (may be null)
     float* color;            // resolve: rt_div(1, n_p) * frameSum, interleaved r,g,b (may be null)
 };
+
+// The selection of an adaptive call on a row shard (rt_adaptive.h,
+// ad_selected_shard): A describes the shard (height = its rows, npix = rows *
+// width; rowv / rowm / rowc unused), the column taps come from the ranks'
+// gathered row-sum blocks.  A block is 3 planes of rows_per_shard * width
+// 32-bit words (sum v float, sum M float, tap count int32), the shard's rows in
+// shard order, then zero padding rows; `gathered` is `shards` blocks, so word k
+// of image pixel (x, y) is
+//   gathered[(((y % shards) * 3 + k) * rows_per_shard + y / shards) * width + x].
+// The existing kernels take rt_ad_args alone: its layout stays as it is.
+struct rt_ad_shard_args {
+    rt_ad_args A;
+    const float* gathered;
+    int shards, rows_per_shard;
+    int image_height;        // of the whole frame: the window clips there
+    int row_offset;          // shard row j is image row row_offset + j * shards
+};

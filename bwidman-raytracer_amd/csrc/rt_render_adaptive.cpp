@@ -1,20 +1,28 @@
 // rt_render_adaptive.cpp — variance-driven adaptive sampling at the C ABI
 // (include/rt_abi.h): rt_render_adaptive*, rt_adaptive_last_stats,
-// rt_get_counts.  csrc/rt_adaptive.h has the selection's arithmetic,
-// rt_adaptive.hip and rt_kernel_list.h the kernels, rt_cpu.cpp their host twins.
+// rt_get_counts, and the two-phase form on row shards (rt_adaptive_export_rows*,
+// rt_render_adaptive_shard*, rt_render_adaptive_multi).
+// csrc/rt_adaptive.h has the selection's arithmetic, rt_adaptive.hip and
+// rt_kernel_list.h the kernels, rt_cpu.cpp their host twins.
 //
 // One call is, on one stream and inside one render pass (so every later call
 // is ordered after all of it): [count fill, the first call of an accumulation]
 // row sums, column sums + test + scan + scatter, the list render kernel, the
 // moment update of the listed pixels, the resolve pass.  The list and its
 // length never leave the device.
+//
+// On row shards the row sums are phase 1 (rt_adaptive_export_rows: the shard's
+// own rows into its block, nothing of the accumulation's state changes) and the
+// rest is phase 2 (rt_render_adaptive_shard), whose test reads the column taps
+// from the ranks' gathered blocks; every pass behind the test is the full
+// frame's over the shard's rows * width.
 #include <cmath>
 
 #include "rt_context.h"
 
 namespace {
 
-int params_check(rt_context* c, const rt_adaptive_params* p, int& max_bounces) {
+int params_check(rt_context* c, const rt_adaptive_params* p, int& max_bounces, bool shard_ok = false) {
     if (!c || !p) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
     if (p->samples < 1 || !(p->tolerance > 0.0f) || !(p->lum_floor >= 0.0f) || std::isinf(p->lum_floor) ||
@@ -29,7 +37,7 @@ int params_check(rt_context* c, const rt_adaptive_params* p, int& max_bounces) {
         return fail(c, RT_ERR_UNSUPPORTED,
                     "rt_render_adaptive: not in RT_PRECISION_REFERENCE_FAST (a list schedule would be a new "
                     "arithmetic form of that mode)");
-    if (c->rng.p && (c->row_offset != 0 || c->row_stride > 1))
+    if (!shard_ok && c->rng.p && c->holds_shard())
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the context holds a row shard (offset %d, stride %d): the selection window needs a full frame",
                     c->row_offset, c->row_stride);
@@ -52,9 +60,9 @@ int params_check(rt_context* c, const rt_adaptive_params* p, int& max_bounces) {
 // The buffers of the non-uniform state and of a selection; the arguments of
 // this call's passes.  `fresh`: the counts are to be filled first.
 int setup(rt_context* c, const rt_adaptive_params* p, rt_ad_args& A, bool& fresh) {
-    const size_t npix = (size_t)c->height * c->width;
+    const size_t npix = (size_t)c->rows * c->width;  // the context's pixel state: the frame, or its row shard
     const int wpr = (c->width + 63) / 64;
-    const size_t nwords = (size_t)wpr * c->height;
+    const size_t nwords = (size_t)wpr * c->rows;
     const char* oom = "host adaptive state for %zu pixels";
     int rc = ensure_buf(c, c->ad_cnt, npix * sizeof(uint2), oom, npix);
     if (!rc) rc = ensure_buf(c, c->ad_rows, npix * 3 * sizeof(float), oom, npix);
@@ -66,7 +74,7 @@ int setup(rt_context* c, const rt_adaptive_params* p, rt_ad_args& A, bool& fresh
     fresh = !c->st.nonuniform();
     std::memset(&A, 0, sizeof A);
     A.width = c->width;
-    A.height = c->height;
+    A.height = c->rows;
     A.npix = (long)npix;
     A.words_per_row = wpr;
     A.k = p->samples;
@@ -94,7 +102,7 @@ int setup(rt_context* c, const rt_adaptive_params* p, rt_ad_args& A, bool& fresh
 }
 
 void kparams(rt_context* c, int samples, int max_bounces, rt_kparams& K) {
-    fill_view(c, c->width, c->height, 0, 1, c->rows, K);
+    fill_view(c, c->width, c->height, c->row_offset, c->row_stride > 1 ? c->row_stride : 1, c->rows, K);
     K.samples = samples;
     K.max_bounces = max_bounces;
     K.first_frame = 2u;  // never 1: a listed pixel continues (its frame is n_p + 1, from the counts)
@@ -103,7 +111,25 @@ void kparams(rt_context* c, int samples, int max_bounces, rt_kparams& K) {
     K.rgba = nullptr;  // the resolve pass writes the image
 }
 
-int cpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, float* color) {
+// The ranks' gathered row-sum blocks of a phase 2 (p null: a full-frame call,
+// which makes its own row sums)
+struct Gathered {
+    const float* p;
+    int shards, rows_per_shard;
+};
+
+rt_ad_shard_args shard_args(const rt_context* c, const rt_ad_args& A, const Gathered& g) {
+    rt_ad_shard_args S;
+    S.A = A;
+    S.gathered = g.p;
+    S.shards = g.shards;
+    S.rows_per_shard = g.rows_per_shard;
+    S.image_height = c->height;
+    S.row_offset = c->row_offset;
+    return S;
+}
+
+int cpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, float* color, const Gathered& g) {
     const HostFpEnv fp;
     rt_ad_args A;
     bool fresh = false;
@@ -121,7 +147,10 @@ int cpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, fl
     auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<float, std::milli>(b - a).count(); };
     (void)c->render.begin(nullptr, true);
     const auto t0 = clock::now();
-    rt_cpu_adaptive_select(A, c->threads);
+    if (g.p)
+        rt_cpu_adaptive_select_shard(shard_args(c, A, g), c->threads);
+    else
+        rt_cpu_adaptive_select(A, c->threads);
     const auto t1 = clock::now();
     rt_cpu_adaptive_render(K, A, c->threads);
     const auto t2 = clock::now();
@@ -139,7 +168,7 @@ int cpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, fl
 
 // The GPU call on stream s; rgba / color: device pointers or null
 int gpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, unsigned* rgba, float* color,
-                 hipStream_t s) {
+                 hipStream_t s, const Gathered& g) {
     const HostFpEnv fp;
     HIP_TRY(c, hipSetDevice(c->device));
     rt_ad_args A;
@@ -165,8 +194,8 @@ int gpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, un
     if (timed) HIP_TRY(c, hipEventRecord(c->ad_ev[0], s));
     hipError_t e = hipSuccess;
     if (fresh) e = rt_launch_adaptive_fill(A.cnt, A.total, A.npix, c->st.tracked_frames(), c->st.batches(), s);
-    if (e == hipSuccess) e = rt_launch_adaptive(A, 0, s);
-    if (e == hipSuccess) e = rt_launch_adaptive(A, 1, s);
+    if (e == hipSuccess && !g.p) e = rt_launch_adaptive(A, 0, s);
+    if (e == hipSuccess) e = g.p ? rt_launch_adaptive_shard(shard_args(c, A, g), s) : rt_launch_adaptive(A, 1, s);
     if (e == hipSuccess && timed) e = hipEventRecord(c->ad_ev[1], s);
     const rt_list_args L = {A.list, A.list_n, A.cnt};
     if (e == hipSuccess) e = rt_launch_render_list(K, L, c->num_cus, which, s);
@@ -211,6 +240,106 @@ int read_stats(rt_context* c, rt_adaptive_stats* st) {
     return RT_OK;
 }
 
+// ---- on row shards --------------------------------------------------------------
+size_t block_words(const rt_context* c, int rows_per_shard) { return (size_t)3 * (size_t)rows_per_shard * (size_t)c->width; }
+
+// What phase 1 needs besides its destination: rt_render_adaptive's checks minus the shard refusal
+int export_rows_check(rt_context* c, const rt_adaptive_params* p, int rows_per_shard) {
+    int mb = -1;
+    if (const int rc = params_check(c, p, mb, true)) return rc;
+    if (rows_per_shard < c->rows)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "rows_per_shard %d below the shard's %d rows", rows_per_shard, c->rows);
+    if ((long long)rows_per_shard * c->width > (1ll << 31))
+        return fail(c, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 words");
+    return RT_OK;
+}
+
+// Phase 1 of a checked call: the row sums of the context's own rows into
+// `block` (device memory on a GPU context, on stream s: after the last render
+// and its moment update, and the next render after it, as an rt_export_shard;
+// host memory on a CPU context).  In the uniform state the counts the row sums
+// read are the context's, written to the scratch the first adaptive call fills
+// anyway: nothing a uniform render, rt_export_shard or rt_get_counts reads.
+int export_rows_pass(rt_context* c, const rt_adaptive_params* p, int rows_per_shard, float* block, hipStream_t s) {
+    const HostFpEnv fp;
+    if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
+    rt_ad_args A;
+    bool fresh = false;
+    if (const int rc = setup(c, p, A, fresh)) return rc;
+    const long plane = (long)rows_per_shard * c->width;
+    A.rowv = block;
+    A.rowm = block + plane;
+    A.rowc = reinterpret_cast<int*>(block + 2 * plane);
+    if (c->cpu) {
+        if (fresh) {
+            const uint2 v = make_uint2(c->st.tracked_frames(), c->st.batches());
+            for (long i = 0; i < A.npix; i++) A.cnt[i] = v;
+        }
+        (void)c->xport.begin(nullptr, false);
+        rt_cpu_adaptive_rows_block(A, plane, c->threads);
+        (void)c->xport.end(nullptr);
+    } else {
+        HIP_TRY(c, c->xport.create(false));
+        if (const int rc = order_after_all(c, s)) return rc;
+        if (fresh)
+            HIP_TRY(c, rt_launch_adaptive_fill(A.cnt, A.total, A.npix, c->st.tracked_frames(), c->st.batches(), s));
+        HIP_TRY(c, rt_launch_adaptive_rows_block(A, plane, s));
+        HIP_TRY(c, c->xport.end(s));
+    }
+    c->st.export_done(p->radius);
+    return RT_OK;
+}
+
+// What phase 2 needs besides its source and destinations
+int shard_call_check(rt_context* c, const rt_adaptive_params* p, int& max_bounces, const void* gathered, int shards,
+                     int rows_per_shard) {
+    if (!c || !p || !gathered) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (const int rc = params_check(c, p, max_bounces, true)) return rc;
+    if (!c->st.export_current(p->radius))
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "rt_render_adaptive_shard: no current rt_adaptive_export_rows of this context with radius %d (none "
+                    "was made, or a render, reset, scene or camera call came since)",
+                    p->radius);
+    if (shards != (c->row_stride > 1 ? c->row_stride : 1))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "shards %d is not the context's row stride %d", shards,
+                    c->row_stride > 1 ? c->row_stride : 1);
+    if (rows_per_shard < 1 || (long long)rows_per_shard * shards < c->height)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "bad gather geometry: %d shards of %d rows for height %d", shards,
+                    rows_per_shard, c->height);
+    if ((long long)rows_per_shard * c->width > (1ll << 31))
+        return fail(c, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 words");
+    return RT_OK;
+}
+
+// Phase 2 of a checked call on the host forms' path: `gathered` is host memory
+// (staged to the device on a GPU context), the outputs are the shard's rows in
+// shard order; synchronous
+int shard_call_host(rt_context* c, const rt_adaptive_params* p, int max_bounces, const float* gathered, int shards,
+                    int rows_per_shard, uint8_t* rgba_out, float* color_out, bool sync) {
+    const size_t npix = (size_t)c->rows * c->width;
+    if (c->cpu) {
+        if (const int rc = cpu_adaptive(c, p, max_bounces, color_out, {gathered, shards, rows_per_shard})) return rc;
+        if (rgba_out) std::memcpy(rgba_out, c->rgba.p, npix * 4);
+        return RT_OK;
+    }
+    const size_t gbytes = (size_t)shards * block_words(c, rows_per_shard) * sizeof(float);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_buf(c, c->rgba, npix * 4);
+    if (!rc && color_out) rc = ensure_buf(c, c->ad_color, npix * 3 * sizeof(float));
+    if (!rc && gathered != c->ad_gather.p) rc = ensure_buf(c, c->ad_gather, gbytes);
+    if (rc) return rc;
+    if (gathered != c->ad_gather.p)
+        HIP_TRY(c, hipMemcpyAsync(c->ad_gather.p, gathered, gbytes, hipMemcpyHostToDevice, c->stream));
+    rc = gpu_adaptive(c, p, max_bounces, c->rgba.as<unsigned>(), color_out ? c->ad_color.as<float>() : nullptr, c->stream,
+                      {c->ad_gather.as<float>(), shards, rows_per_shard});
+    if (rc) return rc;
+    if (rgba_out) HIP_TRY(c, hipMemcpyAsync(rgba_out, c->rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    if (color_out)
+        HIP_TRY(c, hipMemcpyAsync(color_out, c->ad_color.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (sync) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -233,7 +362,7 @@ int rt_render_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounc
     if (const int rc = params_check(c, p, max_bounces)) return rc;
     const size_t npix = (size_t)c->height * c->width;
     if (c->cpu) {
-        if (const int rc = cpu_adaptive(c, p, max_bounces, color_out)) return rc;
+        if (const int rc = cpu_adaptive(c, p, max_bounces, color_out, {})) return rc;
         if (rgba_out) std::memcpy(rgba_out, c->rgba.p, npix * 4);
         return stats_out ? read_stats(c, stats_out) : RT_OK;
     }
@@ -241,7 +370,7 @@ int rt_render_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounc
     int rc = ensure_buf(c, c->rgba, npix * 4);
     if (!rc && color_out) rc = ensure_buf(c, c->ad_color, npix * 3 * sizeof(float));
     if (rc) return rc;
-    rc = gpu_adaptive(c, p, max_bounces, c->rgba.as<unsigned>(), color_out ? c->ad_color.as<float>() : nullptr, c->stream);
+    rc = gpu_adaptive(c, p, max_bounces, c->rgba.as<unsigned>(), color_out ? c->ad_color.as<float>() : nullptr, c->stream, {});
     if (rc) return rc;
     if (rgba_out) HIP_TRY(c, hipMemcpyAsync(rgba_out, c->rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
     if (color_out)
@@ -256,7 +385,7 @@ int rt_render_adaptive_device(rt_context* c, const rt_adaptive_params* p, int ma
     if (const int rc = params_check(c, p, max_bounces)) return rc;
     if (rgba_device && ((uintptr_t)rgba_device & 3u))
         return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
-    return gpu_adaptive(c, p, max_bounces, (unsigned*)rgba_device, nullptr, stream ? (hipStream_t)stream : c->stream);
+    return gpu_adaptive(c, p, max_bounces, (unsigned*)rgba_device, nullptr, stream ? (hipStream_t)stream : c->stream, {});
 }
 
 int rt_adaptive_last_stats(rt_context* c, rt_adaptive_stats* stats_out) { return read_stats(c, stats_out); }
@@ -284,6 +413,159 @@ int rt_get_counts(rt_context* c, uint32_t* frames_out, uint32_t* batches_out) {
         if (frames_out) frames_out[i] = cn[i].x;
         if (batches_out) batches_out[i] = cn[i].y;
     }
+    return RT_OK;
+}
+
+int rt_adaptive_export_rows(rt_context* c, const rt_adaptive_params* p, int rows_per_shard, float* block_host) {
+    if (!c || !p || !block_host) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = export_rows_check(c, p, rows_per_shard);
+    if (rc) return rc;
+    if (c->cpu) return export_rows_pass(c, p, rows_per_shard, block_host, nullptr);
+    const size_t bytes = block_words(c, rows_per_shard) * sizeof(float);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensure_buf(c, c->ad_block, bytes))) return rc;
+    if ((rc = export_rows_pass(c, p, rows_per_shard, c->ad_block.as<float>(), c->stream))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(block_host, c->ad_block.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
+int rt_adaptive_export_rows_device(rt_context* c, const rt_adaptive_params* p, int rows_per_shard, void* block_device,
+                                   void* stream) {
+    if (!c || !p || !block_device) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_adaptive_export_rows_device: CPU context");
+    if ((uintptr_t)block_device & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "block_device not 4-byte aligned");
+    if (const int rc = export_rows_check(c, p, rows_per_shard)) return rc;
+    return export_rows_pass(c, p, rows_per_shard, (float*)block_device, stream ? (hipStream_t)stream : c->stream);
+}
+
+int rt_render_adaptive_shard(rt_context* c, const rt_adaptive_params* p, int max_bounces, const float* gathered_host,
+                             int shards, int rows_per_shard, uint8_t* rgba_out, float* color_out,
+                             rt_adaptive_stats* stats_out) {
+    if (const int rc = shard_call_check(c, p, max_bounces, gathered_host, shards, rows_per_shard)) return rc;
+    if (const int rc = shard_call_host(c, p, max_bounces, gathered_host, shards, rows_per_shard, rgba_out, color_out, true))
+        return rc;
+    return stats_out ? read_stats(c, stats_out) : RT_OK;
+}
+
+int rt_render_adaptive_shard_device(rt_context* c, const rt_adaptive_params* p, int max_bounces,
+                                    const void* gathered_device, int shards, int rows_per_shard, void* rgba_device,
+                                    void* stream) {
+    if (c && c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_render_adaptive_shard_device: CPU context");
+    if (const int rc = shard_call_check(c, p, max_bounces, gathered_device, shards, rows_per_shard)) return rc;
+    if (((uintptr_t)gathered_device & 3u) || (rgba_device && ((uintptr_t)rgba_device & 3u)))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "gathered_device or rgba_device not 4-byte aligned");
+    return gpu_adaptive(c, p, max_bounces, (unsigned*)rgba_device, nullptr, stream ? (hipStream_t)stream : c->stream,
+                        {(const float*)gathered_device, shards, rows_per_shard});
+}
+
+int rt_render_adaptive_multi(rt_context* const* ctxs, int n, const rt_adaptive_params* p, int max_bounces,
+                             uint8_t* rgba_out, rt_adaptive_stats* stats_out) {
+    if (!ctxs || n <= 0 || !ctxs[0]) return RT_ERR_INVALID_ARGUMENT;
+    rt_context* d = ctxs[0];
+    if (!p) return fail(d, RT_ERR_INVALID_ARGUMENT, "null argument");
+    // every condition first: a refusal touches nothing
+    for (int i = 0; i < n; i++) {
+        if (!ctxs[i]) return fail(d, RT_ERR_INVALID_ARGUMENT, "null context %d", i);
+        if (ctxs[i]->cpu != d->cpu)
+            return fail(d, RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive_multi: GPU and CPU contexts mixed");
+        for (int j = 0; j < i; j++)
+            if (ctxs[j] == ctxs[i]) return fail(d, RT_ERR_INVALID_ARGUMENT, "context listed twice");
+    }
+    const int width = d->width, height = d->height;
+    if (width <= 0 || height <= 0)
+        return fail(d, RT_ERR_INVALID_ARGUMENT, "no frame shape yet (render or rt_init_rand first)");
+    const int active = n < height ? n : height;  // contexts beyond the image height hold no rows
+    const int rps = (height + n - 1) / n;
+    std::vector<int> bounces;
+    if (!try_resize(bounces, (size_t)active)) return fail(d, RT_ERR_OUT_OF_MEMORY, "host state for %d contexts", n);
+    for (int i = 0; i < active; i++) {
+        rt_context* c = ctxs[i];
+        if (c->width != width || c->height != height || c->row_offset != i || (c->row_stride > 1 ? c->row_stride : 1) != n ||
+            !c->accum.p)
+            return fail(d, RT_ERR_INVALID_ARGUMENT, "context %d holds %dx%d offset %d stride %d, not shard %d of %d of %dx%d",
+                        i, c->width, c->height, c->row_offset, c->row_stride, i, n, width, height);
+        if (c->st.frame() != d->st.frame() || c->st.batches() != d->st.batches())
+            return fail(d, RT_ERR_INVALID_ARGUMENT, "frame counters or batches differ (context %d: %u, %u; context 0: %u, %u)",
+                        i, c->st.frame(), c->st.batches(), d->st.frame(), d->st.batches());
+        bounces[(size_t)i] = max_bounces;
+        if (const int rc = params_check(c, p, bounces[(size_t)i], true)) {
+            if (c != d) (void)fail(d, rc, "context %d: %s", i, c->err.c_str());
+            return rc;
+        }
+        if ((long long)rps * width > (1ll << 31)) return fail(d, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 words");
+    }
+    const size_t blk = block_words(d, rps);
+    const size_t gbytes = (size_t)n * blk * sizeof(float);
+    // a failure at context i leaves work of the contexts before it in flight: drain it
+    auto drain = [&](int launched, int code) {
+        for (int j = 0; j < launched && !d->cpu; j++) {
+            (void)hipSetDevice(ctxs[j]->device);
+            (void)hipStreamSynchronize(ctxs[j]->stream);
+        }
+        return code;
+    };
+    // the gathered blocks: on every GPU context's device; CPU contexts share context 0's
+    for (int i = 0; i < (d->cpu ? 1 : active); i++) {
+        rt_context* c = ctxs[i];
+        if (!c->cpu && hipSetDevice(c->device) != hipSuccess) return fail(c, RT_ERR_HIP, "hipSetDevice");
+        if (const int rc = ensure_buf(c, c->ad_gather, gbytes, "host gathered row sums (%zu words)", (size_t)n * blk))
+            return rc;
+    }
+    // phase 1 into the context's own slot, then that block to every other context
+    for (int i = 0; i < active; i++) {
+        rt_context* c = ctxs[i];
+        float* own = (c->cpu ? d : c)->ad_gather.as<float>() + (size_t)i * blk;
+        if (const int rc = export_rows_pass(c, p, rps, own, c->stream)) return drain(i + 1, rc);
+        for (int j = 0; j < active && !c->cpu; j++) {
+            if (j == i) continue;
+            rt_context* o = ctxs[j];
+            float* dst = o->ad_gather.as<float>() + (size_t)i * blk;
+            const hipError_t e = o->device == c->device
+                                     ? hipMemcpyAsync(dst, own, blk * sizeof(float), hipMemcpyDeviceToDevice, c->stream)
+                                     : hipMemcpyPeerAsync(dst, o->device, own, c->device, blk * sizeof(float), c->stream);
+            if (e != hipSuccess) return drain(i + 1, hip_fail(c, e, "block copy"));
+        }
+    }
+    // every block is in place before a phase 2 is queued (the call synchronises anyway)
+    for (int i = 0; i < active && !d->cpu; i++) {
+        rt_context* c = ctxs[i];
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    for (int i = 0; i < active; i++) {
+        rt_context* c = ctxs[i];
+        const float* g = (c->cpu ? d : c)->ad_gather.as<float>();
+        if (const int rc = shard_call_host(c, p, bounces[(size_t)i], g, n, rps, nullptr, nullptr, false)) return drain(i + 1, rc);
+        if (!rgba_out) continue;
+        // the shard's rows to their image rows: row j of context i is row i + j * n
+        uint8_t* dst = rgba_out + (size_t)i * width * 4;
+        if (c->cpu) {
+            for (int j = 0; j < c->rows; j++)
+                std::memcpy(dst + (size_t)j * n * width * 4, c->rgba.as<uint8_t>() + (size_t)j * width * 4, (size_t)width * 4);
+        } else {
+            const hipError_t e = hipMemcpy2DAsync(dst, (size_t)n * width * 4, c->rgba.p, (size_t)width * 4, (size_t)width * 4,
+                                                  (size_t)c->rows, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) return drain(i + 1, hip_fail(c, e, "hipMemcpy2DAsync"));
+        }
+    }
+    rt_adaptive_stats sum = {0, 0, -1.0f, -1.0f, -1.0f};
+    for (int i = 0; i < active; i++) {
+        rt_context* c = ctxs[i];
+        if (!c->cpu) {
+            HIP_TRY(c, hipSetDevice(c->device));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        if (!stats_out) continue;
+        rt_adaptive_stats st;
+        if (const int rc = read_stats(c, &st)) return drain(active, rc);
+        sum.selected += st.selected;
+        sum.frames_total += st.frames_total;
+        sum.select_ms = st.select_ms > sum.select_ms ? st.select_ms : sum.select_ms;
+        sum.render_ms = st.render_ms > sum.render_ms ? st.render_ms : sum.render_ms;
+        sum.resolve_ms = st.resolve_ms > sum.resolve_ms ? st.resolve_ms : sum.resolve_ms;
+    }
+    if (stats_out) *stats_out = sum;
     return RT_OK;
 }
 

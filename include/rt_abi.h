@@ -196,7 +196,8 @@ RT_API void rt_destroy(rt_context* ctx);
  * renders on the CPU, and every entry point behaves on it as on a GPU
  * context (rt_set_scene, rt_init_rand, rt_render, rt_render_ex, rt_controls,
  * rt_get_state / rt_set_state, ...; rt_last_kernel_ms gives the last render's
- * wall time) except rt_render_device, rt_render_adaptive_device, rt_denoise_device, rt_denoise_var_device,
+ * wall time) except rt_render_device, rt_render_adaptive_device, rt_adaptive_export_rows_device,
+ * rt_render_adaptive_shard_device, rt_denoise_device, rt_denoise_var_device,
  * rt_temporal_device, rt_render_multi and rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no
  * device memory).
  * Replaces the reference's config-1 CPU path and is the CPU baseline of
@@ -691,6 +692,68 @@ RT_API int rt_adaptive_last_stats(rt_context* ctx, rt_adaptive_stats* stats_out)
  * batches tracked.  In the uniform state every pixel reports the context's
  * (frame counter - 1, rt_moments_batches).  Synchronous. */
 RT_API int rt_get_counts(rt_context* ctx, uint32_t* frames_out, uint32_t* batches_out);
+
+/* ---- adaptive sampling on row shards ------------------------
+ * rt_render_adaptive refuses a context that holds a row shard: the window's
+ * column taps lie on other ranks.  The two-phase form lifts that.  Only the
+ * row sums cross ranks: phase 1 writes a context's ROW-SUM BLOCK, the ranks
+ * all-gather the blocks, phase 2 tests the context's own rows against the
+ * gathered blocks and then runs every later stage of rt_render_adaptive on its
+ * rows.  N shard contexts end with, interleaved, exactly the bits of one
+ * context that ran rt_render_adaptive on the whole frame, on both backends.
+ *
+ * Block layout, the contract between ranks.  A block is 3 planes of
+ * rows_per_shard * width 32-bit words: plane 0 the row sums of v (float), plane
+ * 1 of M (float), plane 2 the tap counts (int32).  A plane holds the shard's
+ * rows in shard order (row j = image row row_offset + j * row_stride), then
+ * padding rows up to rows_per_shard: phase 1 zero-fills them, phase 2 never
+ * reads them (rt_export_shard's block shape).  GATHERED is `shards` consecutive
+ * blocks, block r = rows r, r + shards, ...: word k of image pixel (x, y) is
+ * gathered[(((y % shards) * 3 + k) * rows_per_shard + y / shards) * width + x].
+ * Every rank needs every block (an all-gather); copies must keep the bits.
+ *
+ * Phase 1.  The row sums of the context's own rows with params->radius into
+ * block_host (3 * rows_per_shard * width words; synchronous), or into DEVICE
+ * memory (4-byte aligned) on HIP stream `stream` (NULL = the context's) with
+ * rt_export_shard_device's ordering and no host synchronisation.  It does not
+ * change the accumulation: a continuing uniform render, rt_export_shard and
+ * rt_get_counts afterwards behave as if it had not been called.  Checks and
+ * errors are rt_render_adaptive's without the shard refusal, and
+ * RT_ERR_INVALID_ARGUMENT for rows_per_shard below the context's rows. */
+RT_API int rt_adaptive_export_rows(rt_context* ctx, const rt_adaptive_params* params, int rows_per_shard,
+                                   float* block_host);
+RT_API int rt_adaptive_export_rows_device(rt_context* ctx, const rt_adaptive_params* params, int rows_per_shard,
+                                          void* block_device, void* stream);
+/* Phase 2.  [count fill on the first call of an accumulation,] the test from
+ * the gathered blocks, scan, scatter, list render, moment update, resolve; the
+ * outputs are the shard's rows in shard order (rows * width), as rt_render_ex's.
+ * RT_ERR_INVALID_ARGUMENT when the context's last phase 1 is not current (none
+ * was made, a render, reset, scene or camera call came since, or it was made
+ * with another radius), shards is not the context's row stride (1 on a
+ * full-frame context, which then gives rt_render_adaptive's bits),
+ * rows_per_shard * shards < height, or params or gathered is NULL.  Afterwards
+ * the accumulation is non-uniform exactly as after rt_render_adaptive.  The
+ * device form runs on one stream inside one render pass with
+ * rt_render_adaptive_device's ordering rules and never synchronises with the
+ * host; the caller orders the gather between the phases, as with
+ * rt_assemble_device.  CPU context: RT_ERR_UNSUPPORTED for the device forms. */
+RT_API int rt_render_adaptive_shard(rt_context* ctx, const rt_adaptive_params* params, int max_bounces,
+                                    const float* gathered_host, int shards, int rows_per_shard, uint8_t* rgba_out,
+                                    float* color_out, rt_adaptive_stats* stats_out);
+RT_API int rt_render_adaptive_shard_device(rt_context* ctx, const rt_adaptive_params* params, int max_bounces,
+                                           const void* gathered_device, int shards, int rows_per_shard,
+                                           void* rgba_device, void* stream);
+/* The one-process companion of rt_render_multi / rt_assemble_multi: phase 1 on
+ * every context with rows on its own stream, every block copied to every
+ * context's device, phase 2 on every context, the RGBA rows gathered into the
+ * full image (w*h*4 bytes, row 0 = bottom, or NULL); synchronises before
+ * returning.  stats_out (may be NULL): the sums of selected and frames_total
+ * and the maxima of the three stage times.  The contexts must be all GPU or
+ * all CPU contexts, distinct, hold shards i (mod n) of one frame and have equal
+ * frame counters and equal batches; anything else is RT_ERR_INVALID_ARGUMENT
+ * and nothing is touched.  Contexts beyond the image height are skipped. */
+RT_API int rt_render_adaptive_multi(rt_context* const* ctxs, int n, const rt_adaptive_params* params, int max_bounces,
+                                    uint8_t* rgba_out, rt_adaptive_stats* stats_out);
 
 /* Post-render passes on a non-uniform accumulation.  Off
  * (the default) rt_denoise*, rt_denoise_var* and rt_temporal* refuse the
