@@ -5,6 +5,8 @@ The product is the HIP library bwidman-raytracer_amd/lib/libbwrt.so
 reference's driver (scenes, render loop, multi-GPU sharding).
 """
 from . import abi, scenes  # noqa: F401
-from .renderer import Renderer, assemble_multi, render_adaptive_multi, render_multi, shard_rows  # noqa: F401
+from .renderer import (Renderer, assemble_adaptive_multi, assemble_multi, render_adaptive_multi,  # noqa: F401
+                       render_multi, shard_rows)
 
-__all__ = ["abi", "scenes", "Renderer", "assemble_multi", "render_adaptive_multi", "render_multi", "shard_rows"]
+__all__ = ["abi", "scenes", "Renderer", "assemble_adaptive_multi", "assemble_multi", "render_adaptive_multi", "render_multi",
+           "shard_rows"]

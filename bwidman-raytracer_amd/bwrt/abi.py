@@ -206,6 +206,12 @@ def _proto(lib):
         "rt_get_assembled": (C.c_int, [vp, vp, vp]),
         "rt_assemble_drop": (C.c_int, [vp]),
         "rt_last_assemble_ms": (C.c_float, [vp]),
+        "rt_export_shard_adaptive": (C.c_int, [vp, C.c_int, C.c_int, vp, P(C.c_uint), P(C.c_uint)]),
+        "rt_export_shard_adaptive_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, P(C.c_uint), P(C.c_uint)]),
+        "rt_assemble_adaptive": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint]),
+        "rt_assemble_adaptive_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, vp]),
+        "rt_assemble_adaptive_multi": (C.c_int, [P(vp), C.c_int, C.c_int, C.c_int]),
+        "rt_get_assembled_counts": (C.c_int, [vp, vp, vp]),
         "rt_error_string": (C.c_char_p, [C.c_int]),
         "rt_last_error": (C.c_char_p, [vp]),
         "rt_last_kernel_name": (C.c_char_p, [vp]),

@@ -125,6 +125,50 @@ def gather_frame(renderer, plan: ShardPlan, width: int, planes: int = 3, group=N
     return root
 
 
+def gather_frame_adaptive(renderer, plan: ShardPlan, width: int, planes: int = 4, group=None, dst: int = 0,
+                          stream=None):
+    """gather_frame for a frame sampled adaptively (render_adaptive below;
+    DESIGN.md section 19): rt_export_shard_adaptive -> gather_rows ->
+    rt_assemble_adaptive.  The blocks carry every pixel's counts (planes 4 =
+    frameSum and n_p, 7 = with the moments and J_p), so with
+    set_adaptive_filters on `dst`'s denoise, denoise_var and temporal give what
+    one renderer gives that ran render_adaptive on the whole frame.  The ranks'
+    accumulations may be uniform or non-uniform.  Returns True on `dst`, False
+    elsewhere.
+
+    Streams, host synchronisation (none on a GPU renderer), the gloo path of a
+    CPU renderer and the zero block of a rank without rows are gather_frame's."""
+    import torch
+    import torch.distributed as dist
+    rps = plan.rows_per_shard
+    root = (dist.get_rank(group) if group is not None else dist.get_rank()) == dst
+    if renderer.is_cpu:
+        # (float32 tensors are copied as bytes: the count planes' integers and any float's bits survive)
+        block = torch.zeros((planes, rps, width), dtype=torch.float32)
+        frames = batches = 0
+        if plan.rows > 0:
+            arr, frames, batches = renderer.export_shard_adaptive(rps, width, planes)
+            block.copy_(torch.from_numpy(arr))
+        gathered = gather_rows(block, plan, group=group, dst=dst)
+        if root:
+            renderer.assemble_adaptive(gathered.numpy(), frames, batches)
+        return root
+    dev = torch.device("cuda", renderer.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        frames = batches = 0
+        if plan.rows > 0:
+            block = torch.empty((planes, rps, width), dtype=torch.float32, device=dev)
+            frames, batches = renderer.export_shard_adaptive_device(block.data_ptr(), rps, planes, s.cuda_stream)
+        else:
+            block = torch.zeros((planes, rps, width), dtype=torch.float32, device=dev)
+        gathered = gather_rows(block, plan, group=group, dst=dst)
+        if root:
+            renderer.assemble_adaptive_device(gathered.data_ptr(), plan.world, rps, planes, frames, batches,
+                                              s.cuda_stream)
+    return root
+
+
 def render_adaptive(renderer, plan: ShardPlan, width: int, max_bounces: int = -1, group=None, stream=None, **params):
     """One adaptive call across the ranks' row shards:
     rt_adaptive_export_rows -> all_gather -> rt_render_adaptive_shard.  Only

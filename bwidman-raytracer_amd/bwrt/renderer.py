@@ -520,6 +520,53 @@ class Renderer:
     def last_assemble_ms(self) -> float:
         return self.lib.rt_last_assemble_ms(self.ctx)
 
+    # -- counted blocks: adaptive (non-uniform) frames of row shards ------------
+    def export_shard_adaptive(self, rows_per_shard, width, planes=4):
+        """rt_export_shard_adaptive: this context's counted block, (planes,
+        rows_per_shard, width) float32 — R, G, B of frameSum and n_p (planes=4),
+        or R, G, B, M, M2, n_p, J_p (planes=7); the count planes hold uint32
+        bits (block[-1].view(np.uint32)) — and the (frames, batches) of the
+        uniform base.  Works on a uniform and on a non-uniform accumulation."""
+        block = np.empty((planes, rows_per_shard, width), np.float32)
+        n, j = C.c_uint(), C.c_uint()
+        self._check(self.lib.rt_export_shard_adaptive(self.ctx, rows_per_shard, planes, block.ctypes.data, C.byref(n),
+                                                      C.byref(j)))
+        return block, n.value, j.value
+
+    def export_shard_adaptive_device(self, block_ptr: int, rows_per_shard, planes=4, stream_ptr: int | None = None):
+        """rt_export_shard_adaptive_device: the counted block into device
+        memory on a stream (asynchronous; after the last render or adaptive
+        call, and the next render after it).  Returns (frames, batches)."""
+        n, j = C.c_uint(), C.c_uint()
+        self._check(self.lib.rt_export_shard_adaptive_device(self.ctx, rows_per_shard, planes, block_ptr, stream_ptr,
+                                                             C.byref(n), C.byref(j)))
+        return n.value, j.value
+
+    def assemble_adaptive(self, gathered, frames, batches=0):
+        """rt_assemble_adaptive: make the assembled frame with its count plane
+        from `gathered`, (shards, planes, rows_per_shard, width) float32 counted
+        blocks on the host.  With set_adaptive_filters on, denoise, denoise_var
+        and temporal on a renderer whose own state is a row shard then take
+        every pixel's own counts; `frames` / `batches` are the uniform base."""
+        g = np.ascontiguousarray(gathered, dtype=np.float32)
+        shards, planes, rps, _ = g.shape
+        self._check(self.lib.rt_assemble_adaptive(self.ctx, g.ctypes.data, shards, rps, planes, frames, batches))
+
+    def assemble_adaptive_device(self, gathered_ptr: int, shards, rows_per_shard, planes, frames, batches=0,
+                                 stream_ptr: int | None = None):
+        """rt_assemble_adaptive_device: the same from device memory on a stream
+        (asynchronous; ordered like assemble_device)."""
+        self._check(self.lib.rt_assemble_adaptive_device(self.ctx, gathered_ptr, shards, rows_per_shard, planes,
+                                                         frames, batches, stream_ptr))
+
+    def assembled_counts(self, width, height):
+        """rt_get_assembled_counts: the counted assembled frame's per-pixel
+        (frames, batches), two (H, W) uint32 arrays (as counts())."""
+        n = np.empty((height, width), np.uint32)
+        j = np.empty((height, width), np.uint32)
+        self._check(self.lib.rt_get_assembled_counts(self.ctx, n.ctypes.data, j.ctypes.data))
+        return n, j
+
     # -- checkpoint / resume -----------------------------------------------
     def get_state(self, rows, width):
         rng = np.empty((6, rows, width), dtype=np.uint32)
@@ -560,6 +607,20 @@ def assemble_multi(renderers, planes: int = 0, dst: int = 0):
     lib = renderers[0].lib
     arr = (C.c_void_p * len(renderers))(*[r.ctx.value for r in renderers])
     rc = lib.rt_assemble_multi(arr, len(renderers), planes, dst)
+    if rc != abi.RT_OK:
+        renderers[dst if 0 <= dst < len(renderers) else 0]._check(rc)
+    return renderers[dst].assembled()
+
+
+def assemble_adaptive_multi(renderers, planes: int = 0, dst: int = 0):
+    """rt_assemble_adaptive_multi, beside render_adaptive_multi: assemble_multi
+    with counted blocks, for renderers whose accumulations are uniform or
+    non-uniform.  planes 4, 7 (with the moments), or 0 = 7 when every
+    renderer's moments are current.  Returns the (frames, batches) of the
+    uniform base; renderers[dst].assembled_counts() has the pixels' own."""
+    lib = renderers[0].lib
+    arr = (C.c_void_p * len(renderers))(*[r.ctx.value for r in renderers])
+    rc = lib.rt_assemble_adaptive_multi(arr, len(renderers), planes, dst)
     if rc != abi.RT_OK:
         renderers[dst if 0 <= dst < len(renderers) else 0]._check(rc)
     return renderers[dst].assembled()

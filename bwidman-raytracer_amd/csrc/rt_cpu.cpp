@@ -356,6 +356,15 @@ void rt_cpu_assemble(const rt_asm_args& A, int threads) {
     parallel_items(asm_items(A, A.rows, 1), threads, [&](long q) { asm_assemble_item<1>(A, q); });
 }
 
+// counted blocks: likewise
+void rt_cpu_export_shard_adaptive(const rt_asmc_args& C, int threads) {
+    parallel_items(asmc_items(C, C.a.rows_per_shard, 1), threads, [&](long q) { asmc_export_item<1>(C, q); });
+}
+
+void rt_cpu_assemble_adaptive(const rt_asmc_args& C, int threads) {
+    parallel_items(asmc_items(C, C.a.rows, 1), threads, [&](long q) { asmc_assemble_item<1>(C, q); });
+}
+
 // ---- adaptive sampling on the host (rt_adaptive.h) -----------------------------
 #include "rt_adaptive.h"
 

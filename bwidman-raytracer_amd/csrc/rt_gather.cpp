@@ -1,25 +1,38 @@
 // rt_gather.cpp — row shards into one frame (include/rt_abi.h, DESIGN.md
-// section 17): rt_export_shard writes a context's block, rt_assemble
+// sections 17 and 19): rt_export_shard writes a context's block, rt_assemble
 // de-interleaves the ranks' gathered blocks into the context's assembled frame,
-// rt_assemble_multi does both for the contexts of one process.  rt_layout.h
-// (rt_asm_args) has the block layout, rt_assemble.h the indexing; the full-frame
-// passes pick the assembled frame up in rt_post.cpp (frame_src).
+// rt_assemble_multi does both for the contexts of one process.  The _adaptive
+// forms do the same with COUNTED blocks, which carry every pixel's {n_p, J_p},
+// so that a frame sampled adaptively on row shards reaches the count-aware
+// passes.  rt_layout.h (rt_asm_args, rt_asmc_args) has the block layouts,
+// rt_assemble.h the indexing; the full-frame passes pick the assembled frame up
+// in rt_post.cpp (frame_src, frame_counts).
 //
-// Neither call reads or writes the RNG state or the frame counter or writes
-// frameSum or the moments; both are copies, so there is no arithmetic to keep
-// exact.
+// No call reads or writes the RNG state or the frame counter or writes
+// frameSum, the moments or the counts; all are copies, so there is no
+// arithmetic to keep exact.
 #include "rt_context.h"
 
 namespace {
+
+// A block is uncounted (3 or 5 planes) or counted (4 or 7); the moments come
+// with 5 and 7
+bool counted_planes(int planes) { return planes == 4 || planes == 7; }
+bool moment_planes(int planes) { return planes == 5 || planes == 7; }
+int planes_check(rt_context* c, int planes, bool counted) {
+    if (counted ? counted_planes(planes) : (planes == 3 || planes == 5)) return RT_OK;
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "planes %d is neither %s", planes, counted ? "4 nor 7" : "3 nor 5");
+}
 
 size_t block_floats(const rt_context* c, int rows_per_shard, int planes) {
     return (size_t)planes * (size_t)rows_per_shard * (size_t)c->width;
 }
 
-// What an export needs besides its destination
-int export_check(rt_context* c, int rows_per_shard, int planes) {
-    if (planes != 3 && planes != 5) return fail(c, RT_ERR_INVALID_ARGUMENT, "planes %d is neither 3 nor 5", planes);
-    if (c->st.nonuniform())
+// What an export needs besides its destination.  Only a counted block can
+// stand for a non-uniform accumulation.
+int export_check(rt_context* c, int rows_per_shard, int planes, bool counted) {
+    if (const int rc = planes_check(c, planes, counted)) return rc;
+    if (!counted && c->st.nonuniform())
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the accumulation is non-uniform (rt_render_adaptive): a block carries one frame count");
     if (c->st.frame() < 2u || !c->accum.p || c->rows <= 0)
@@ -28,36 +41,49 @@ int export_check(rt_context* c, int rows_per_shard, int planes) {
         return fail(c, RT_ERR_INVALID_ARGUMENT, "rows_per_shard %d below the shard's %d rows", rows_per_shard, c->rows);
     if ((long long)rows_per_shard * c->width > (1ll << 31))
         return fail(c, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 floats");
-    if (planes == 5 && !c->st.current())
+    if (moment_planes(planes) && !c->st.current())
         return fail(c, RT_ERR_INVALID_ARGUMENT,
-                    "5 planes need current moments (rt_set_moments before the accumulation's first render)");
+                    "%d planes need current moments (rt_set_moments before the accumulation's first render)", planes);
     return RT_OK;
 }
 
 // The export pass of a checked call into `block` (device memory on a GPU
-// context, on stream s: after the last render and its moment update, and the
-// next render after it; host memory on a CPU context)
+// context, on stream s: after the last render or adaptive call and its update
+// and resolve, and the next render after it; host memory on a CPU context).  A
+// counted block of a uniform accumulation gets the context's {n, J} for every
+// pixel: nothing of the context is written.
 int export_pass(rt_context* c, int rows_per_shard, int planes, float* block, hipStream_t s) {
-    rt_asm_args A;
-    std::memset(&A, 0, sizeof A);
+    rt_asmc_args C;
+    std::memset(&C, 0, sizeof C);
+    rt_asm_args& A = C.a;
     A.width = c->width;
     A.rows = c->rows;
     A.shards = 1;
     A.rows_per_shard = rows_per_shard;
     A.planes = planes;
     A.sum = c->accum.as<float>();
-    A.mom = planes == 5 ? c->mom_m.as<float2>() : nullptr;
+    A.mom = moment_planes(planes) ? c->mom_m.as<float2>() : nullptr;
     A.block = block;
+    const bool counted = counted_planes(planes);
+    if (counted) {
+        C.cnt = c->st.nonuniform() ? c->ad_cnt.as<uint2>() : nullptr;
+        C.n = c->st.frames();
+        C.j = c->st.batches();
+    }
     if (c->cpu) {
         (void)c->xport.begin(nullptr, false);
-        rt_cpu_export_shard(A, c->threads);
+        if (counted)
+            rt_cpu_export_shard_adaptive(C, c->threads);
+        else
+            rt_cpu_export_shard(A, c->threads);
         (void)c->xport.end(nullptr);
         return RT_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, c->xport.create(false));
     if (const int rc = order_after_all(c, s)) return rc;
-    HIP_TRY(c, rt_launch_export_shard(A, c->deint_blocks, s));
+    HIP_TRY(c, counted ? rt_launch_export_shard_adaptive(C, c->deint_blocks, s)
+                       : rt_launch_export_shard(A, c->deint_blocks, s));
     HIP_TRY(c, c->xport.end(s));
     return RT_OK;
 }
@@ -67,75 +93,11 @@ void report(const rt_context* c, unsigned* frames_out, unsigned* batches_out) {
     if (batches_out) *batches_out = c->st.batches();
 }
 
-// What an assembly needs besides its source
-int assemble_check(rt_context* c, int shards, int rows_per_shard, int planes, unsigned frames) {
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
-    if (c->width <= 0 || c->height <= 0)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "no frame shape yet (render or rt_init_rand first)");
-    if (planes != 3 && planes != 5) return fail(c, RT_ERR_INVALID_ARGUMENT, "planes %d is neither 3 nor 5", planes);
-    if (shards < 1 || rows_per_shard < 1 || (long long)rows_per_shard * shards < c->height)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "bad assembly geometry: %d shards of %d rows for height %d", shards,
-                    rows_per_shard, c->height);
-    if (frames < 1u) return fail(c, RT_ERR_INVALID_ARGUMENT, "frames must be >= 1");
-    if ((long long)rows_per_shard * c->width > (1ll << 31))
-        return fail(c, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 floats");
-    return RT_OK;
-}
-
-// The assembly pass of a checked call from `gathered` (device memory on a GPU
-// context, on stream s: after every earlier pass that reads the assembled
-// frame, and they after it), then the snapshot's record
-int assemble_pass(rt_context* c, const float* gathered, int shards, int rows_per_shard, int planes, unsigned frames,
-                  unsigned batches, hipStream_t s) {
-    const size_t npix = (size_t)c->height * c->width;
-    const char* oom = "host assembled frame for %zu pixels";
-    if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_buf(c, c->as.sum, npix * 3 * sizeof(float), oom, npix);
-    if (!rc && planes == 5) rc = ensure_buf(c, c->as.mom, npix * sizeof(float2), oom, npix);
-    if (rc) {
-        if (!c->as.sum.p || (c->as.planes == 5 && !c->as.mom.p)) c->as.made = false;  // it went in the attempt to grow
-        return rc;
-    }
-    rt_asm_args A;
-    std::memset(&A, 0, sizeof A);
-    A.width = c->width;
-    A.rows = c->height;
-    A.shards = shards;
-    A.rows_per_shard = rows_per_shard;
-    A.planes = planes;
-    A.sum = c->as.sum.as<float>();
-    A.mom = planes == 5 ? c->as.mom.as<float2>() : nullptr;
-    A.block = const_cast<float*>(gathered);
-    c->as.made = false;  // until the pass is queued: a failure leaves no half-written snapshot behind
-    if (c->cpu) {
-        (void)c->assemble.begin(nullptr, true);
-        rt_cpu_assemble(A, c->threads);
-        (void)c->assemble.end(nullptr);
-    } else {
-        HIP_TRY(c, c->assemble.create(true));
-        if ((rc = order_after_all(c, s))) return rc;
-        HIP_TRY(c, c->assemble.begin(s, true));
-        HIP_TRY(c, rt_launch_assemble(A, c->deint_blocks, s));
-        HIP_TRY(c, c->assemble.end(s));
-    }
-    c->as.made = true;
-    c->as.planes = planes;
-    c->as.width = c->width;
-    c->as.height = c->height;
-    c->as.frames = frames;
-    c->as.batches = planes == 5 ? batches : 0u;
-    c->as.view = c->view;
-    return RT_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rt_export_shard(rt_context* c, int rows_per_shard, int planes, float* block, unsigned* frames_out,
-                    unsigned* batches_out) {
+// The host form of an export (`counted`: rt_export_shard_adaptive)
+int export_host(rt_context* c, int rows_per_shard, int planes, float* block, unsigned* frames_out,
+                unsigned* batches_out, bool counted) {
     if (!c || !block) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = export_check(c, rows_per_shard, planes);
+    int rc = export_check(c, rows_per_shard, planes, counted);
     if (rc) return rc;
     if (c->cpu) {
         if ((rc = export_pass(c, rows_per_shard, planes, block, nullptr))) return rc;
@@ -151,12 +113,13 @@ int rt_export_shard(rt_context* c, int rows_per_shard, int planes, float* block,
     return RT_OK;
 }
 
-int rt_export_shard_device(rt_context* c, int rows_per_shard, int planes, void* block_device, void* stream,
-                           unsigned* frames_out, unsigned* batches_out) {
+// The device form (`name`: the entry point)
+int export_device(rt_context* c, const char* name, int rows_per_shard, int planes, void* block_device, void* stream,
+                  unsigned* frames_out, unsigned* batches_out, bool counted) {
     if (!c || !block_device) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_export_shard_device: CPU context");
+    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "%s: CPU context", name);
     if ((uintptr_t)block_device & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "block_device not 4-byte aligned");
-    int rc = export_check(c, rows_per_shard, planes);
+    int rc = export_check(c, rows_per_shard, planes, counted);
     if (rc) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     if ((rc = export_pass(c, rows_per_shard, planes, (float*)block_device, s))) return rc;
@@ -164,10 +127,82 @@ int rt_export_shard_device(rt_context* c, int rows_per_shard, int planes, void* 
     return RT_OK;
 }
 
-int rt_assemble(rt_context* c, const float* gathered, int shards, int rows_per_shard, int planes, unsigned frames,
-                unsigned batches) {
+// What an assembly needs besides its source
+int assemble_check(rt_context* c, int shards, int rows_per_shard, int planes, unsigned frames, bool counted) {
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    if (c->width <= 0 || c->height <= 0)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "no frame shape yet (render or rt_init_rand first)");
+    if (const int rc = planes_check(c, planes, counted)) return rc;
+    if (shards < 1 || rows_per_shard < 1 || (long long)rows_per_shard * shards < c->height)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "bad assembly geometry: %d shards of %d rows for height %d", shards,
+                    rows_per_shard, c->height);
+    if (frames < 1u) return fail(c, RT_ERR_INVALID_ARGUMENT, "frames must be >= 1");
+    if ((long long)rows_per_shard * c->width > (1ll << 31))
+        return fail(c, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 floats");
+    return RT_OK;
+}
+
+// The assembly pass of a checked call from `gathered` (device memory on a GPU
+// context, on stream s: after every earlier pass that reads the assembled
+// frame, and they after it), then the snapshot's record.  The context has one
+// assembled frame: a counted and an uncounted assembly replace each other's.
+int assemble_pass(rt_context* c, const float* gathered, int shards, int rows_per_shard, int planes, unsigned frames,
+                  unsigned batches, hipStream_t s) {
+    const size_t npix = (size_t)c->height * c->width;
+    const char* oom = "host assembled frame for %zu pixels";
+    const bool counted = counted_planes(planes), moments = moment_planes(planes);
+    if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_buf(c, c->as.sum, npix * 3 * sizeof(float), oom, npix);
+    if (!rc && moments) rc = ensure_buf(c, c->as.mom, npix * sizeof(float2), oom, npix);
+    if (!rc && counted) rc = ensure_buf(c, c->as.cnt, npix * sizeof(uint2), oom, npix);
+    if (rc) {
+        // a buffer of the earlier frame went in the attempt to grow
+        if (!c->as.sum.p || (c->as.has_moments() && !c->as.mom.p) || (c->as.counted() && !c->as.cnt.p))
+            c->as.made = false;
+        return rc;
+    }
+    rt_asmc_args C;
+    std::memset(&C, 0, sizeof C);
+    rt_asm_args& A = C.a;
+    A.width = c->width;
+    A.rows = c->height;
+    A.shards = shards;
+    A.rows_per_shard = rows_per_shard;
+    A.planes = planes;
+    A.sum = c->as.sum.as<float>();
+    A.mom = moments ? c->as.mom.as<float2>() : nullptr;
+    A.block = const_cast<float*>(gathered);
+    C.cnt = counted ? c->as.cnt.as<uint2>() : nullptr;
+    c->as.made = false;  // until the pass is queued: a failure leaves no half-written snapshot behind
+    if (c->cpu) {
+        (void)c->assemble.begin(nullptr, true);
+        if (counted)
+            rt_cpu_assemble_adaptive(C, c->threads);
+        else
+            rt_cpu_assemble(A, c->threads);
+        (void)c->assemble.end(nullptr);
+    } else {
+        HIP_TRY(c, c->assemble.create(true));
+        if ((rc = order_after_all(c, s))) return rc;
+        HIP_TRY(c, c->assemble.begin(s, true));
+        HIP_TRY(c, counted ? rt_launch_assemble_adaptive(C, c->deint_blocks, s)
+                           : rt_launch_assemble(A, c->deint_blocks, s));
+        HIP_TRY(c, c->assemble.end(s));
+    }
+    c->as.made = true;
+    c->as.planes = planes;
+    c->as.width = c->width;
+    c->as.height = c->height;
+    c->as.frames = frames;
+    c->as.batches = moments ? batches : 0u;
+    c->as.view = c->view;
+    return RT_OK;
+}
+
+int assemble_host(rt_context* c, const float* gathered, int shards, int rows_per_shard, int planes, unsigned frames,
+                  unsigned batches, bool counted) {
     if (!c || !gathered) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = assemble_check(c, shards, rows_per_shard, planes, frames);
+    int rc = assemble_check(c, shards, rows_per_shard, planes, frames, counted);
     if (rc) return rc;
     if (c->cpu) return assemble_pass(c, gathered, shards, rows_per_shard, planes, frames, batches, nullptr);
     const size_t bytes = (size_t)shards * block_floats(c, rows_per_shard, planes) * sizeof(float);
@@ -179,27 +214,30 @@ int rt_assemble(rt_context* c, const float* gathered, int shards, int rows_per_s
     return rc;
 }
 
-int rt_assemble_device(rt_context* c, const void* gathered_device, int shards, int rows_per_shard, int planes,
-                       unsigned frames, unsigned batches, void* stream) {
+int assemble_device(rt_context* c, const char* name, const void* gathered_device, int shards, int rows_per_shard,
+                    int planes, unsigned frames, unsigned batches, void* stream, bool counted) {
     if (!c || !gathered_device) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_assemble_device: CPU context");
+    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "%s: CPU context", name);
     if ((uintptr_t)gathered_device & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "gathered_device not 4-byte aligned");
-    const int rc = assemble_check(c, shards, rows_per_shard, planes, frames);
+    const int rc = assemble_check(c, shards, rows_per_shard, planes, frames, counted);
     if (rc) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     return assemble_pass(c, (const float*)gathered_device, shards, rows_per_shard, planes, frames, batches, s);
 }
 
-int rt_assemble_multi(rt_context* const* ctxs, int n, int planes, int dst) {
+// rt_assemble_multi and, `counted`, rt_assemble_adaptive_multi (`name`): 3 and
+// 5 planes against 4 and 7, and only the counted form takes contexts in the
+// non-uniform state
+int assemble_multi(rt_context* const* ctxs, int n, int planes, int dst, bool counted, const char* name) {
     if (!ctxs || n <= 0 || dst < 0 || dst >= n || !ctxs[dst]) return RT_ERR_INVALID_ARGUMENT;
     rt_context* d = ctxs[dst];
-    if (planes != 0 && planes != 3 && planes != 5)
-        return fail(d, RT_ERR_INVALID_ARGUMENT, "planes %d is neither 0, 3 nor 5", planes);
+    const int plain = counted ? 4 : 3, full = counted ? 7 : 5;
+    if (planes != 0 && planes != plain && planes != full)
+        return fail(d, RT_ERR_INVALID_ARGUMENT, "planes %d is neither 0, %d nor %d", planes, plain, full);
     // every condition first: a refusal touches nothing
     for (int i = 0; i < n; i++) {
         if (!ctxs[i]) return fail(d, RT_ERR_INVALID_ARGUMENT, "null context %d", i);
-        if (ctxs[i]->cpu != d->cpu)
-            return fail(d, RT_ERR_INVALID_ARGUMENT, "rt_assemble_multi: GPU and CPU contexts mixed");
+        if (ctxs[i]->cpu != d->cpu) return fail(d, RT_ERR_INVALID_ARGUMENT, "%s: GPU and CPU contexts mixed", name);
         for (int j = 0; j < i; j++)
             if (ctxs[j] == ctxs[i]) return fail(d, RT_ERR_INVALID_ARGUMENT, "context listed twice");
     }
@@ -215,7 +253,7 @@ int rt_assemble_multi(rt_context* const* ctxs, int n, int planes, int dst) {
             return fail(d, RT_ERR_INVALID_ARGUMENT,
                         "context %d holds %dx%d offset %d stride %d, not shard %d of %d of %dx%d", i, c->width,
                         c->height, c->row_offset, c->row_stride, i, n, width, height);
-        if (c->st.nonuniform())
+        if (!counted && c->st.nonuniform())
             return fail(d, RT_ERR_UNSUPPORTED,
                         "the accumulation is non-uniform (rt_render_adaptive): a block carries one frame count");
         if (c->st.frame() < 2u) return fail(d, RT_ERR_INVALID_ARGUMENT, "no frame accumulated yet (render first)");
@@ -224,10 +262,10 @@ int rt_assemble_multi(rt_context* const* ctxs, int n, int planes, int dst) {
                         c->st.frame(), ctxs[0]->st.frame());
         current = current && c->st.current() && c->st.batches() == ctxs[0]->st.batches();
     }
-    if (planes == 0) planes = current ? 5 : 3;
-    if (planes == 5 && !current)
+    if (planes == 0) planes = current ? full : plain;
+    if (planes == full && !current)
         return fail(d, RT_ERR_INVALID_ARGUMENT,
-                    "5 planes need current moments of equal batches on every context (rt_set_moments)");
+                    "%d planes need current moments of equal batches on every context (rt_set_moments)", full);
     const int rps = (height + n - 1) / n;
     const unsigned frames = ctxs[0]->st.frames(), batches = ctxs[0]->st.batches();
     const size_t blk = block_floats(d, rps, planes);
@@ -273,6 +311,62 @@ int rt_assemble_multi(rt_context* const* ctxs, int n, int planes, int dst) {
     return rc;
 }
 
+}  // namespace
+
+extern "C" {
+
+int rt_export_shard(rt_context* c, int rows_per_shard, int planes, float* block, unsigned* frames_out,
+                    unsigned* batches_out) {
+    return export_host(c, rows_per_shard, planes, block, frames_out, batches_out, false);
+}
+
+int rt_export_shard_device(rt_context* c, int rows_per_shard, int planes, void* block_device, void* stream,
+                           unsigned* frames_out, unsigned* batches_out) {
+    return export_device(c, "rt_export_shard_device", rows_per_shard, planes, block_device, stream, frames_out,
+                         batches_out, false);
+}
+
+int rt_export_shard_adaptive(rt_context* c, int rows_per_shard, int planes, float* block, unsigned* frames_out,
+                             unsigned* batches_out) {
+    return export_host(c, rows_per_shard, planes, block, frames_out, batches_out, true);
+}
+
+int rt_export_shard_adaptive_device(rt_context* c, int rows_per_shard, int planes, void* block_device, void* stream,
+                                    unsigned* frames_out, unsigned* batches_out) {
+    return export_device(c, "rt_export_shard_adaptive_device", rows_per_shard, planes, block_device, stream,
+                         frames_out, batches_out, true);
+}
+
+int rt_assemble(rt_context* c, const float* gathered, int shards, int rows_per_shard, int planes, unsigned frames,
+                unsigned batches) {
+    return assemble_host(c, gathered, shards, rows_per_shard, planes, frames, batches, false);
+}
+
+int rt_assemble_device(rt_context* c, const void* gathered_device, int shards, int rows_per_shard, int planes,
+                       unsigned frames, unsigned batches, void* stream) {
+    return assemble_device(c, "rt_assemble_device", gathered_device, shards, rows_per_shard, planes, frames, batches,
+                           stream, false);
+}
+
+int rt_assemble_adaptive(rt_context* c, const float* gathered, int shards, int rows_per_shard, int planes,
+                         unsigned frames, unsigned batches) {
+    return assemble_host(c, gathered, shards, rows_per_shard, planes, frames, batches, true);
+}
+
+int rt_assemble_adaptive_device(rt_context* c, const void* gathered_device, int shards, int rows_per_shard, int planes,
+                                unsigned frames, unsigned batches, void* stream) {
+    return assemble_device(c, "rt_assemble_adaptive_device", gathered_device, shards, rows_per_shard, planes, frames,
+                           batches, stream, true);
+}
+
+int rt_assemble_multi(rt_context* const* ctxs, int n, int planes, int dst) {
+    return assemble_multi(ctxs, n, planes, dst, false, "rt_assemble_multi");
+}
+
+int rt_assemble_adaptive_multi(rt_context* const* ctxs, int n, int planes, int dst) {
+    return assemble_multi(ctxs, n, planes, dst, true, "rt_assemble_adaptive_multi");
+}
+
 int rt_assembled(const rt_context* c, unsigned* frames_out, unsigned* batches_out) {
     if (!c || !c->assembled_current()) return 0;
     if (frames_out) *frames_out = c->as.frames;
@@ -283,8 +377,8 @@ int rt_assembled(const rt_context* c, unsigned* frames_out, unsigned* batches_ou
 int rt_get_assembled(rt_context* c, float* accum_rgb, float* moments) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (!c->as.made) return fail(c, RT_ERR_INVALID_ARGUMENT, "no assembled frame (rt_assemble first)");
-    if (moments && c->as.planes != 5)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "the assembled frame has 3 planes: no moments");
+    if (moments && !c->as.has_moments())
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "the assembled frame has %d planes: no moments", c->as.planes);
     const size_t npix = (size_t)c->as.height * c->as.width;
     if (c->cpu) {
         if (accum_rgb) planes_to_rgb(c->as.sum.as<float>(), npix, accum_rgb);
@@ -298,6 +392,26 @@ int rt_get_assembled(rt_context* c, float* accum_rgb, float* moments) {
                                     {moments, c->as.mom.p, npix * sizeof(float2)}});
     if (rc) return rc;
     if (accum_rgb) planes_to_rgb(planes.data(), npix, accum_rgb);
+    return RT_OK;
+}
+
+int rt_get_assembled_counts(rt_context* c, uint32_t* frames_out, uint32_t* batches_out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->as.made) return fail(c, RT_ERR_INVALID_ARGUMENT, "no assembled frame (rt_assemble_adaptive first)");
+    if (!c->as.counted())
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "the assembled frame has %d planes: no counts", c->as.planes);
+    const size_t npix = (size_t)c->as.height * c->as.width;
+    const uint2* cn = c->as.cnt.as<uint2>();
+    std::vector<uint2> host;
+    if (!c->cpu) {
+        if (!try_resize(host, npix)) return fail(c, RT_ERR_OUT_OF_MEMORY, "host counts for %zu pixels", npix);
+        if (const int rc = read_settled(c, {{host.data(), cn, npix * sizeof(uint2)}})) return rc;
+        cn = host.data();
+    }
+    for (size_t i = 0; i < npix; i++) {
+        if (frames_out) frames_out[i] = cn[i].x;
+        if (batches_out) batches_out[i] = cn[i].y;
+    }
     return RT_OK;
 }
 

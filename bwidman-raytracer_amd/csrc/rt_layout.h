@@ -268,6 +268,21 @@ struct rt_asm_args {
     float* block;        // export writes the block; assembly reads `gathered` here
 };
 
+// One export or assembly pass of a COUNTED block (rt_assemble.h;
+// rt_export_shard_adaptive, rt_assemble_adaptive): the
+// block above with the pixels' counts behind it.  a.planes is 4 — R, G, B, n_p
+// — or 7 — R, G, B, M, M2, n_p, J_p; the count planes hold uint32 words.  Rows,
+// padding, `gathered` and the addressing are rt_asm_args' with this `planes`:
+//   cnt[y * width + x] = {word of plane 5, of plane 6}      planes == 7
+//   cnt[y * width + x] = {word of plane 3, 0}               planes == 4
+// The four kernels of rt_asm_args take that struct alone: its layout stays as
+// it is.
+struct rt_asmc_args {
+    rt_asm_args a;       // planes 4 or 7; mom only with 7
+    uint2* cnt;          // {n_p, J_p} per pixel: assembly writes it; export reads it, or, when null,
+    unsigned n, j;       // writes these two constants for every pixel of the shard (a uniform accumulation)
+};
+
 // One pass of the variance-guided filter (rt_denoise_var.h): the input stage
 // (reads accum, writes dst), a sigma pass (reads src) or a level; src and dst
 // hold {colour, variance}.

@@ -71,7 +71,10 @@ int ensure_guides(rt_context* c, hipStream_t s) {
 // pixel state is the full frame reads its own accumulation and never consults
 // an assembled frame: a stale snapshot cannot replace newer data.  A context
 // that holds a row shard reads its assembled frame (rt_assemble) while that is
-// current: its planes, its n and, with 5 planes, its moments and J.
+// current: its planes, its n and, with moments, theirs and J.  A COUNTED
+// assembled frame (rt_assemble_adaptive, section 19) also has every pixel's
+// {n_p, J_p} (frame_counts): the passes take those, as on a context in the
+// non-uniform state, and n and J here are only the uniform base.
 struct FrameSrc {
     const float* sum;    // frameSum, 3 planes of width * height
     const float2* mom;   // {M, M2} per pixel (read only when `tracked`)
@@ -82,7 +85,7 @@ struct FrameSrc {
 bool reads_assembled(const rt_context* c) { return c->holds_shard() && c->assembled_current(); }
 FrameSrc frame_src(const rt_context* c) {
     if (reads_assembled(c)) {
-        const bool mom = c->as.planes == 5;
+        const bool mom = c->as.has_moments();
         return {c->as.sum.as<float>(), mom ? c->as.mom.as<float2>() : nullptr, c->as.frames, mom ? c->as.batches : 0u,
                 mom};
     }
@@ -94,7 +97,15 @@ FrameSrc frame_src(const rt_context* c) {
 // reprojection (`who`) need besides their parameters
 int full_frame_check(rt_context* c, const char* who) {
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
-    if (reads_assembled(c)) return RT_OK;  // a snapshot with its own n >= 1 (a shard is never non-uniform)
+    if (reads_assembled(c)) {
+        // a snapshot with its own n >= 1, whatever state the shard's own accumulation is in; one with
+        // counts is a non-uniform frame, which the passes take only behind the same switch
+        if (c->as.counted() && !c->st.filters())
+            return fail(c, RT_ERR_UNSUPPORTED,
+                        "the assembled frame is non-uniform (rt_assemble_adaptive): %s takes one frame count for all "
+                        "pixels (rt_set_adaptive_filters)", who);
+        return RT_OK;
+    }
     const char* shard = "the context holds a row shard (offset %d, stride %d): %s needs a full frame%s";
     // (a stale assembled frame is reported whatever the shard's own frame counter says)
     if (c->holds_shard() && c->as.made)
@@ -109,12 +120,20 @@ int full_frame_check(rt_context* c, const char* who) {
     return RT_OK;
 }
 
-// The counts {n_p, J_p} a pass takes in the non-uniform state (then every
+// The counts {n_p, J_p} of the context's own pixel state while that is
+// non-uniform; null = uniform.  The adaptive call that wrote them ran inside the
+// render pass, so prepare_frame's order_after_all has ordered the stream behind
+// its update and resolve passes, whatever stream it ran on.
+const uint2* own_counts(const rt_context* c) { return c->st.nonuniform() ? c->ad_cnt.as<uint2>() : nullptr; }
+
+// The counts a full-frame pass takes beside frame_src's planes (then every
 // pixel's colour is rt_div(1, n_p) * frameSum_p, rt_atrous.h); null = uniform.
-// The adaptive call that wrote them ran inside the render pass, so
-// prepare_frame's order_after_all has ordered the stream behind its update and
-// resolve passes, whatever stream it ran on.
-const uint2* frame_counts(const rt_context* c) { return c->st.nonuniform() ? c->ad_cnt.as<uint2>() : nullptr; }
+// An assembled frame brings its own or has none: the shard's counts describe
+// other pixels.
+const uint2* frame_counts(const rt_context* c) {
+    if (reads_assembled(c)) return c->as.counted() ? c->as.cnt.as<uint2>() : nullptr;
+    return own_counts(c);
+}
 
 // iterations and sigmas of a filter (`term`: what its first sigma weighs)
 int filter_check(rt_context* c, int iterations, const char* term, float s0, float sn, float sp) {
@@ -255,13 +274,15 @@ int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream
         A.rd = 1.0f / ((float)(src.batches - 1u) * (float)src.frames);
         A.mom = src.mom;
     }
-    // non-uniform: the context's frame and batch counts are the uniform base,
-    // but every pixel's moments are current for its own n_p (the state lives
-    // only while tracking does): the choice is per pixel, J_p >= min_batches
+    // non-uniform: the frame and batch counts are the uniform base, but every
+    // pixel's moments are current for its own n_p (the state lives only while
+    // tracking does): the choice is per pixel, J_p >= min_batches.  The moments
+    // are the frame's own; a counted assembled frame of 4 planes has none and
+    // J_p = 0 everywhere, so every pixel takes the spatial estimate.
     if ((A.cnt = frame_counts(c))) {
         A.tracked = 0;
         A.min_batches = (unsigned)dp->min_batches;
-        A.mom = c->mom_m.as<float2>();
+        A.mom = src.mom;
     }
     A.rs = c->dn_rs.as<float>();
     float4* col[2] = {c->dn_col[0].as<float4>(), c->dn_col[1].as<float4>()};
@@ -564,7 +585,7 @@ int rt_get_variance(rt_context* c, float* var_out, float* lum_out) {
                     J ? "live" : "not live", J);
     const size_t npix = (size_t)c->rows * c->width;
     const float2* m = c->mom_m.as<float2>();
-    const uint2* cn = frame_counts(c);  // non-uniform: each pixel's own {n_p, J_p}
+    const uint2* cn = own_counts(c);  // non-uniform: each pixel's own {n_p, J_p}
     std::vector<float2> host;
     std::vector<uint2> host_cn;
     if (!c->cpu) {

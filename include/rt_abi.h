@@ -773,8 +773,10 @@ RT_API int rt_render_adaptive_multi(rt_context* const* ctxs, int n, const rt_ada
  * bit, and GPU and CPU contexts agree bit for bit.  No pass writes the
  * accumulation, the counts or the moments.  The switch has no other effect: a
  * uniform accumulation runs the same code whatever it says, and uniform renders
- * that continue a non-uniform accumulation, rt_render_multi, row shards and
- * RT_PRECISION_REFERENCE_FAST stay unsupported.  It may be changed at any time. */
+ * that continue a non-uniform accumulation, rt_render_multi and
+ * RT_PRECISION_REFERENCE_FAST stay unsupported.  On a shard context the same
+ * switch lets the passes read a counted assembled frame (rt_assemble_adaptive
+ * below).  It may be changed at any time. */
 RT_API int rt_set_adaptive_filters(rt_context* ctx, int enable);
 RT_API int rt_get_adaptive_filters(const rt_context* ctx);
 
@@ -867,6 +869,66 @@ RT_API int rt_assemble_drop(rt_context* ctx);
 /* Duration (ms) of the last assembly (HIP events on its stream; wall time on
  * a CPU context); -1 when unavailable. */
 RT_API float rt_last_assemble_ms(rt_context* ctx);
+
+/* ---- counted assembled frames: adaptive frames of row shards --------------------
+ *   After an adaptive call on row shards
+ * (rt_render_adaptive_shard*, rt_render_adaptive_multi) the accumulation is
+ * non-uniform and the calls above refuse it: their block carries one frame
+ * count.  A COUNTED block carries every pixel's {n_p, J_p}, and a COUNTED
+ * ASSEMBLED FRAME keeps them as a full-frame plane.  With
+ * rt_set_adaptive_filters() on, the three passes on the shard context read it
+ * through their count-aware forms: bit for bit what a single full-frame context
+ * gives after the same rt_render_adaptive calls with the switch on.  With the
+ * switch off they refuse a counted frame with RT_ERR_UNSUPPORTED.  Everything
+ * above keeps its behaviour and its refusals; an uncounted assembled frame is
+ * read as a uniform frame whatever the switch says and whatever state the
+ * shard's own accumulation is in.
+ *
+ * A counted block is `planes` planes of rows_per_shard * width 32-bit words;
+ * planes = 4: R, G, B of frameSum, then n_p (uint32); planes = 7: R, G, B, M,
+ * M2, n_p, J_p.  Rows, padding, GATHERED and the addressing are those above
+ * with this `planes`.  Every copy keeps every bit.  An assembled frame of 4
+ * planes has J_p = 0 for every pixel: rt_denoise_var takes the spatial estimate
+ * everywhere, whatever min_batches is.
+ *
+ * rt_export_shard_adaptive: as rt_export_shard, for a non-uniform accumulation
+ * (the counts are the context's, rt_get_counts) and for a uniform one (every
+ * pixel gets the context's {n, J}; nothing of the context is allocated or
+ * written, so a continuing uniform render behaves as if it had not been
+ * called).  Reports the uniform base (frame counter - 1, rt_moments_batches).
+ * RT_ERR_INVALID_ARGUMENT: a null pointer, planes not 4 or 7, rows_per_shard
+ * below the shard's rows, no frame accumulated yet, or planes == 7 while the
+ * tracked moments do not describe the accumulation.  The device form is
+ * ordered after the context's last render or adaptive call with its update and
+ * resolve passes, and the next render after it; CPU context:
+ * RT_ERR_UNSUPPORTED. */
+RT_API int rt_export_shard_adaptive(rt_context* ctx, int rows_per_shard, int planes, float* block,
+                                    unsigned* frames_out, unsigned* batches_out);
+RT_API int rt_export_shard_adaptive_device(rt_context* ctx, int rows_per_shard, int planes, void* block_device,
+                                           void* stream, unsigned* frames_out, unsigned* batches_out);
+/* Make the context's assembled frame, with its count plane, from gathered
+ * counted blocks.  `frames` and `batches` are the uniform base, which
+ * rt_assembled reports and no pass reads.  Arguments (planes 4 or 7), errors,
+ * currency, drop, timing and ordering are rt_assemble's and
+ * rt_assemble_device's; a refused call leaves an earlier assembled frame as it
+ * was.  A context has one assembled frame: rt_assemble and
+ * rt_assemble_adaptive replace each other's. */
+RT_API int rt_assemble_adaptive(rt_context* ctx, const float* gathered, int shards, int rows_per_shard, int planes,
+                                unsigned frames, unsigned batches);
+RT_API int rt_assemble_adaptive_device(rt_context* ctx, const void* gathered_device, int shards,
+                                       int rows_per_shard, int planes, unsigned frames, unsigned batches,
+                                       void* stream);
+/* The one-process companion of rt_render_adaptive_multi: rt_assemble_multi
+ * with counted blocks.  Every context may be uniform or non-uniform; the other
+ * conditions are rt_assemble_multi's, all checked before anything is touched.
+ * planes: 4, 7, or 0 = 7 if every context's moments are current (with equal
+ * batches) and 4 otherwise. */
+RT_API int rt_assemble_adaptive_multi(rt_context* const* ctxs, int n, int planes, int dst);
+/* Host readout of the last assembled frame's counts, w*h uint32 each (either
+ * may be NULL), as rt_get_counts'.  RT_ERR_INVALID_ARGUMENT: no assembled
+ * frame, or one without counts (rt_assemble).  rt_get_assembled reads a
+ * counted frame too, its moments only with 7 planes. */
+RT_API int rt_get_assembled_counts(rt_context* ctx, uint32_t* frames_out, uint32_t* batches_out);
 
 RT_API const char* rt_error_string(int status);
 RT_API const char* rt_last_error(const rt_context* ctx);
