@@ -85,6 +85,42 @@ def gather_rows(local_block, plan: ShardPlan, out=None, group=None, dst: int = 0
     return out if root else None
 
 
+def _gather_frame(renderer, plan, width, planes, group, dst, stream, counted):
+    """gather_frame (`counted` false) and gather_frame_adaptive: the same steps
+    over the Renderer's uncounted or counted export and assembly."""
+    import torch
+    import torch.distributed as dist
+    tail = "_adaptive" if counted else ""
+    export, export_device = getattr(renderer, "export_shard" + tail), getattr(renderer, f"export_shard{tail}_device")
+    assemble, assemble_device = getattr(renderer, "assemble" + tail), getattr(renderer, f"assemble{tail}_device")
+    rps = plan.rows_per_shard
+    root = (dist.get_rank(group) if group is not None else dist.get_rank()) == dst
+    if renderer.is_cpu:
+        # (float32 tensors are copied as bytes: the count planes' integers and any float's bits survive)
+        block = torch.zeros((planes, rps, width), dtype=torch.float32)
+        frames = batches = 0
+        if plan.rows > 0:  # (a rank beyond the image height sends padding only)
+            arr, frames, batches = export(rps, width, planes)
+            block.copy_(torch.from_numpy(arr))
+        gathered = gather_rows(block, plan, group=group, dst=dst)
+        if root:
+            assemble(gathered.numpy(), frames, batches)
+        return root
+    dev = torch.device("cuda", renderer.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        frames = batches = 0
+        if plan.rows > 0:
+            block = torch.empty((planes, rps, width), dtype=torch.float32, device=dev)
+            frames, batches = export_device(block.data_ptr(), rps, planes, s.cuda_stream)
+        else:
+            block = torch.zeros((planes, rps, width), dtype=torch.float32, device=dev)
+        gathered = gather_rows(block, plan, group=group, dst=dst)
+        if root:
+            assemble_device(gathered.data_ptr(), plan.world, rps, planes, frames, batches, s.cuda_stream)
+    return root
+
+
 def gather_frame(renderer, plan: ShardPlan, width: int, planes: int = 3, group=None, dst: int = 0, stream=None):
     """This rank's row shard into the assembled frame of rank `dst`
     (rt_export_shard -> gather_rows -> rt_assemble): afterwards `dst`'s
@@ -96,33 +132,7 @@ def gather_frame(renderer, plan: ShardPlan, width: int, planes: int = 3, group=N
     A GPU renderer exports, gathers (RCCL) and assembles on `stream` (a
     torch.cuda.Stream; None = torch's current one) without a host
     synchronisation; a CPU renderer goes through host tensors (gloo)."""
-    import torch
-    import torch.distributed as dist
-    rps = plan.rows_per_shard
-    root = (dist.get_rank(group) if group is not None else dist.get_rank()) == dst
-    if renderer.is_cpu:
-        block = torch.zeros((planes, rps, width), dtype=torch.float32)
-        frames = batches = 0
-        if plan.rows > 0:  # (a rank beyond the image height sends padding only)
-            arr, frames, batches = renderer.export_shard(rps, width, planes)
-            block.copy_(torch.from_numpy(arr))
-        gathered = gather_rows(block, plan, group=group, dst=dst)
-        if root:
-            renderer.assemble(gathered.numpy(), frames, batches)
-        return root
-    dev = torch.device("cuda", renderer.device)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.stream(s):
-        frames = batches = 0
-        if plan.rows > 0:
-            block = torch.empty((planes, rps, width), dtype=torch.float32, device=dev)
-            frames, batches = renderer.export_shard_device(block.data_ptr(), rps, planes, s.cuda_stream)
-        else:
-            block = torch.zeros((planes, rps, width), dtype=torch.float32, device=dev)
-        gathered = gather_rows(block, plan, group=group, dst=dst)
-        if root:
-            renderer.assemble_device(gathered.data_ptr(), plan.world, rps, planes, frames, batches, s.cuda_stream)
-    return root
+    return _gather_frame(renderer, plan, width, planes, group, dst, stream, counted=False)
 
 
 def gather_frame_adaptive(renderer, plan: ShardPlan, width: int, planes: int = 4, group=None, dst: int = 0,
@@ -138,35 +148,7 @@ def gather_frame_adaptive(renderer, plan: ShardPlan, width: int, planes: int = 4
 
     Streams, host synchronisation (none on a GPU renderer), the gloo path of a
     CPU renderer and the zero block of a rank without rows are gather_frame's."""
-    import torch
-    import torch.distributed as dist
-    rps = plan.rows_per_shard
-    root = (dist.get_rank(group) if group is not None else dist.get_rank()) == dst
-    if renderer.is_cpu:
-        # (float32 tensors are copied as bytes: the count planes' integers and any float's bits survive)
-        block = torch.zeros((planes, rps, width), dtype=torch.float32)
-        frames = batches = 0
-        if plan.rows > 0:
-            arr, frames, batches = renderer.export_shard_adaptive(rps, width, planes)
-            block.copy_(torch.from_numpy(arr))
-        gathered = gather_rows(block, plan, group=group, dst=dst)
-        if root:
-            renderer.assemble_adaptive(gathered.numpy(), frames, batches)
-        return root
-    dev = torch.device("cuda", renderer.device)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.stream(s):
-        frames = batches = 0
-        if plan.rows > 0:
-            block = torch.empty((planes, rps, width), dtype=torch.float32, device=dev)
-            frames, batches = renderer.export_shard_adaptive_device(block.data_ptr(), rps, planes, s.cuda_stream)
-        else:
-            block = torch.zeros((planes, rps, width), dtype=torch.float32, device=dev)
-        gathered = gather_rows(block, plan, group=group, dst=dst)
-        if root:
-            renderer.assemble_adaptive_device(gathered.data_ptr(), plan.world, rps, planes, frames, batches,
-                                              s.cuda_stream)
-    return root
+    return _gather_frame(renderer, plan, width, planes, group, dst, stream, counted=True)
 
 
 def render_adaptive(renderer, plan: ShardPlan, width: int, max_bounces: int = -1, group=None, stream=None, **params):

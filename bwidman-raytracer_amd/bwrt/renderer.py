@@ -464,41 +464,53 @@ class Renderer:
         return bool(self.lib.rt_get_adaptive_filters(self.ctx))
 
     # -- row shards into one frame: the assembled frame -------------------------
+    # (one body per pair of an uncounted entry point and its counted twin: `fn`
+    # is the C function)
+    def _export_shard(self, fn, rows_per_shard, width, planes):
+        block = np.empty((planes, rows_per_shard, width), np.float32)
+        n, j = C.c_uint(), C.c_uint()
+        self._check(fn(self.ctx, rows_per_shard, planes, block.ctypes.data, C.byref(n), C.byref(j)))
+        return block, n.value, j.value
+
+    def _export_shard_device(self, fn, block_ptr, rows_per_shard, planes, stream_ptr):
+        n, j = C.c_uint(), C.c_uint()
+        self._check(fn(self.ctx, rows_per_shard, planes, block_ptr, stream_ptr, C.byref(n), C.byref(j)))
+        return n.value, j.value
+
+    def _assemble(self, fn, gathered, frames, batches):
+        g = np.ascontiguousarray(gathered, dtype=np.float32)
+        shards, planes, rps, _ = g.shape
+        self._check(fn(self.ctx, g.ctypes.data, shards, rps, planes, frames, batches))
+
+    def _assemble_device(self, fn, gathered_ptr, shards, rows_per_shard, planes, frames, batches, stream_ptr):
+        self._check(fn(self.ctx, gathered_ptr, shards, rows_per_shard, planes, frames, batches, stream_ptr))
+
     def export_shard(self, rows_per_shard, width, planes=3):
         """rt_export_shard: this context's block, (planes, rows_per_shard,
         width) float32 — R, G, B of frameSum (then M, M2 with planes=5), the
         shard's rows first, zero rows after them — and the (frames, batches)
         it stands for."""
-        block = np.empty((planes, rows_per_shard, width), np.float32)
-        n, j = C.c_uint(), C.c_uint()
-        self._check(self.lib.rt_export_shard(self.ctx, rows_per_shard, planes, block.ctypes.data, C.byref(n),
-                                             C.byref(j)))
-        return block, n.value, j.value
+        return self._export_shard(self.lib.rt_export_shard, rows_per_shard, width, planes)
 
     def export_shard_device(self, block_ptr: int, rows_per_shard, planes=3, stream_ptr: int | None = None):
         """rt_export_shard_device: the block into device memory on a stream
         (asynchronous; after the last render, and the next render after it).
         Returns (frames, batches)."""
-        n, j = C.c_uint(), C.c_uint()
-        self._check(self.lib.rt_export_shard_device(self.ctx, rows_per_shard, planes, block_ptr, stream_ptr,
-                                                    C.byref(n), C.byref(j)))
-        return n.value, j.value
+        return self._export_shard_device(self.lib.rt_export_shard_device, block_ptr, rows_per_shard, planes, stream_ptr)
 
     def assemble(self, gathered, frames, batches=0):
         """rt_assemble: make the assembled frame from `gathered`, (shards,
         planes, rows_per_shard, width) float32 on the host: block r holds rows
         r, r + shards, ...  denoise, denoise_var and temporal on a renderer
         whose own state is a row shard then read it, with its frames / batches."""
-        g = np.ascontiguousarray(gathered, dtype=np.float32)
-        shards, planes, rps, _ = g.shape
-        self._check(self.lib.rt_assemble(self.ctx, g.ctypes.data, shards, rps, planes, frames, batches))
+        self._assemble(self.lib.rt_assemble, gathered, frames, batches)
 
     def assemble_device(self, gathered_ptr: int, shards, rows_per_shard, planes, frames, batches=0,
                         stream_ptr: int | None = None):
         """rt_assemble_device: the same from device memory on a stream
         (asynchronous; ordered against the passes that read the assembled frame)."""
-        self._check(self.lib.rt_assemble_device(self.ctx, gathered_ptr, shards, rows_per_shard, planes, frames,
-                                                batches, stream_ptr))
+        self._assemble_device(self.lib.rt_assemble_device, gathered_ptr, shards, rows_per_shard, planes, frames, batches,
+                              stream_ptr)
 
     def assembled(self):
         """rt_assembled: (frames, batches) of the current assembled frame, or None."""
@@ -527,20 +539,14 @@ class Renderer:
         or R, G, B, M, M2, n_p, J_p (planes=7); the count planes hold uint32
         bits (block[-1].view(np.uint32)) — and the (frames, batches) of the
         uniform base.  Works on a uniform and on a non-uniform accumulation."""
-        block = np.empty((planes, rows_per_shard, width), np.float32)
-        n, j = C.c_uint(), C.c_uint()
-        self._check(self.lib.rt_export_shard_adaptive(self.ctx, rows_per_shard, planes, block.ctypes.data, C.byref(n),
-                                                      C.byref(j)))
-        return block, n.value, j.value
+        return self._export_shard(self.lib.rt_export_shard_adaptive, rows_per_shard, width, planes)
 
     def export_shard_adaptive_device(self, block_ptr: int, rows_per_shard, planes=4, stream_ptr: int | None = None):
         """rt_export_shard_adaptive_device: the counted block into device
         memory on a stream (asynchronous; after the last render or adaptive
         call, and the next render after it).  Returns (frames, batches)."""
-        n, j = C.c_uint(), C.c_uint()
-        self._check(self.lib.rt_export_shard_adaptive_device(self.ctx, rows_per_shard, planes, block_ptr, stream_ptr,
-                                                             C.byref(n), C.byref(j)))
-        return n.value, j.value
+        return self._export_shard_device(self.lib.rt_export_shard_adaptive_device, block_ptr, rows_per_shard, planes,
+                                         stream_ptr)
 
     def assemble_adaptive(self, gathered, frames, batches=0):
         """rt_assemble_adaptive: make the assembled frame with its count plane
@@ -548,16 +554,14 @@ class Renderer:
         blocks on the host.  With set_adaptive_filters on, denoise, denoise_var
         and temporal on a renderer whose own state is a row shard then take
         every pixel's own counts; `frames` / `batches` are the uniform base."""
-        g = np.ascontiguousarray(gathered, dtype=np.float32)
-        shards, planes, rps, _ = g.shape
-        self._check(self.lib.rt_assemble_adaptive(self.ctx, g.ctypes.data, shards, rps, planes, frames, batches))
+        self._assemble(self.lib.rt_assemble_adaptive, gathered, frames, batches)
 
     def assemble_adaptive_device(self, gathered_ptr: int, shards, rows_per_shard, planes, frames, batches=0,
                                  stream_ptr: int | None = None):
         """rt_assemble_adaptive_device: the same from device memory on a stream
         (asynchronous; ordered like assemble_device)."""
-        self._check(self.lib.rt_assemble_adaptive_device(self.ctx, gathered_ptr, shards, rows_per_shard, planes,
-                                                         frames, batches, stream_ptr))
+        self._assemble_device(self.lib.rt_assemble_adaptive_device, gathered_ptr, shards, rows_per_shard, planes, frames,
+                              batches, stream_ptr)
 
     def assembled_counts(self, width, height):
         """rt_get_assembled_counts: the counted assembled frame's per-pixel
@@ -585,16 +589,21 @@ def shard_rows(height: int, row_offset: int, row_stride: int) -> int:
     return len(range(row_offset, height, row_stride)) if row_stride > 0 else 0
 
 
+def _multi_call(renderers, fn, *args, reports: int = 0):
+    """A C function over the renderers' contexts: fn(ctxs, n, *args); a failure
+    is raised by renderers[reports] (renderers[0] when that is no index)."""
+    arr = (C.c_void_p * len(renderers))(*[r.ctx.value for r in renderers])
+    rc = fn(arr, len(renderers), *args)
+    if rc != abi.RT_OK:
+        renderers[reports if 0 <= reports < len(renderers) else 0]._check(rc)
+
+
 def render_multi(renderers, width: int, height: int, samples: int) -> np.ndarray:
     """rt_render_multi: one image across several Renderers (one per GPU, same
     scene/camera set on each) in this process; returns (H, W, 4) uint8, row 0
     = bottom.  Renderer i renders rows y = i (mod len(renderers))."""
-    lib = renderers[0].lib
-    arr = (C.c_void_p * len(renderers))(*[r.ctx.value for r in renderers])
     out = np.empty((height, width, 4), np.uint8)
-    rc = lib.rt_render_multi(arr, len(renderers), width, height, samples, out.ctypes.data)
-    if rc != abi.RT_OK:
-        renderers[0]._check(rc)
+    _multi_call(renderers, renderers[0].lib.rt_render_multi, width, height, samples, out.ctypes.data)
     return out
 
 
@@ -604,11 +613,7 @@ def assemble_multi(renderers, planes: int = 0, dst: int = 0):
     temporal then run on the whole frame.  planes 3, 5 (with the moments), or
     0 = 5 when every renderer's moments are current.  Returns the (frames,
     batches) of the assembled frame."""
-    lib = renderers[0].lib
-    arr = (C.c_void_p * len(renderers))(*[r.ctx.value for r in renderers])
-    rc = lib.rt_assemble_multi(arr, len(renderers), planes, dst)
-    if rc != abi.RT_OK:
-        renderers[dst if 0 <= dst < len(renderers) else 0]._check(rc)
+    _multi_call(renderers, renderers[0].lib.rt_assemble_multi, planes, dst, reports=dst)
     return renderers[dst].assembled()
 
 
@@ -618,11 +623,7 @@ def assemble_adaptive_multi(renderers, planes: int = 0, dst: int = 0):
     non-uniform.  planes 4, 7 (with the moments), or 0 = 7 when every
     renderer's moments are current.  Returns the (frames, batches) of the
     uniform base; renderers[dst].assembled_counts() has the pixels' own."""
-    lib = renderers[0].lib
-    arr = (C.c_void_p * len(renderers))(*[r.ctx.value for r in renderers])
-    rc = lib.rt_assemble_adaptive_multi(arr, len(renderers), planes, dst)
-    if rc != abi.RT_OK:
-        renderers[dst if 0 <= dst < len(renderers) else 0]._check(rc)
+    _multi_call(renderers, renderers[0].lib.rt_assemble_adaptive_multi, planes, dst, reports=dst)
     return renderers[dst].assembled()
 
 
@@ -631,12 +632,8 @@ def render_adaptive_multi(renderers, width: int, height: int, max_bounces=-1, **
     the Renderers' row shards (export the row sums, copy every block to every
     renderer, select, render, resolve).  Returns ((H, W, 4) uint8 with row 0 =
     bottom, stats dict: selected and frames_total summed, stage times maxima)."""
-    lib = renderers[0].lib
-    arr = (C.c_void_p * len(renderers))(*[r.ctx.value for r in renderers])
     d = renderers[0].adaptive_params(**params)
     out = np.empty((height, width, 4), np.uint8)
     st = abi.AdaptiveStats()
-    rc = lib.rt_render_adaptive_multi(arr, len(renderers), C.byref(d), max_bounces, out.ctypes.data, C.byref(st))
-    if rc != abi.RT_OK:
-        renderers[0]._check(rc)
+    _multi_call(renderers, renderers[0].lib.rt_render_adaptive_multi, C.byref(d), max_bounces, out.ctypes.data, C.byref(st))
     return out, Renderer._stats(st)

@@ -7,6 +7,7 @@
 //   rt_render_adaptive.cpp  rt_render_adaptive*, rt_get_counts (rt_adaptive.h)
 //   rt_post.cpp     first-hit features, denoiser, temporal reprojection, moment readout
 //   rt_gather.cpp   rt_export_shard*, rt_assemble*, the assembled frame (rt_assemble.h)
+//   rt_group.h      over this header: lists of shard contexts, block geometry, the _device preamble
 //   rt_scene.cpp    the scene compiler (rt_scene.h; no HIP, no context)
 //   rt_accum.h      the accumulation's host state and its transition table (no HIP)
 // The render kernels: rt_launch.h declares the launchers of their units
@@ -17,7 +18,7 @@
 // and the reprojection share, host and device), rt_atrous_tile.h (the pixel and
 // the LDS-tiled kernel with their launchers, device only), then one header and
 // one unit each: rt_denoise, rt_denoise_var, rt_temporal, rt_moments; rt_assemble
-// (the copies behind rt_export_shard* and rt_assemble*).
+// (the two copies behind rt_export_shard* and rt_assemble*, counted or not).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -60,8 +61,6 @@ void rt_cpu_moments(const rt_mom_args& A, int threads);
 void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads);
 void rt_cpu_export_shard(const rt_asm_args& A, int threads);
 void rt_cpu_assemble(const rt_asm_args& A, int threads);
-void rt_cpu_export_shard_adaptive(const rt_asmc_args& C, int threads);
-void rt_cpu_assemble_adaptive(const rt_asmc_args& C, int threads);
 // a-trous filter (rt_denoise.hip)
 hipError_t rt_launch_denoise_level(const rt_dn_level& L, bool tiled, hipStream_t stream);
 // temporal reprojection (rt_temporal.hip)
@@ -70,12 +69,9 @@ hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream);
 hipError_t rt_launch_moments(const rt_mom_args& A, hipStream_t stream);
 // variance-guided filter (rt_denoise_var.hip): stage 0 input, 1 sigma pass, 2 level
 hipError_t rt_launch_denoise_var(const rt_dv_args& A, int stage, bool tiled, hipStream_t stream);
-// a shard's block and the assembled frame (rt_assemble.hip); max_blocks > 0 caps the grid
+// a shard's block and the assembled frame, counted or not (rt_assemble.hip); max_blocks > 0 caps the grid
 hipError_t rt_launch_export_shard(const rt_asm_args& A, int max_blocks, hipStream_t stream);
 hipError_t rt_launch_assemble(const rt_asm_args& A, int max_blocks, hipStream_t stream);
-// the same over a counted block (rt_export_shard_adaptive, rt_assemble_adaptive)
-hipError_t rt_launch_export_shard_adaptive(const rt_asmc_args& C, int max_blocks, hipStream_t stream);
-hipError_t rt_launch_assemble_adaptive(const rt_asmc_args& C, int max_blocks, hipStream_t stream);
 // adaptive sampling (rt_adaptive.hip): the count fill; stage 0 row sums, 1 column
 // sums + test + scan + scatter, 2 the listed pixels' moment update, 3 resolve
 hipError_t rt_launch_adaptive_fill(uint2* cnt, unsigned long long* total, long npix, unsigned n, unsigned J,
@@ -313,8 +309,8 @@ struct rt_context {
         int planes = 0, width = 0, height = 0;
         unsigned frames = 0, batches = 0;
         unsigned long long view = 0;
-        bool counted() const { return planes == 4 || planes == 7; }
-        bool has_moments() const { return planes == 5 || planes == 7; }
+        bool counted() const { return rt_block_shape_of(planes).counted; }
+        bool has_moments() const { return rt_block_shape_of(planes).moments; }
     };
     Assembled as;
     Buf as_block, as_gather;

@@ -349,20 +349,15 @@ void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads) {
 // The 4-byte items of the kernels, on the same pool: every item writes only its
 // own words, so the result does not depend on the thread count
 void rt_cpu_export_shard(const rt_asm_args& A, int threads) {
-    parallel_items(asm_items(A, A.rows_per_shard, 1), threads, [&](long q) { asm_export_item<1>(A, q); });
+    const bool counted = rt_block_shape_of(A.planes).counted;
+    parallel_items(asm_items(A, A.rows_per_shard, 1), threads,
+                   [&](long q) { counted ? asm_export_item<1, true>(A, q) : asm_export_item<1, false>(A, q); });
 }
 
 void rt_cpu_assemble(const rt_asm_args& A, int threads) {
-    parallel_items(asm_items(A, A.rows, 1), threads, [&](long q) { asm_assemble_item<1>(A, q); });
-}
-
-// counted blocks: likewise
-void rt_cpu_export_shard_adaptive(const rt_asmc_args& C, int threads) {
-    parallel_items(asmc_items(C, C.a.rows_per_shard, 1), threads, [&](long q) { asmc_export_item<1>(C, q); });
-}
-
-void rt_cpu_assemble_adaptive(const rt_asmc_args& C, int threads) {
-    parallel_items(asmc_items(C, C.a.rows, 1), threads, [&](long q) { asmc_assemble_item<1>(C, q); });
+    const bool counted = rt_block_shape_of(A.planes).counted;
+    parallel_items(asm_items(A, A.rows, 1), threads,
+                   [&](long q) { counted ? asm_assemble_item<1, true>(A, q) : asm_assemble_item<1, false>(A, q); });
 }
 
 // ---- adaptive sampling on the host (rt_adaptive.h) -----------------------------

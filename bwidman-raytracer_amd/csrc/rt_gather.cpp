@@ -4,24 +4,27 @@
 // rt_assemble_multi does both for the contexts of one process.  The _adaptive
 // forms do the same with COUNTED blocks, which carry every pixel's {n_p, J_p},
 // so that a frame sampled adaptively on row shards reaches the count-aware
-// passes.  rt_layout.h (rt_asm_args, rt_asmc_args) has the block layouts,
-// rt_assemble.h the indexing; the full-frame passes pick the assembled frame up
-// in rt_post.cpp (frame_src, frame_counts).
+// passes.  rt_layout.h (rt_asm_args) has the one block layout of the four plane
+// counts, rt_assemble.h the indexing; the full-frame passes pick the assembled
+// frame up in rt_post.cpp (frame_src, frame_counts).  Both forms run the same
+// passes: `counted` decides only which plane counts an entry point accepts and
+// whether it takes a non-uniform accumulation.
 //
 // No call reads or writes the RNG state or the frame counter or writes
 // frameSum, the moments or the counts; all are copies, so there is no
 // arithmetic to keep exact.
-#include "rt_context.h"
+#include "rt_group.h"
 
 namespace {
 
-// A block is uncounted (3 or 5 planes) or counted (4 or 7); the moments come
-// with 5 and 7
-bool counted_planes(int planes) { return planes == 4 || planes == 7; }
-bool moment_planes(int planes) { return planes == 5 || planes == 7; }
+// The plain and the full plane count of the uncounted (3, 5) and of the counted
+// (4, 7) entry points
+int plain_planes(bool counted) { return counted ? 4 : 3; }
+int full_planes(bool counted) { return counted ? 7 : 5; }
 int planes_check(rt_context* c, int planes, bool counted) {
-    if (counted ? counted_planes(planes) : (planes == 3 || planes == 5)) return RT_OK;
-    return fail(c, RT_ERR_INVALID_ARGUMENT, "planes %d is neither %s", planes, counted ? "4 nor 7" : "3 nor 5");
+    if (planes == plain_planes(counted) || planes == full_planes(counted)) return RT_OK;
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "planes %d is neither %d nor %d", planes, plain_planes(counted),
+                full_planes(counted));
 }
 
 size_t block_floats(const rt_context* c, int rows_per_shard, int planes) {
@@ -37,11 +40,9 @@ int export_check(rt_context* c, int rows_per_shard, int planes, bool counted) {
                     "the accumulation is non-uniform (rt_render_adaptive): a block carries one frame count");
     if (c->st.frame() < 2u || !c->accum.p || c->rows <= 0)
         return fail(c, RT_ERR_INVALID_ARGUMENT, "no frame accumulated yet (render first)");
-    if (rows_per_shard < c->rows)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "rows_per_shard %d below the shard's %d rows", rows_per_shard, c->rows);
-    if ((long long)rows_per_shard * c->width > (1ll << 31))
-        return fail(c, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 floats");
-    if (moment_planes(planes) && !c->st.current())
+    if (const int rc = block_rows_check(c, rows_per_shard)) return rc;
+    if (const int rc = block_plane_check(c, rows_per_shard)) return rc;
+    if (rt_block_shape_of(planes).moments && !c->st.current())
         return fail(c, RT_ERR_INVALID_ARGUMENT,
                     "%d planes need current moments (rt_set_moments before the accumulation's first render)", planes);
     return RT_OK;
@@ -53,37 +54,32 @@ int export_check(rt_context* c, int rows_per_shard, int planes, bool counted) {
 // counted block of a uniform accumulation gets the context's {n, J} for every
 // pixel: nothing of the context is written.
 int export_pass(rt_context* c, int rows_per_shard, int planes, float* block, hipStream_t s) {
-    rt_asmc_args C;
-    std::memset(&C, 0, sizeof C);
-    rt_asm_args& A = C.a;
+    const rt_block_shape B = rt_block_shape_of(planes);
+    rt_asm_args A;
+    std::memset(&A, 0, sizeof A);
     A.width = c->width;
     A.rows = c->rows;
     A.shards = 1;
     A.rows_per_shard = rows_per_shard;
     A.planes = planes;
     A.sum = c->accum.as<float>();
-    A.mom = moment_planes(planes) ? c->mom_m.as<float2>() : nullptr;
+    A.mom = B.moments ? c->mom_m.as<float2>() : nullptr;
     A.block = block;
-    const bool counted = counted_planes(planes);
-    if (counted) {
-        C.cnt = c->st.nonuniform() ? c->ad_cnt.as<uint2>() : nullptr;
-        C.n = c->st.frames();
-        C.j = c->st.batches();
+    if (B.counted) {
+        A.cnt = c->st.nonuniform() ? c->ad_cnt.as<uint2>() : nullptr;
+        A.n = c->st.frames();
+        A.j = c->st.batches();
     }
     if (c->cpu) {
         (void)c->xport.begin(nullptr, false);
-        if (counted)
-            rt_cpu_export_shard_adaptive(C, c->threads);
-        else
-            rt_cpu_export_shard(A, c->threads);
+        rt_cpu_export_shard(A, c->threads);
         (void)c->xport.end(nullptr);
         return RT_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, c->xport.create(false));
     if (const int rc = order_after_all(c, s)) return rc;
-    HIP_TRY(c, counted ? rt_launch_export_shard_adaptive(C, c->deint_blocks, s)
-                       : rt_launch_export_shard(A, c->deint_blocks, s));
+    HIP_TRY(c, rt_launch_export_shard(A, c->deint_blocks, s));
     HIP_TRY(c, c->xport.end(s));
     return RT_OK;
 }
@@ -116,12 +112,10 @@ int export_host(rt_context* c, int rows_per_shard, int planes, float* block, uns
 // The device form (`name`: the entry point)
 int export_device(rt_context* c, const char* name, int rows_per_shard, int planes, void* block_device, void* stream,
                   unsigned* frames_out, unsigned* batches_out, bool counted) {
-    if (!c || !block_device) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "%s: CPU context", name);
-    if ((uintptr_t)block_device & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "block_device not 4-byte aligned");
-    int rc = export_check(c, rows_per_shard, planes, counted);
+    hipStream_t s;
+    int rc = device_call(c, name, {{block_device, "block_device", true}}, stream, &s);
     if (rc) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = export_check(c, rows_per_shard, planes, counted))) return rc;
     if ((rc = export_pass(c, rows_per_shard, planes, (float*)block_device, s))) return rc;
     report(c, frames_out, batches_out);
     return RT_OK;
@@ -133,13 +127,9 @@ int assemble_check(rt_context* c, int shards, int rows_per_shard, int planes, un
     if (c->width <= 0 || c->height <= 0)
         return fail(c, RT_ERR_INVALID_ARGUMENT, "no frame shape yet (render or rt_init_rand first)");
     if (const int rc = planes_check(c, planes, counted)) return rc;
-    if (shards < 1 || rows_per_shard < 1 || (long long)rows_per_shard * shards < c->height)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "bad assembly geometry: %d shards of %d rows for height %d", shards,
-                    rows_per_shard, c->height);
+    if (const int rc = block_cover_check(c, "assembly", shards, rows_per_shard)) return rc;
     if (frames < 1u) return fail(c, RT_ERR_INVALID_ARGUMENT, "frames must be >= 1");
-    if ((long long)rows_per_shard * c->width > (1ll << 31))
-        return fail(c, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 floats");
-    return RT_OK;
+    return block_plane_check(c, rows_per_shard);
 }
 
 // The assembly pass of a checked call from `gathered` (device memory on a GPU
@@ -150,7 +140,7 @@ int assemble_pass(rt_context* c, const float* gathered, int shards, int rows_per
                   unsigned batches, hipStream_t s) {
     const size_t npix = (size_t)c->height * c->width;
     const char* oom = "host assembled frame for %zu pixels";
-    const bool counted = counted_planes(planes), moments = moment_planes(planes);
+    const bool counted = rt_block_shape_of(planes).counted, moments = rt_block_shape_of(planes).moments;
     if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
     int rc = ensure_buf(c, c->as.sum, npix * 3 * sizeof(float), oom, npix);
     if (!rc && moments) rc = ensure_buf(c, c->as.mom, npix * sizeof(float2), oom, npix);
@@ -161,9 +151,8 @@ int assemble_pass(rt_context* c, const float* gathered, int shards, int rows_per
             c->as.made = false;
         return rc;
     }
-    rt_asmc_args C;
-    std::memset(&C, 0, sizeof C);
-    rt_asm_args& A = C.a;
+    rt_asm_args A;
+    std::memset(&A, 0, sizeof A);
     A.width = c->width;
     A.rows = c->height;
     A.shards = shards;
@@ -172,21 +161,17 @@ int assemble_pass(rt_context* c, const float* gathered, int shards, int rows_per
     A.sum = c->as.sum.as<float>();
     A.mom = moments ? c->as.mom.as<float2>() : nullptr;
     A.block = const_cast<float*>(gathered);
-    C.cnt = counted ? c->as.cnt.as<uint2>() : nullptr;
+    A.cnt = counted ? c->as.cnt.as<uint2>() : nullptr;
     c->as.made = false;  // until the pass is queued: a failure leaves no half-written snapshot behind
     if (c->cpu) {
         (void)c->assemble.begin(nullptr, true);
-        if (counted)
-            rt_cpu_assemble_adaptive(C, c->threads);
-        else
-            rt_cpu_assemble(A, c->threads);
+        rt_cpu_assemble(A, c->threads);
         (void)c->assemble.end(nullptr);
     } else {
         HIP_TRY(c, c->assemble.create(true));
         if ((rc = order_after_all(c, s))) return rc;
         HIP_TRY(c, c->assemble.begin(s, true));
-        HIP_TRY(c, counted ? rt_launch_assemble_adaptive(C, c->deint_blocks, s)
-                           : rt_launch_assemble(A, c->deint_blocks, s));
+        HIP_TRY(c, rt_launch_assemble(A, c->deint_blocks, s));
         HIP_TRY(c, c->assemble.end(s));
     }
     c->as.made = true;
@@ -216,12 +201,10 @@ int assemble_host(rt_context* c, const float* gathered, int shards, int rows_per
 
 int assemble_device(rt_context* c, const char* name, const void* gathered_device, int shards, int rows_per_shard,
                     int planes, unsigned frames, unsigned batches, void* stream, bool counted) {
-    if (!c || !gathered_device) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "%s: CPU context", name);
-    if ((uintptr_t)gathered_device & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "gathered_device not 4-byte aligned");
-    const int rc = assemble_check(c, shards, rows_per_shard, planes, frames, counted);
+    hipStream_t s;
+    int rc = device_call(c, name, {{gathered_device, "gathered_device", true}}, stream, &s);
     if (rc) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = assemble_check(c, shards, rows_per_shard, planes, frames, counted))) return rc;
     return assemble_pass(c, (const float*)gathered_device, shards, rows_per_shard, planes, frames, batches, s);
 }
 
@@ -231,42 +214,32 @@ int assemble_device(rt_context* c, const char* name, const void* gathered_device
 int assemble_multi(rt_context* const* ctxs, int n, int planes, int dst, bool counted, const char* name) {
     if (!ctxs || n <= 0 || dst < 0 || dst >= n || !ctxs[dst]) return RT_ERR_INVALID_ARGUMENT;
     rt_context* d = ctxs[dst];
-    const int plain = counted ? 4 : 3, full = counted ? 7 : 5;
+    const int plain = plain_planes(counted), full = full_planes(counted);
     if (planes != 0 && planes != plain && planes != full)
         return fail(d, RT_ERR_INVALID_ARGUMENT, "planes %d is neither 0, %d nor %d", planes, plain, full);
     // every condition first: a refusal touches nothing
-    for (int i = 0; i < n; i++) {
-        if (!ctxs[i]) return fail(d, RT_ERR_INVALID_ARGUMENT, "null context %d", i);
-        if (ctxs[i]->cpu != d->cpu) return fail(d, RT_ERR_INVALID_ARGUMENT, "%s: GPU and CPU contexts mixed", name);
-        for (int j = 0; j < i; j++)
-            if (ctxs[j] == ctxs[i]) return fail(d, RT_ERR_INVALID_ARGUMENT, "context listed twice");
-    }
+    if (const int rc = group_scan(ctxs, n, d, name)) return rc;
     const int width = d->width, height = d->height;
     if (!d->has_scene) return fail(d, RT_ERR_NO_SCENE, "rt_set_scene() not called");
     if (width <= 0 || height <= 0)
         return fail(d, RT_ERR_INVALID_ARGUMENT, "no frame shape yet (render or rt_init_rand first)");
-    const int active = n < height ? n : height;  // contexts beyond the image height hold no rows
+    const int active = group_active(n, height);
     bool current = true;
     for (int i = 0; i < active; i++) {
         const rt_context* c = ctxs[i];
-        if (c->width != width || c->height != height || c->row_offset != i || c->row_stride != n || !c->accum.p)
-            return fail(d, RT_ERR_INVALID_ARGUMENT,
-                        "context %d holds %dx%d offset %d stride %d, not shard %d of %d of %dx%d", i, c->width,
-                        c->height, c->row_offset, c->row_stride, i, n, width, height);
+        if (const int rc = group_shard_check(d, c, i, n, c->row_stride, width, height)) return rc;
         if (!counted && c->st.nonuniform())
             return fail(d, RT_ERR_UNSUPPORTED,
                         "the accumulation is non-uniform (rt_render_adaptive): a block carries one frame count");
         if (c->st.frame() < 2u) return fail(d, RT_ERR_INVALID_ARGUMENT, "no frame accumulated yet (render first)");
-        if (c->st.frame() != ctxs[0]->st.frame())
-            return fail(d, RT_ERR_INVALID_ARGUMENT, "frame counters differ (context %d: %u, context 0: %u)", i,
-                        c->st.frame(), ctxs[0]->st.frame());
+        if (const int rc = group_counters_check(d, c, i, ctxs[0], false)) return rc;
         current = current && c->st.current() && c->st.batches() == ctxs[0]->st.batches();
     }
     if (planes == 0) planes = current ? full : plain;
     if (planes == full && !current)
         return fail(d, RT_ERR_INVALID_ARGUMENT,
                     "%d planes need current moments of equal batches on every context (rt_set_moments)", full);
-    const int rps = (height + n - 1) / n;
+    const int rps = group_rows_per_shard(n, height);
     const unsigned frames = ctxs[0]->st.frames(), batches = ctxs[0]->st.batches();
     const size_t blk = block_floats(d, rps, planes);
     if (!d->cpu) HIP_TRY(d, hipSetDevice(d->device));
@@ -276,36 +249,20 @@ int assemble_multi(rt_context* const* ctxs, int n, int planes, int dst, bool cou
     float* gathered = d->as_gather.as<float>();
     // (as_gather is read only by assemblies of host forms, which synchronise before they return)
     // a failure at context i leaves exports and copies of contexts 0..i-1 in flight: drain them
-    auto drain = [&](int launched, int code) {
-        for (int j = 0; j < launched && !d->cpu; j++) {
-            (void)hipSetDevice(ctxs[j]->device);
-            (void)hipStreamSynchronize(ctxs[j]->stream);
-        }
-        return code;
-    };
     for (int i = 0; i < active; i++) {
         rt_context* c = ctxs[i];
         if (c->cpu) {
-            if ((rc = export_pass(c, rps, planes, gathered + (size_t)i * blk, nullptr))) return drain(i, rc);
+            if ((rc = export_pass(c, rps, planes, gathered + (size_t)i * blk, nullptr))) return rc;
             continue;
         }
-        if (hipSetDevice(c->device) != hipSuccess) return drain(i, fail(c, RT_ERR_HIP, "hipSetDevice"));
-        if ((rc = ensure_buf(c, c->as_block, blk * sizeof(float)))) return drain(i, rc);
-        if ((rc = export_pass(c, rps, planes, c->as_block.as<float>(), c->stream))) return drain(i + 1, rc);
-        const hipError_t e =
-            c->device == d->device
-                ? hipMemcpyAsync(gathered + (size_t)i * blk, c->as_block.p, blk * sizeof(float), hipMemcpyDeviceToDevice,
-                                 c->stream)
-                : hipMemcpyPeerAsync(gathered + (size_t)i * blk, d->device, c->as_block.p, c->device,
-                                     blk * sizeof(float), c->stream);
-        if (e != hipSuccess) return drain(i + 1, hip_fail(c, e, "block copy"));
+        if (hipSetDevice(c->device) != hipSuccess) return group_drain(ctxs, i, fail(c, RT_ERR_HIP, "hipSetDevice"));
+        if ((rc = ensure_buf(c, c->as_block, blk * sizeof(float)))) return group_drain(ctxs, i, rc);
+        if ((rc = export_pass(c, rps, planes, c->as_block.as<float>(), c->stream))) return group_drain(ctxs, i + 1, rc);
+        const hipError_t e = group_copy(gathered + (size_t)i * blk, d, c->as_block.p, c, blk * sizeof(float));
+        if (e != hipSuccess) return group_drain(ctxs, i + 1, hip_fail(c, e, "block copy"));
     }
     // the blocks are in place before the assembly is queued (the call synchronises anyway)
-    for (int i = 0; i < active && !d->cpu; i++) {
-        rt_context* c = ctxs[i];
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    if ((rc = group_sync(ctxs, active))) return rc;
     rc = assemble_pass(d, gathered, n, rps, planes, frames, batches, d->stream);
     if (!d->cpu) HIP_TRY(d, hipStreamSynchronize(d->stream));
     return rc;

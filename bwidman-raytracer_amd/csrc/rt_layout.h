@@ -244,43 +244,55 @@ struct rt_mom_args {
     float2* mom;         // {M, M2}: weighted mean of the batch luminances and sum of k_j (l_j - mean)^2
 };
 
-// One export or assembly pass (rt_assemble.h; rt_export_shard, rt_assemble).
-// A context's BLOCK is `planes` planes of rows_per_shard * width floats:
-// planes 0..2 are R, G, B of its frameSum, and with planes == 5 planes 3 and 4
-// are M and M2 of its tracked moments.  A plane holds the shard's rows in
+// One export or assembly pass (rt_assemble.h; rt_export_shard*, rt_assemble*;
+// DESIGN.md sections 17, 19 and 20).  A context's BLOCK is `planes` planes of
+// rows_per_shard * width 4-byte words:
+//
+//   planes   0  1  2   3    4    5    6     moments   counts
+//     3      R  G  B                          no        no
+//     5      R  G  B   M    M2                yes       no
+//     4      R  G  B   n_p                    no        yes
+//     7      R  G  B   M    M2   n_p  J_p     yes       yes
+//
+// R, G, B (the context's frameSum) and M, M2 (its tracked moments) are float
+// words, n_p and J_p (the pixels' counts) uint32 words; rt_block_shape derives
+// the two columns on the right from `planes`.  A plane holds the shard's rows in
 // shard order (row j is image row row_offset + j * row_stride), then padding
 // rows up to rows_per_shard, which export zero-fills and assembly never reads.
 // GATHERED is `shards` consecutive blocks, block r = rows r, r + shards, ...
 // (the layout of rt_deinterleave_rows_device and bwrt.dist.gather_rows).  The
-// assembled frame has frameSum's full-frame layout: with r = y % shards and
-// j = y / shards,
-//   sum[k * width * height + y * width + x]
-//       = gathered[((r * planes + k) * rows_per_shard + j) * width + x]    k < 3
-//   mom[y * width + x] = {the same with k = 3, with k = 4}
+// assembled frame has the context's full-frame layouts: with r = y % shards,
+// j = y / shards and
+//   word(k) = gathered[((r * planes + k) * rows_per_shard + j) * width + x],
+//   sum[k * width * height + y * width + x] = word(k)                  k < 3
+//   mom[y * width + x] = {word(3), word(4)}                            moments
+//   cnt[y * width + x] = {word(first count plane), word(the next) or 0 without moments}
+struct rt_block_shape {
+    bool moments, counted;
+    int slots;           // items per pixel group of a pass: one per colour plane, one for {M, M2}, one for the counts
+    int count_plane;     // the first count plane
+};
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline rt_block_shape rt_block_shape_of(int planes) {
+    const bool moments = planes == 5 || planes == 7, counted = planes == 4 || planes == 7;
+    return {moments, counted, 3 + (int)moments + (int)counted, moments ? 5 : 3};
+}
 struct rt_asm_args {
+    // (the count fields first: what the passes of an uncounted block read then
+    // lies in one run that ends at the kernel's last argument, and its scalar
+    // loads are grouped as before the fields came)
+    uint2* cnt;          // counted blocks, {n_p, J_p} per pixel: assembly writes it; export reads it, or, when null,
+    unsigned n, j;       // writes these two constants for every pixel of the shard (a uniform accumulation)
     int width;
     int rows;            // export: the shard's rows; assembly: the frame's height
     int shards;          // assembly: blocks in `gathered` (export: 1)
     int rows_per_shard;  // rows of one block plane (>= the shard's rows; shards * it >= height)
-    int planes;          // 3 or 5
+    int planes;          // 3, 5, 4 or 7
     float* sum;          // frameSum, 3 planes of rows * width: export reads it, assembly writes it
-    float2* mom;         // {M, M2} per pixel, likewise; only with 5 planes
+    float2* mom;         // {M, M2} per pixel, likewise; only with moments
     float* block;        // export writes the block; assembly reads `gathered` here
-};
-
-// One export or assembly pass of a COUNTED block (rt_assemble.h;
-// rt_export_shard_adaptive, rt_assemble_adaptive): the
-// block above with the pixels' counts behind it.  a.planes is 4 — R, G, B, n_p
-// — or 7 — R, G, B, M, M2, n_p, J_p; the count planes hold uint32 words.  Rows,
-// padding, `gathered` and the addressing are rt_asm_args' with this `planes`:
-//   cnt[y * width + x] = {word of plane 5, of plane 6}      planes == 7
-//   cnt[y * width + x] = {word of plane 3, 0}               planes == 4
-// The four kernels of rt_asm_args take that struct alone: its layout stays as
-// it is.
-struct rt_asmc_args {
-    rt_asm_args a;       // planes 4 or 7; mom only with 7
-    uint2* cnt;          // {n_p, J_p} per pixel: assembly writes it; export reads it, or, when null,
-    unsigned n, j;       // writes these two constants for every pixel of the shard (a uniform accumulation)
 };
 
 // One pass of the variance-guided filter (rt_denoise_var.h): the input stage

@@ -9,7 +9,7 @@
 #include <initializer_list>
 
 #include "rt_adaptive.h"
-#include "rt_context.h"
+#include "rt_group.h"
 
 namespace {
 
@@ -410,16 +410,6 @@ int host_call(rt_context* c, uint8_t* rgba_out, float* color_out, float* length_
     return read_back(c, npix, rgba_out, out.color, color_out, out.length, length_out);
 }
 
-// A device entry point (`name`): RT_OK and the stream of the call, or the failure
-int device_call(rt_context* c, const char* name, void* rgba_device, void* stream, hipStream_t* s) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "%s: CPU context", name);
-    if (rgba_device && ((uintptr_t)rgba_device & 3u))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
-    *s = stream ? (hipStream_t)stream : c->stream;
-    return RT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -485,7 +475,7 @@ int rt_denoise(rt_context* c, const rt_denoise_params* dp, uint8_t* rgba_out, fl
 int rt_denoise_device(rt_context* c, const rt_denoise_params* dp, void* rgba_device, void* stream) {
     hipStream_t s;
     Result out;
-    const int rc = device_call(c, "rt_denoise_device", rgba_device, stream, &s);
+    const int rc = device_call(c, "rt_denoise_device", {{rgba_device, "rgba_device", false}}, stream, &s);
     return rc ? rc : denoise_levels(c, dp, s, (unsigned*)rgba_device, out);
 }
 
@@ -516,7 +506,7 @@ int rt_denoise_var(rt_context* c, const rt_denoise_var_params* dp, uint8_t* rgba
 int rt_denoise_var_device(rt_context* c, const rt_denoise_var_params* dp, void* rgba_device, void* stream) {
     hipStream_t s;
     Result out;
-    const int rc = device_call(c, "rt_denoise_var_device", rgba_device, stream, &s);
+    const int rc = device_call(c, "rt_denoise_var_device", {{rgba_device, "rgba_device", false}}, stream, &s);
     return rc ? rc : denoise_var_passes(c, dp, s, (unsigned*)rgba_device, out);
 }
 
@@ -545,7 +535,7 @@ int rt_temporal_device(rt_context* c, const rt_temporal_params* tp, const rt_den
                        void* stream) {
     hipStream_t s;
     Result out;
-    const int rc = device_call(c, "rt_temporal_device", rgba_device, stream, &s);
+    const int rc = device_call(c, "rt_temporal_device", {{rgba_device, "rgba_device", false}}, stream, &s);
     return rc ? rc : temporal_pass(c, tp, dn, s, (unsigned*)rgba_device, out);
 }
 

@@ -6,7 +6,7 @@
 // the reference's float operations in the reference's order.
 #include <cmath>
 
-#include "rt_context.h"
+#include "rt_group.h"
 
 static int prepare(rt_context* c, const rt_render_params* p, rt_kparams& K, unsigned& first) {
     const HostFpEnv fp;
@@ -381,55 +381,42 @@ int rt_render(rt_context* c, int width, int height, int samples, uint8_t* rgba_o
 // buffers and are interleaved on the host.
 int rt_render_multi(rt_context* const* ctxs, int n, int width, int height, int samples, uint8_t* rgba_out) {
     if (!ctxs || n <= 0 || width <= 0 || height <= 0 || samples <= 0) return RT_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < n; i++) {
-        if (!ctxs[i]) return RT_ERR_INVALID_ARGUMENT;
-        if (ctxs[i]->cpu) return fail(ctxs[i], RT_ERR_UNSUPPORTED, "rt_render_multi: CPU context");
-        for (int j = 0; j < i; j++)
-            if (ctxs[j] == ctxs[i]) return fail(ctxs[i], RT_ERR_INVALID_ARGUMENT, "context listed twice");
-    }
-    const int active = n < height ? n : height;  // contexts beyond the image height get no rows
+    // (every entry reports on itself, a null one with the bare code)
+    if (const int rc = group_scan(ctxs, n, nullptr, "rt_render_multi", true)) return rc;
+    const int active = group_active(n, height);
     // a failure at context i leaves contexts 0..i-1 with renders and copies
     // into their pinned buffers in flight: drain them before returning, so a
     // later call cannot reuse host_rgba under a running copy
-    auto drain = [&](int launched, int rc) {
-        for (int j = 0; j < launched; j++) {
-            (void)hipSetDevice(ctxs[j]->device);
-            (void)hipStreamSynchronize(ctxs[j]->stream);
-        }
-        return rc;
-    };
     for (int i = 0; i < active; i++) {
         rt_context* c = ctxs[i];
         const rt_render_params p = next_frames(c, width, height, samples, i, n);
         rt_kparams K;
         unsigned first = 0;
         int rc = prepare(c, &p, K, first);
-        if (rc) return drain(i, rc);
+        if (rc) return group_drain(ctxs, i, rc);
         const size_t bytes = (size_t)c->rows * width * 4;
         rc = ensure_buf(c, c->rgba, bytes);
-        if (rc) return drain(i, rc);
+        if (rc) return group_drain(ctxs, i, rc);
         if (c->host_rgba_bytes < bytes) {
             rc = quiesce(c);
-            if (rc) return drain(i, rc);
-            if (hipStreamSynchronize(c->stream) != hipSuccess) return drain(i, fail(c, RT_ERR_HIP, "stream sync"));
+            if (rc) return group_drain(ctxs, i, rc);
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return group_drain(ctxs, i, fail(c, RT_ERR_HIP, "stream sync"));
             if (c->host_rgba) (void)hipHostFree(c->host_rgba);
             c->host_rgba = nullptr;
             c->host_rgba_bytes = 0;
             const hipError_t e = hipHostMalloc(&c->host_rgba, bytes, hipHostMallocDefault);
-            if (e != hipSuccess) return drain(i, hip_fail(c, e, "hipHostMalloc"));
+            if (e != hipSuccess) return group_drain(ctxs, i, hip_fail(c, e, "hipHostMalloc"));
             c->host_rgba_bytes = bytes;
         }
         K.rgba = c->rgba.as<unsigned>();
         rc = launch(c, K, c->stream, first, samples);
-        if (rc) return drain(i + 1, rc);
+        if (rc) return group_drain(ctxs, i + 1, rc);
         const hipError_t e = hipMemcpyAsync(c->host_rgba, c->rgba.p, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) return drain(i + 1, hip_fail(c, e, "hipMemcpyAsync"));
+        if (e != hipSuccess) return group_drain(ctxs, i + 1, hip_fail(c, e, "hipMemcpyAsync"));
     }
-    for (int i = 0; i < active; i++) {
-        rt_context* c = ctxs[i];
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (!rgba_out) continue;
+    if (const int rc = group_sync(ctxs, active)) return rc;
+    for (int i = 0; i < active && rgba_out; i++) {
+        const rt_context* c = ctxs[i];
         const uint8_t* src = (const uint8_t*)c->host_rgba;
         for (int j = 0; j < c->rows; j++)
             std::memcpy(rgba_out + ((size_t)(i + j * n) * width) * 4, src + (size_t)j * width * 4, (size_t)width * 4);
@@ -438,16 +425,14 @@ int rt_render_multi(rt_context* const* ctxs, int n, int width, int height, int s
 }
 
 int rt_render_device(rt_context* c, const rt_render_params* p, void* rgba_device, void* stream) {
-    if (c && c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_render_device: CPU context");
+    int rc = device_ctx(c, "rt_render_device");
+    if (rc) return rc;
     rt_kparams K;
     unsigned first = 0;
-    int rc = prepare(c, p, K, first);
-    if (rc) return rc;
-    if (rgba_device && ((uintptr_t)rgba_device & 3u))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
+    if ((rc = prepare(c, p, K, first))) return rc;
+    if ((rc = device_aligned(c, {{rgba_device, "rgba_device", false}}))) return rc;
     K.rgba = (unsigned*)rgba_device;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return launch(c, K, s, first, p->samples);
+    return launch(c, K, device_stream(c, stream), first, p->samples);
 }
 
 int rt_deinterleave_rows_device(rt_context* c, const void* gathered, void* image, int width, int height,

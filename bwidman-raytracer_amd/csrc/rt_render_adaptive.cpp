@@ -18,7 +18,7 @@
 // frame's over the shard's rows * width.
 #include <cmath>
 
-#include "rt_context.h"
+#include "rt_group.h"
 
 namespace {
 
@@ -247,11 +247,8 @@ size_t block_words(const rt_context* c, int rows_per_shard) { return (size_t)3 *
 int export_rows_check(rt_context* c, const rt_adaptive_params* p, int rows_per_shard) {
     int mb = -1;
     if (const int rc = params_check(c, p, mb, true)) return rc;
-    if (rows_per_shard < c->rows)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "rows_per_shard %d below the shard's %d rows", rows_per_shard, c->rows);
-    if ((long long)rows_per_shard * c->width > (1ll << 31))
-        return fail(c, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 words");
-    return RT_OK;
+    if (const int rc = block_rows_check(c, rows_per_shard)) return rc;
+    return block_plane_check(c, rows_per_shard);
 }
 
 // Phase 1 of a checked call: the row sums of the context's own rows into
@@ -303,12 +300,8 @@ int shard_call_check(rt_context* c, const rt_adaptive_params* p, int& max_bounce
     if (shards != (c->row_stride > 1 ? c->row_stride : 1))
         return fail(c, RT_ERR_INVALID_ARGUMENT, "shards %d is not the context's row stride %d", shards,
                     c->row_stride > 1 ? c->row_stride : 1);
-    if (rows_per_shard < 1 || (long long)rows_per_shard * shards < c->height)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "bad gather geometry: %d shards of %d rows for height %d", shards,
-                    rows_per_shard, c->height);
-    if ((long long)rows_per_shard * c->width > (1ll << 31))
-        return fail(c, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 words");
-    return RT_OK;
+    if (const int rc = block_cover_check(c, "gather", shards, rows_per_shard)) return rc;
+    return block_plane_check(c, rows_per_shard);
 }
 
 // Phase 2 of a checked call on the host forms' path: `gathered` is host memory
@@ -381,11 +374,10 @@ int rt_render_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounc
 
 int rt_render_adaptive_device(rt_context* c, const rt_adaptive_params* p, int max_bounces, void* rgba_device,
                               void* stream) {
-    if (c && c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_render_adaptive_device: CPU context");
+    if (const int rc = device_ctx(c, "rt_render_adaptive_device")) return rc;
     if (const int rc = params_check(c, p, max_bounces)) return rc;
-    if (rgba_device && ((uintptr_t)rgba_device & 3u))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba_device not 4-byte aligned");
-    return gpu_adaptive(c, p, max_bounces, (unsigned*)rgba_device, nullptr, stream ? (hipStream_t)stream : c->stream, {});
+    if (const int rc = device_aligned(c, {{rgba_device, "rgba_device", false}})) return rc;
+    return gpu_adaptive(c, p, max_bounces, (unsigned*)rgba_device, nullptr, device_stream(c, stream), {});
 }
 
 int rt_adaptive_last_stats(rt_context* c, rt_adaptive_stats* stats_out) { return read_stats(c, stats_out); }
@@ -432,11 +424,12 @@ int rt_adaptive_export_rows(rt_context* c, const rt_adaptive_params* p, int rows
 
 int rt_adaptive_export_rows_device(rt_context* c, const rt_adaptive_params* p, int rows_per_shard, void* block_device,
                                    void* stream) {
-    if (!c || !p || !block_device) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_adaptive_export_rows_device: CPU context");
-    if ((uintptr_t)block_device & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "block_device not 4-byte aligned");
+    if (!p) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    hipStream_t s;
+    if (const int rc = device_call(c, "rt_adaptive_export_rows_device", {{block_device, "block_device", true}}, stream, &s))
+        return rc;
     if (const int rc = export_rows_check(c, p, rows_per_shard)) return rc;
-    return export_rows_pass(c, p, rows_per_shard, (float*)block_device, stream ? (hipStream_t)stream : c->stream);
+    return export_rows_pass(c, p, rows_per_shard, (float*)block_device, s);
 }
 
 int rt_render_adaptive_shard(rt_context* c, const rt_adaptive_params* p, int max_bounces, const float* gathered_host,
@@ -451,11 +444,11 @@ int rt_render_adaptive_shard(rt_context* c, const rt_adaptive_params* p, int max
 int rt_render_adaptive_shard_device(rt_context* c, const rt_adaptive_params* p, int max_bounces,
                                     const void* gathered_device, int shards, int rows_per_shard, void* rgba_device,
                                     void* stream) {
-    if (c && c->cpu) return fail(c, RT_ERR_UNSUPPORTED, "rt_render_adaptive_shard_device: CPU context");
+    if (const int rc = device_ctx(c, "rt_render_adaptive_shard_device")) return rc;
     if (const int rc = shard_call_check(c, p, max_bounces, gathered_device, shards, rows_per_shard)) return rc;
-    if (((uintptr_t)gathered_device & 3u) || (rgba_device && ((uintptr_t)rgba_device & 3u)))
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "gathered_device or rgba_device not 4-byte aligned");
-    return gpu_adaptive(c, p, max_bounces, (unsigned*)rgba_device, nullptr, stream ? (hipStream_t)stream : c->stream,
+    const int rc = device_aligned(c, {{gathered_device, "gathered_device", true}, {rgba_device, "rgba_device", false}});
+    if (rc) return rc;
+    return gpu_adaptive(c, p, max_bounces, (unsigned*)rgba_device, nullptr, device_stream(c, stream),
                         {(const float*)gathered_device, shards, rows_per_shard});
 }
 
@@ -465,46 +458,28 @@ int rt_render_adaptive_multi(rt_context* const* ctxs, int n, const rt_adaptive_p
     rt_context* d = ctxs[0];
     if (!p) return fail(d, RT_ERR_INVALID_ARGUMENT, "null argument");
     // every condition first: a refusal touches nothing
-    for (int i = 0; i < n; i++) {
-        if (!ctxs[i]) return fail(d, RT_ERR_INVALID_ARGUMENT, "null context %d", i);
-        if (ctxs[i]->cpu != d->cpu)
-            return fail(d, RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive_multi: GPU and CPU contexts mixed");
-        for (int j = 0; j < i; j++)
-            if (ctxs[j] == ctxs[i]) return fail(d, RT_ERR_INVALID_ARGUMENT, "context listed twice");
-    }
+    if (const int rc = group_scan(ctxs, n, d, "rt_render_adaptive_multi")) return rc;
     const int width = d->width, height = d->height;
     if (width <= 0 || height <= 0)
         return fail(d, RT_ERR_INVALID_ARGUMENT, "no frame shape yet (render or rt_init_rand first)");
-    const int active = n < height ? n : height;  // contexts beyond the image height hold no rows
-    const int rps = (height + n - 1) / n;
+    const int active = group_active(n, height), rps = group_rows_per_shard(n, height);
     std::vector<int> bounces;
     if (!try_resize(bounces, (size_t)active)) return fail(d, RT_ERR_OUT_OF_MEMORY, "host state for %d contexts", n);
     for (int i = 0; i < active; i++) {
         rt_context* c = ctxs[i];
-        if (c->width != width || c->height != height || c->row_offset != i || (c->row_stride > 1 ? c->row_stride : 1) != n ||
-            !c->accum.p)
-            return fail(d, RT_ERR_INVALID_ARGUMENT, "context %d holds %dx%d offset %d stride %d, not shard %d of %d of %dx%d",
-                        i, c->width, c->height, c->row_offset, c->row_stride, i, n, width, height);
-        if (c->st.frame() != d->st.frame() || c->st.batches() != d->st.batches())
-            return fail(d, RT_ERR_INVALID_ARGUMENT, "frame counters or batches differ (context %d: %u, %u; context 0: %u, %u)",
-                        i, c->st.frame(), c->st.batches(), d->st.frame(), d->st.batches());
+        // (a full-frame context's row stride may read 0 or 1)
+        if (const int rc = group_shard_check(d, c, i, n, c->row_stride > 1 ? c->row_stride : 1, width, height)) return rc;
+        if (const int rc = group_counters_check(d, c, i, d, true)) return rc;
         bounces[(size_t)i] = max_bounces;
         if (const int rc = params_check(c, p, bounces[(size_t)i], true)) {
             if (c != d) (void)fail(d, rc, "context %d: %s", i, c->err.c_str());
             return rc;
         }
-        if ((long long)rps * width > (1ll << 31)) return fail(d, RT_ERR_UNSUPPORTED, "block plane larger than 2^31 words");
+        if (const int rc = block_plane_check(d, rps)) return rc;
     }
     const size_t blk = block_words(d, rps);
     const size_t gbytes = (size_t)n * blk * sizeof(float);
-    // a failure at context i leaves work of the contexts before it in flight: drain it
-    auto drain = [&](int launched, int code) {
-        for (int j = 0; j < launched && !d->cpu; j++) {
-            (void)hipSetDevice(ctxs[j]->device);
-            (void)hipStreamSynchronize(ctxs[j]->stream);
-        }
-        return code;
-    };
+    // (from here on a failure at context i leaves work of the contexts before it in flight: group_drain)
     // the gathered blocks: on every GPU context's device; CPU contexts share context 0's
     for (int i = 0; i < (d->cpu ? 1 : active); i++) {
         rt_context* c = ctxs[i];
@@ -516,27 +491,22 @@ int rt_render_adaptive_multi(rt_context* const* ctxs, int n, const rt_adaptive_p
     for (int i = 0; i < active; i++) {
         rt_context* c = ctxs[i];
         float* own = (c->cpu ? d : c)->ad_gather.as<float>() + (size_t)i * blk;
-        if (const int rc = export_rows_pass(c, p, rps, own, c->stream)) return drain(i + 1, rc);
+        if (const int rc = export_rows_pass(c, p, rps, own, c->stream)) return group_drain(ctxs, i + 1, rc);
         for (int j = 0; j < active && !c->cpu; j++) {
             if (j == i) continue;
             rt_context* o = ctxs[j];
             float* dst = o->ad_gather.as<float>() + (size_t)i * blk;
-            const hipError_t e = o->device == c->device
-                                     ? hipMemcpyAsync(dst, own, blk * sizeof(float), hipMemcpyDeviceToDevice, c->stream)
-                                     : hipMemcpyPeerAsync(dst, o->device, own, c->device, blk * sizeof(float), c->stream);
-            if (e != hipSuccess) return drain(i + 1, hip_fail(c, e, "block copy"));
+            const hipError_t e = group_copy(dst, o, own, c, blk * sizeof(float));
+            if (e != hipSuccess) return group_drain(ctxs, i + 1, hip_fail(c, e, "block copy"));
         }
     }
     // every block is in place before a phase 2 is queued (the call synchronises anyway)
-    for (int i = 0; i < active && !d->cpu; i++) {
-        rt_context* c = ctxs[i];
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    if (const int rc = group_sync(ctxs, active)) return rc;
     for (int i = 0; i < active; i++) {
         rt_context* c = ctxs[i];
         const float* g = (c->cpu ? d : c)->ad_gather.as<float>();
-        if (const int rc = shard_call_host(c, p, bounces[(size_t)i], g, n, rps, nullptr, nullptr, false)) return drain(i + 1, rc);
+        if (const int rc = shard_call_host(c, p, bounces[(size_t)i], g, n, rps, nullptr, nullptr, false))
+            return group_drain(ctxs, i + 1, rc);
         if (!rgba_out) continue;
         // the shard's rows to their image rows: row j of context i is row i + j * n
         uint8_t* dst = rgba_out + (size_t)i * width * 4;
@@ -546,19 +516,15 @@ int rt_render_adaptive_multi(rt_context* const* ctxs, int n, const rt_adaptive_p
         } else {
             const hipError_t e = hipMemcpy2DAsync(dst, (size_t)n * width * 4, c->rgba.p, (size_t)width * 4, (size_t)width * 4,
                                                   (size_t)c->rows, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) return drain(i + 1, hip_fail(c, e, "hipMemcpy2DAsync"));
+            if (e != hipSuccess) return group_drain(ctxs, i + 1, hip_fail(c, e, "hipMemcpy2DAsync"));
         }
     }
     rt_adaptive_stats sum = {0, 0, -1.0f, -1.0f, -1.0f};
-    for (int i = 0; i < active; i++) {
+    if (const int rc = group_sync(ctxs, active)) return rc;
+    for (int i = 0; i < active && stats_out; i++) {
         rt_context* c = ctxs[i];
-        if (!c->cpu) {
-            HIP_TRY(c, hipSetDevice(c->device));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
-        if (!stats_out) continue;
         rt_adaptive_stats st;
-        if (const int rc = read_stats(c, &st)) return drain(active, rc);
+        if (const int rc = read_stats(c, &st)) return group_drain(ctxs, active, rc);
         sum.selected += st.selected;
         sum.frames_total += st.frames_total;
         sum.select_ms = st.select_ms > sum.select_ms ? st.select_ms : sum.select_ms;

@@ -143,3 +143,103 @@ def shard_state(r, rows, w):
     rng, acc = r.get_state(rows, w)
     var = r.variance(rows, w, want_lum=True) if r.moments_batches >= 2 else ()
     return bits((rng, acc, r.counts(rows, w)) + tuple(var)), r.frame_counter, r.moments_batches
+
+
+# ---- the four plane counts are one layout ---------------------------------------------
+# (width, height, shards): the 4-byte form; the 16-byte form; contexts beyond the height
+LAYOUT_SHAPES = [(67, 45, 3), (64, 36, 8), (5, 3, 8)]
+LAYOUT_CALLS = (2, 2, 2, 2)  # 4 x 2 tracked frames: n = 8, J = 4
+
+
+def _words(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _layout_blocks(rs, w, h, rps, plane_counts):
+    """planes -> (gathered, frames, batches) of the contexts' blocks with one
+    padding row at least; the blocks of contexts without rows are zero."""
+    out = {}
+    for planes in plane_counts:
+        g = np.zeros((len(rs), planes, rps, w), np.float32)
+        base = set()
+        for i, r in enumerate(rs[:h]):
+            export = r.export_shard_adaptive if planes in (4, 7) else r.export_shard
+            g[i], n, j = export(rps, w, planes)
+            base.add((n, j))
+            assert not _words(g[i, :, rows_of(h, len(rs), i):]).any(), (planes, i)  # padding rows are zero
+        assert len(base) == 1, base
+        out[planes] = (g, *base.pop())
+    return out
+
+
+def _layout_assembled(r, blocks, w, h):
+    """planes -> what rs[0] holds after assembling that block: sum, and mom / (n, j) where the block has them"""
+    got = {}
+    for planes, (g, n, j) in blocks.items():
+        (r.assemble_adaptive if planes in (4, 7) else r.assemble)(g, n, j)
+        moments = planes in (5, 7)
+        frame = r.get_assembled(w, h, want_moments=moments)
+        got[planes] = {"sum": frame[0] if moments else frame}
+        if moments:
+            got[planes]["mom"] = frame[1]
+        if planes in (4, 7):
+            got[planes]["n"], got[planes]["j"] = r.assembled_counts(w, h)
+    return got
+
+
+def one_layout(lib, w, h, shards, gpu=False):
+    """The blocks of 3, 5, 4 and 7 planes of one set of shard contexts agree
+    word for word where they hold the same planes, and so do their assembled
+    frames: in the uniform state for all four, after one adaptive call for 4
+    and 7 (3 and 5 refuse).  Returns {(state, planes): gathered blocks}."""
+    from bwrt import abi
+    rs = []
+    for i in range(shards):
+        r = A.new(lib, gpu)
+        r.set_scene(M.scene_of("07"))
+        r.set_moments(True)
+        if i < h:
+            A.accumulate(r, w, h, i, shards, calls=LAYOUT_CALLS)
+        rs.append(r)
+    rps = -(-h // shards) + 1
+    n, J = sum(LAYOUT_CALLS), len(LAYOUT_CALLS)
+    kept = {}
+    try:
+        # uniform, current moments: all four
+        blocks = _layout_blocks(rs, w, h, rps, (3, 5, 4, 7))
+        u = {p: _words(b[0]) for p, b in blocks.items()}
+        assert [(b[1], b[2]) for b in blocks.values()] == [(n, J)] * 4
+        for p in (5, 4, 7):
+            assert np.array_equal(u[p][:, :3], u[3]), p
+        assert np.array_equal(u[5][:, 3:5], u[7][:, 3:5])
+        assert np.array_equal(u[4][:, 3], u[7][:, 5])
+        for i in range(min(shards, h)):
+            rows = rows_of(h, shards, i)
+            assert (u[4][i, 3, :rows] == n).all() and (u[7][i, 6, :rows] == J).all(), i
+        got = _layout_assembled(rs[0], blocks, w, h)
+        for p in (5, 4, 7):
+            assert same(got[p]["sum"], got[3]["sum"]), p
+        assert same(got[5]["mom"], got[7]["mom"])
+        assert (got[4]["n"] == n).all() and not got[4]["j"].any()
+        assert (got[7]["n"] == n).all() and (got[7]["j"] == J).all()
+        kept.update({("uniform", p): b[0] for p, b in blocks.items()})
+        # after one adaptive call: 4 and 7 only
+        M.two_phase(rs, w, h, sequence(w, h)[0])
+        scratch = np.empty((5, rps, w), np.float32)
+        for r in rs[:h]:
+            for p in (3, 5):
+                assert r.lib.rt_export_shard(r.ctx, rps, p, scratch.ctypes.data, None, None) == abi.RT_ERR_UNSUPPORTED
+                assert b"non-uniform" in r.lib.rt_last_error(r.ctx)
+        blocks = _layout_blocks(rs, w, h, rps, (4, 7))
+        u = {p: _words(b[0]) for p, b in blocks.items()}
+        assert np.array_equal(u[4][:, :3], u[7][:, :3]) and np.array_equal(u[4][:, 3], u[7][:, 5])
+        got = _layout_assembled(rs[0], blocks, w, h)
+        assert same(got[4]["sum"], got[7]["sum"]) and same(got[4]["n"], got[7]["n"]) and not got[4]["j"].any()
+        for i, r in enumerate(rs[:h]):
+            cn, cj = r.counts(rows_of(h, shards, i), w)
+            assert same(got[7]["n"][i::shards], cn) and same(got[7]["j"][i::shards], cj), i
+        print(f"{w}x{h}, {shards} shards: n_p after the adaptive call {np.unique(got[7]['n'])}")
+        kept.update({("adaptive", p): b[0] for p, b in blocks.items()})
+    finally:
+        M.close(rs)
+    return kept

@@ -453,3 +453,12 @@ def test_thread_count_invariance(bwrt_lib):
         got.append(A.bits((g, rs[0].get_assembled(w, h, want_moments=True), rs[0].assembled_counts(w, h))))
         M.close(rs)
     assert got[0] == got[1]
+
+
+# ---- 8. the four plane counts are one layout -----------------------------------------------------------------
+@pytest.mark.parametrize("w,h,s", K.LAYOUT_SHAPES)
+def test_plane_counts_are_one_layout(bwrt_lib, w, h, s):
+    """Blocks of 3, 5, 4 and 7 planes of the same contexts hold the same words
+    in the planes they share, and assemble to the same frame (K.one_layout)."""
+    blocks = K.one_layout(bwrt_lib, w, h, s)
+    assert set(blocks) == {("uniform", p) for p in (3, 5, 4, 7)} | {("adaptive", p) for p in (4, 7)}

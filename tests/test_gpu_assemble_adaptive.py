@@ -275,3 +275,19 @@ def test_gather_frame_adaptive_over_nccl_one_rank():
                        env=env, cwd=REPO, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert "counted assembled frame equals the accumulation" in r.stdout
+
+
+# ---- 5. the four plane counts are one layout ---------------------------------------------------------------
+@pytest.mark.parametrize("w,h,s", K.LAYOUT_SHAPES)
+def test_gpu_plane_counts_are_one_layout(bwrt_lib, w, h, s):
+    """tests/test_assemble_adaptive.py's check on GPU contexts, and the GPU
+    blocks against the CPU backend's."""
+    gpu = K.one_layout(bwrt_lib, w, h, s, gpu=True)
+    cpu = K.one_layout(bwrt_lib, w, h, s)
+    assert gpu.keys() == cpu.keys() and len(gpu) == 6
+    for (state, planes), g in gpu.items():
+        c = cpu[(state, planes)]
+        if planes in (4, 7):
+            assert blocks_equal(g, c, planes), (state, planes)
+        else:
+            assert K.same_values(g, c), (state, planes)
