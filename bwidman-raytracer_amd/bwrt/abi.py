@@ -180,6 +180,9 @@ def _proto(lib):
         "rt_temporal_device": (C.c_int, [vp, P(TemporalParams), P(DenoiseParams), vp, vp]),
         "rt_temporal_reset": (C.c_int, [vp]),
         "rt_last_temporal_ms": (C.c_float, [vp]),
+        "rt_temporal_var": (C.c_int, [vp, P(TemporalParams), P(DenoiseVarParams), vp, vp, vp, vp]),
+        "rt_temporal_var_device": (C.c_int, [vp, P(TemporalParams), P(DenoiseVarParams), vp, vp]),
+        "rt_last_temporal_var_ms": (C.c_float, [vp]),
         "rt_set_moments": (C.c_int, [vp, C.c_int]),
         "rt_get_moments": (C.c_int, [vp]),
         "rt_moments_batches": (C.c_int, [vp]),

@@ -335,6 +335,44 @@ class Renderer:
     def last_temporal_ms(self) -> float:
         return self.lib.rt_last_temporal_ms(self.ctx)
 
+    # -- temporal reprojection of the luminance moments --------------------------
+    def _dv(self, denoise_var):
+        """None, or a dict of denoise_var_params() fields -> a pointer argument."""
+        return None if denoise_var is None else C.byref(self.denoise_var_params(**denoise_var))
+
+    def temporal_var(self, width, height, denoise_var=None, want_color=False, want_length=False,
+                     want_moments=False, **tp):
+        """rt_temporal_var: rt_temporal that also carries a per-pixel variance
+        estimate across camera moves; `tp` are temporal_params() fields,
+        `denoise_var` (a dict of denoise_var_params() fields, {} = the
+        defaults) runs the variance-guided levels over the result.  Returns the
+        RGBA8 image, with want_color / want_length / want_moments also the
+        linear colour (H, W, 3), the effective sample count (H, W) and {variance
+        of the mean luminance, degrees of freedom} (H, W, 2), in that order."""
+        t = self.temporal_params(**tp)
+        out = np.empty((height, width, 4), np.uint8)
+        col = np.empty((height, width, 3), np.float32) if want_color else None
+        ln = np.empty((height, width), np.float32) if want_length else None
+        mom = np.empty((height, width, 2), np.float32) if want_moments else None
+        self._check(self.lib.rt_temporal_var(self.ctx, C.byref(t), self._dv(denoise_var), out.ctypes.data,
+                                             col.ctypes.data if col is not None else None,
+                                             ln.ctypes.data if ln is not None else None,
+                                             mom.ctypes.data if mom is not None else None))
+        res = ((out,) + ((col,) if want_color else ()) + ((ln,) if want_length else ())
+               + ((mom,) if want_moments else ()))
+        return res if len(res) > 1 else out
+
+    def temporal_var_device(self, rgba_ptr: int, stream_ptr: int | None = None, denoise_var=None, **tp):
+        """rt_temporal_var_device: the reprojected (and, with `denoise_var`,
+        filtered) RGBA8 into device memory on a stream (asynchronous; ordered as
+        temporal_device)."""
+        t = self.temporal_params(**tp)
+        self._check(self.lib.rt_temporal_var_device(self.ctx, C.byref(t), self._dv(denoise_var), rgba_ptr,
+                                                    stream_ptr))
+
+    def last_temporal_var_ms(self) -> float:
+        return self.lib.rt_last_temporal_var_ms(self.ctx)
+
     # -- luminance moment tracking ---------------------------------------------
     def set_moments(self, enable: bool = True):
         """rt_set_moments: track per-pixel luminance moments behind every render

@@ -65,7 +65,7 @@ int hip_fail(rt_context* c, hipError_t e, const char* what) {
 int quiesce(rt_context* c) {
     if (c->cpu) return RT_OK;
     HIP_TRY(c, c->render.flush());
-    for (Pass* p : {&c->denoise, &c->temporal, &c->denoise_var, &c->xport, &c->assemble, &c->render})
+    for (Pass* p : {&c->denoise, &c->temporal, &c->denoise_var, &c->temporal_var, &c->xport, &c->assemble, &c->render})
         HIP_TRY(c, p->sync());
     return RT_OK;
 }
@@ -87,7 +87,7 @@ int read_settled(rt_context* c, std::initializer_list<HostCopy> copies) {
 // full-frame passes read: work of any of them on stream s waits for the last
 // of each that ran on another stream (no host sync)
 int order_after_all(rt_context* c, hipStream_t s) {
-    for (Pass* p : {&c->render, &c->denoise, &c->temporal, &c->denoise_var, &c->xport, &c->assemble})
+    for (Pass* p : {&c->render, &c->denoise, &c->temporal, &c->denoise_var, &c->temporal_var, &c->xport, &c->assemble})
         HIP_TRY(c, p->wait_on(s));
     return RT_OK;
 }
@@ -212,7 +212,7 @@ int rt_create_cpu(int threads, rt_context** out) {
     if (!rt_cpu_supported()) return RT_ERR_UNSUPPORTED;
     rt_context* c = new rt_context();
     c->cpu = true;
-    c->render.host = c->denoise.host = c->temporal.host = c->denoise_var.host = true;
+    c->render.host = c->denoise.host = c->temporal.host = c->denoise_var.host = c->temporal_var.host = true;
     c->xport.host = c->assemble.host = true;
     c->device = -1;
     c->threads = threads > 0 ? threads : rt_cpu_threads();
@@ -248,7 +248,7 @@ void rt_destroy(rt_context* c) {
         (void)hipSetDevice(c->device);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
         c->render.pending = false;  // its launch is done: the stream is synchronised
-        for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var, &c->xport, &c->assemble}) {
+        for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var, &c->temporal_var, &c->xport, &c->assemble}) {
             (void)p->sync();
             p->destroy();
         }
@@ -509,7 +509,7 @@ int rt_synchronize(rt_context* c) {
     // marks the last render (later renders on a caller's stream wait on it)
     HIP_TRY(c, c->render.flush());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var, &c->xport, &c->assemble})
+    for (Pass* p : {&c->render, &c->aux, &c->denoise, &c->temporal, &c->denoise_var, &c->temporal_var, &c->xport, &c->assemble})
         HIP_TRY(c, p->sync());
     return RT_OK;
 }

@@ -17,7 +17,7 @@
 // The post-render passes' kernels and arithmetic: rt_atrous.h (what the filters
 // and the reprojection share, host and device), rt_atrous_tile.h (the pixel and
 // the LDS-tiled kernel with their launchers, device only), then one header and
-// one unit each: rt_denoise, rt_denoise_var, rt_temporal, rt_moments; rt_assemble
+// one unit each: rt_denoise, rt_denoise_var, rt_temporal, rt_temporal_var, rt_moments; rt_assemble
 // (the two copies behind rt_export_shard* and rt_assemble*, counted or not).
 #pragma once
 
@@ -57,6 +57,8 @@ bool rt_cpu_supported();
 void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb);
 void rt_cpu_denoise_level(const rt_dn_level& L, int threads);
 void rt_cpu_temporal(const rt_tp_args& T, int threads);
+void rt_cpu_temporal_var(const rt_tv_args& V, int threads);
+void rt_cpu_temporal_var_input(const rt_tv_input& A, int threads);
 void rt_cpu_moments(const rt_mom_args& A, int threads);
 void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads);
 void rt_cpu_export_shard(const rt_asm_args& A, int threads);
@@ -65,6 +67,9 @@ void rt_cpu_assemble(const rt_asm_args& A, int threads);
 hipError_t rt_launch_denoise_level(const rt_dn_level& L, bool tiled, hipStream_t stream);
 // temporal reprojection (rt_temporal.hip)
 hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream);
+// moment-carrying reprojection and the input stage of the levels behind it (rt_temporal_var.hip)
+hipError_t rt_launch_temporal_var(const rt_tv_args& V, hipStream_t stream);
+hipError_t rt_launch_temporal_var_input(const rt_tv_input& A, hipStream_t stream);
 // luminance moment update (rt_moments.hip)
 hipError_t rt_launch_moments(const rt_mom_args& A, hipStream_t stream);
 // variance-guided filter (rt_denoise_var.hip): stage 0 input, 1 sigma pass, 2 level
@@ -201,12 +206,14 @@ struct rt_context {
     // colour buffers.  temporal: the reprojection pass, likewise; its events
     // are created by the first temporal call.  denoise_var: the
     // variance-guided filter, which shares the guides and colour buffers with
-    // the denoiser; its events are created by its first call.  xport: the
+    // the denoiser; its events are created by its first call.
+    // temporal_var: the moment-carrying reprojection pass (rt_temporal_var),
+    // which shares the history sets with `temporal`; likewise.  xport: the
     // last rt_export_shard, which reads frameSum and the moments (the next
     // render waits for it).  assemble: the last rt_assemble, which writes the
     // assembled frame the three full-frame passes read.  Both create their
     // events on first use.
-    Pass render, aux, denoise, temporal, denoise_var, xport, assemble;
+    Pass render, aux, denoise, temporal, denoise_var, temporal_var, xport, assemble;
     // CPU backend (rt_create_cpu): host buffers, and the scalar fallback of
     // rt_cpu.cpp instead of the kernels
     bool cpu = false;
@@ -274,9 +281,13 @@ struct rt_context {
     // guide copy, camera}: tp[tp_hist] is the history, tp[tp_hist ^ 1] the
     // pending result of view tp_pending_view; the first call in a later view
     // swaps them (tp_hist ^= 1).  Nothing is allocated (events included)
-    // before the first call.
+    // before the first call.  rt_temporal_var shares the sets, the view
+    // counting and the promotion: a set it wrote also holds {s2, dof} per pixel
+    // in `mom` (has_mom; a set rt_temporal wrote has none).  The two planes are
+    // allocated by the first rt_temporal_var call only.
     struct TpSet {
-        Buf col, ga, gb;
+        Buf col, ga, gb, mom;
+        bool has_mom = false;
         float cam_pos[3] = {}, rot[9] = {}, screen_z = 0.0f;
     };
     unsigned long long view = 1;

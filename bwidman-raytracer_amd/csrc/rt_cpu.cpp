@@ -232,6 +232,7 @@ int rt_cpu_render(const rt_kparams& K, int threads) {
 #include "rt_denoise_var.h"
 #include "rt_moments.h"
 #include "rt_temporal.h"
+#include "rt_temporal_var.h"
 
 namespace {
 
@@ -323,6 +324,15 @@ void rt_cpu_temporal(const rt_tp_args& T, int threads) {
         else
             tp_run_pixel(T, x, y);
     });
+}
+
+// The moment-carrying reprojection pass and the input stage of the levels
+// behind it (rt_temporal_var.h), on the same pool
+void rt_cpu_temporal_var(const rt_tv_args& V, int threads) {
+    parallel_pixels(V.t.width, V.t.height, threads, [&](int x, int y, long) { tv_run_pixel(V, x, y); });
+}
+void rt_cpu_temporal_var_input(const rt_tv_input& A, int threads) {
+    parallel_pixels(A.f.width, A.f.height, threads, [&](int x, int y, long p) { at_store(A.f, p, tv_input(A, x, y)); });
 }
 
 // The luminance moment update of one render call (rt_moments.h), on the same pool

@@ -313,6 +313,27 @@ struct rt_dv_args : rt_dv_uniform {
     const uint2* cnt;
 };
 
+// One reprojection pass that carries the luminance moments (rt_temporal_var.h):
+// rt_temporal's pass over a uniform accumulation, and one {s2, dof} plane beside
+// each colour + length plane.
+struct rt_tv_args {
+    rt_tp_uniform t;
+    int tracked;         // the frame's tracked moments are current with J >= 2 batches: mom is read
+    float dof_c;         // tracked: (float)(J - 1), else 0
+    const float2* mom;   // tracked: {M, M2} of the current frame
+    const float2* h_mom; // history {s2, dof}; null: the set was written by rt_temporal and has none
+    float2* p_mom;       // pending {s2_out, dof_out}
+};
+
+// The input stage of the variance-guided levels behind that pass: f.dst takes
+// {out.xyz, v0} (f.ga, f.gb, f.in, f.ip: the spatial estimate's window)
+struct rt_tv_input {
+    rt_at_frame f;
+    float dof_min;       // (float)min_batches - 1.5f: at or above it v0 = s2 / len, below the spatial estimate
+    const float4* col;   // pending {out.rgb, len_out}
+    const float2* mom;   // pending {s2_out, dof_out}
+};
+
 // The list of an adaptive render (rt_adaptive.h): what the list render kernels
 // (rt_kernel_list.h) take besides rt_kparams, whose layout they leave alone.
 struct rt_list_args {

@@ -1,5 +1,6 @@
 // rt_post.cpp — what the C ABI (include/rt_abi.h) offers after a render:
-// first-hit feature buffers, the a-trous denoiser and temporal reprojection.
+// first-hit feature buffers, the a-trous denoisers and temporal reprojection
+// (with and without the luminance moments).
 //
 // None of them reads or writes the RNG state or the frame counter or writes
 // frameSum; all always run the exact arithmetic (rt_set_precision selects
@@ -10,6 +11,7 @@
 
 #include "rt_adaptive.h"
 #include "rt_group.h"
+#include "rt_temporal_var.h"
 
 namespace {
 
@@ -211,6 +213,8 @@ bool level_tiled(const rt_context* c, int step) { return c->dn_kernel >= 0 ? c->
 struct Result {
     const Buf* color = nullptr;
     const Buf* length = nullptr;
+    const Buf* moments = nullptr;  // rt_temporal_var: the pending {s2, dof}
+    bool filtered = false;         // rt_temporal_var: color's .w is the levels' final variance
 };
 
 // Every level of one denoise call on stream s; the final colour ends in
@@ -249,16 +253,32 @@ int denoise_levels(rt_context* c, const rt_denoise_params* dp, hipStream_t s, un
     return RT_OK;
 }
 
+// The parameter rules of the variance-guided filter
+int denoise_var_check(rt_context* c, const rt_denoise_var_params* dp) {
+    const int rc = filter_check(c, dp->iterations, "luminance", dp->sigma_lum, dp->sigma_normal, dp->sigma_plane);
+    if (rc) return rc;
+    if (dp->min_batches < 2) return fail(c, RT_ERR_INVALID_ARGUMENT, "min_batches %d < 2", dp->min_batches);
+    return RT_OK;
+}
+
+// The pending state of an rt_temporal_var call, for the levels that run behind it
+struct TvPending {
+    const float4* col;  // {out.rgb, len_out}
+    const float2* mom;  // {s2_out, dof_out}
+};
+
 // The variance-guided filter (rt_denoise_var.h) of one call on stream s: the
 // input stage, then per level a sigma pass and the level.  The final {colour,
 // variance} ends in out.color = out.length and, tone-mapped, in rgba (device
-// pointer on a GPU context; may be null).
-int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream_t s, unsigned* rgba, Result& out) {
+// pointer on a GPU context; may be null).  tv non-null (rt_temporal_var on a
+// uniform frame; iterations >= 1): the input stage is rt_temporal_var.h's over
+// that pending state instead of frameSum and the tracked moments.
+int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream_t s, unsigned* rgba, Result& out,
+                       const TvPending* tv = nullptr) {
     const HostFpEnv fp;
     if (!c || !dp) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = filter_check(c, dp->iterations, "luminance", dp->sigma_lum, dp->sigma_normal, dp->sigma_plane);
+    int rc = denoise_var_check(c, dp);
     if (rc) return rc;
-    if (dp->min_batches < 2) return fail(c, RT_ERR_INVALID_ARGUMENT, "min_batches %d < 2", dp->min_batches);
     rc = prepare_frame(c, "the denoiser", c->denoise_var, s,
                        {colour_buf(c->dn_col[0]), colour_buf(c->dn_col[1]),
                         {&c->dn_rs, sizeof(float), "host sigma plane for %zu pixels"}});
@@ -299,14 +319,28 @@ int denoise_var_passes(rt_context* c, const rt_denoise_var_params* dp, hipStream
     };
     HIP_TRY(c, c->denoise_var.begin(s, true));
     A.f.dst = col[0];
-    if ((rc = pass(0, -1))) return rc;
+    if (tv) {
+        rt_tv_input I;
+        std::memset(&I, 0, sizeof I);
+        I.f = A.f;  // (last = 0: a level follows)
+        I.dof_min = (float)dp->min_batches - 1.5f;
+        I.col = tv->col;
+        I.mom = tv->mom;
+        if (c->cpu)
+            rt_cpu_temporal_var_input(I, c->threads);
+        else
+            HIP_TRY(c, rt_launch_temporal_var_input(I, s));
+    } else if ((rc = pass(0, -1))) {
+        return rc;
+    }
     for (int i = 0; i < levels; i++) {
         A.f.step = 1 << i;
         A.f.src = col[i & 1];
         A.f.dst = col[(i + 1) & 1];
         if ((rc = pass(1, i)) || (rc = pass(2, i))) return rc;
     }
-    out.color = out.length = &c->dn_col[levels & 1];
+    out.color = &c->dn_col[levels & 1];
+    if (!tv) out.length = out.color;
     HIP_TRY(c, c->denoise_var.end(s));
     return RT_OK;
 }
@@ -321,22 +355,11 @@ int temporal_check(rt_context* c, const rt_temporal_params* tp, const rt_denoise
     return dn ? denoise_check(c, dn) : RT_OK;
 }
 
-// One temporal call on stream s: promote, reproject, store the pending result
-// of the current view {colour, history length} in out.length; with a filter
-// (dn, iterations >= 1) its levels follow and out.color is their final colour,
-// else the pending one.  rgba: device pointer on a GPU context; may be null.
-int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn, hipStream_t s,
-                  unsigned* rgba, Result& out) {
-    const HostFpEnv fp;
-    int rc = temporal_check(c, tp, dn);
-    if (!rc) {
-        auto hist = [](Buf& b) { return Need{&b, sizeof(float4), "host history buffers for %zu pixels"}; };
-        rt_context::TpSet *t0 = &c->tp[0], *t1 = &c->tp[1];
-        rc = prepare_frame(c, "reprojection", c->temporal, s,
-                           {hist(t0->col), hist(t0->ga), hist(t0->gb), hist(t1->col), hist(t1->ga), hist(t1->gb)});
-    }
-    if (rc) return rc;
-    const bool filter = dn && dn->iterations > 0;
+// The history sets at the start of one rt_temporal or rt_temporal_var call (the
+// two share them): a shape change drops them, the first call of a later view
+// promotes the pending result.  Fills the pass T (zeroed by the caller; all but
+// rgba) and the current view K; returns the set the call writes.
+rt_context::TpSet& temporal_sets(rt_context* c, const rt_temporal_params* tp, rt_tp_uniform& T, rt_kparams& K) {
     if (c->tp_w != c->width || c->tp_h != c->height) {  // (rt_init_rand dropped them already)
         c->tp_has_hist = c->tp_has_pending = false;
         c->tp_w = c->width;
@@ -352,10 +375,7 @@ int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_
     }
     const rt_context::TpSet& H = c->tp[c->tp_hist];
     rt_context::TpSet& P = c->tp[c->tp_hist ^ 1];
-    rt_kparams K;
     fill_view(c, c->width, c->height, 0, 1, c->height, K);
-    rt_tp_args T;
-    std::memset(&T, 0, sizeof T);
     T.width = c->width;
     T.height = c->height;
     T.has_history = c->tp_has_hist ? 1 : 0;
@@ -377,6 +397,39 @@ int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_
     T.p_col = P.col.as<float4>();
     T.p_ga = P.ga.as<float4>();
     T.p_gb = P.gb.as<float4>();
+    return P;
+}
+
+// The pending set P now holds the result of the current view K
+void temporal_stored(rt_context* c, rt_context::TpSet& P, const rt_kparams& K, bool has_mom) {
+    std::memcpy(P.cam_pos, K.cam_pos, sizeof P.cam_pos);
+    std::memcpy(P.rot, K.rot, sizeof P.rot);
+    P.screen_z = K.screen_z;
+    P.has_mom = has_mom;
+    c->tp_has_pending = true;
+    c->tp_pending_view = c->view;
+}
+
+// One temporal call on stream s: promote, reproject, store the pending result
+// of the current view {colour, history length} in out.length; with a filter
+// (dn, iterations >= 1) its levels follow and out.color is their final colour,
+// else the pending one.  rgba: device pointer on a GPU context; may be null.
+int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_params* dn, hipStream_t s,
+                  unsigned* rgba, Result& out) {
+    const HostFpEnv fp;
+    int rc = temporal_check(c, tp, dn);
+    if (!rc) {
+        auto hist = [](Buf& b) { return Need{&b, sizeof(float4), "host history buffers for %zu pixels"}; };
+        rt_context::TpSet *t0 = &c->tp[0], *t1 = &c->tp[1];
+        rc = prepare_frame(c, "reprojection", c->temporal, s,
+                           {hist(t0->col), hist(t0->ga), hist(t0->gb), hist(t1->col), hist(t1->ga), hist(t1->gb)});
+    }
+    if (rc) return rc;
+    const bool filter = dn && dn->iterations > 0;
+    rt_tp_args T;
+    std::memset(&T, 0, sizeof T);
+    rt_kparams K;
+    rt_context::TpSet& P = temporal_sets(c, tp, T, K);
     T.rgba = filter ? nullptr : rgba;  // the filter's last level writes it otherwise
     T.cnt = frame_counts(c);           // non-uniform: they replace n and inv
     HIP_TRY(c, c->temporal.begin(s, true));
@@ -385,20 +438,72 @@ int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_
     else
         HIP_TRY(c, rt_launch_temporal(T, s));
     HIP_TRY(c, c->temporal.end(s));
-    std::memcpy(P.cam_pos, K.cam_pos, sizeof P.cam_pos);
-    std::memcpy(P.rot, K.rot, sizeof P.rot);
-    P.screen_z = K.screen_z;
-    c->tp_has_pending = true;
-    c->tp_pending_view = c->view;
+    temporal_stored(c, P, K, false);
     out.color = out.length = &P.col;
     return filter ? denoise_levels(c, dn, s, rgba, out, T.p_col) : RT_OK;
+}
+
+// One rt_temporal_var call on stream s (rt_temporal_var.h): rt_temporal's pass
+// on the shared history sets with the {s2, dof} plane beside the colour, then,
+// with a filter (dv, iterations >= 1), the variance-guided levels behind the
+// call's own input stage.  out.length and out.moments are the pending planes,
+// out.color the levels' final {colour, variance} or the pending colour.
+int temporal_var_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_var_params* dv, hipStream_t s,
+                      unsigned* rgba, Result& out) {
+    const HostFpEnv fp;
+    int rc = temporal_check(c, tp, nullptr);
+    if (!rc && dv) rc = denoise_var_check(c, dv);
+    if (!rc) rc = full_frame_check(c, "moment reprojection");
+    // (before anything is allocated or promoted: per-pixel counts in the merge are not defined yet)
+    if (!rc && frame_counts(c))
+        return fail(c, RT_ERR_UNSUPPORTED,
+                    "the frame is non-uniform (rt_render_adaptive, rt_assemble_adaptive): rt_temporal_var takes one "
+                    "frame count for all pixels, with or without rt_set_adaptive_filters");
+    if (!rc) {
+        auto hist = [](Buf& b, size_t elem) { return Need{&b, elem, "host history buffers for %zu pixels"}; };
+        rt_context::TpSet *t0 = &c->tp[0], *t1 = &c->tp[1];
+        const size_t e = sizeof(float4);
+        rc = prepare_frame(c, "moment reprojection", c->temporal_var, s,
+                           {hist(t0->col, e), hist(t0->ga, e), hist(t0->gb, e), hist(t0->mom, sizeof(float2)),
+                            hist(t1->col, e), hist(t1->ga, e), hist(t1->gb, e), hist(t1->mom, sizeof(float2))});
+    }
+    if (rc) return rc;
+    const bool filter = dv && dv->iterations > 0;
+    rt_tv_args V;
+    std::memset(&V, 0, sizeof V);
+    rt_kparams K;
+    rt_context::TpSet& P = temporal_sets(c, tp, V.t, K);
+    const rt_context::TpSet& H = c->tp[c->tp_hist];
+    V.t.rgba = filter ? nullptr : rgba;  // the filter's last level writes it otherwise
+    const FrameSrc src = frame_src(c);
+    V.tracked = src.tracked && src.batches >= 2u;
+    if (V.tracked) {
+        V.dof_c = (float)(src.batches - 1u);
+        V.mom = src.mom;
+    }
+    V.h_mom = H.has_mom ? H.mom.as<float2>() : nullptr;
+    V.p_mom = P.mom.as<float2>();
+    HIP_TRY(c, c->temporal_var.begin(s, true));
+    if (c->cpu)
+        rt_cpu_temporal_var(V, c->threads);
+    else
+        HIP_TRY(c, rt_launch_temporal_var(V, s));
+    HIP_TRY(c, c->temporal_var.end(s));
+    temporal_stored(c, P, K, true);
+    out.color = out.length = &P.col;
+    out.moments = &P.mom;
+    out.filtered = filter;
+    if (!filter) return RT_OK;
+    const TvPending pend{V.t.p_col, V.p_mom};
+    return denoise_var_passes(c, dv, s, rgba, out, &pend);
 }
 
 // A host entry point: run(stream, rgba, out) is the pass, on the context's
 // stream, with dn_rgba for its RGBA when the caller wants the image; then the
 // host copies of what it left in `out`
 template <class Run>
-int host_call(rt_context* c, uint8_t* rgba_out, float* color_out, float* length_out, const Run& run) {
+int host_call(rt_context* c, uint8_t* rgba_out, float* color_out, float* length_out, const Run& run,
+              Result* kept = nullptr) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     const size_t npix = (size_t)c->height * c->width;
     if (rgba_out) {
@@ -407,6 +512,7 @@ int host_call(rt_context* c, uint8_t* rgba_out, float* color_out, float* length_
     }
     Result out;
     if (const int rc = run(c->stream, rgba_out ? c->dn_rgba.as<unsigned>() : nullptr, out)) return rc;
+    if (kept) *kept = out;
     return read_back(c, npix, rgba_out, out.color, color_out, out.length, length_out);
 }
 
@@ -547,6 +653,51 @@ int rt_temporal_reset(rt_context* c) {
 }
 
 float rt_last_temporal_ms(rt_context* c) { return c ? c->temporal.elapsed_ms() : -1.0f; }
+
+// ---- temporal reprojection of the luminance moments ----------------------------
+// (csrc/rt_temporal_var.h has the arithmetic)
+
+int rt_temporal_var(rt_context* c, const rt_temporal_params* tp, const rt_denoise_var_params* dv, uint8_t* rgba_out,
+                    float* color_out, float* length_out, float* moments_out) {
+    Result res;
+    int rc = host_call(c, rgba_out, color_out, length_out, [&](hipStream_t s, unsigned* rgba, Result& out) {
+        return temporal_var_pass(c, tp, dv, s, rgba, out);
+    }, &res);
+    if (rc || !moments_out) return rc;
+    // {variance of the mean, dof}: the pending planes, and behind a filter its final .w
+    const HostFpEnv fp;
+    const size_t npix = (size_t)c->height * c->width;
+    const float2* mom = res.moments->as<float2>();
+    const float4* len = res.length->as<float4>();
+    const float4* var = res.filtered ? res.color->as<float4>() : nullptr;
+    std::vector<float2> hm;
+    std::vector<float4> hv;
+    if (!c->cpu) {  // (read_back has synchronised the stream: the buffers are settled)
+        if (!try_resize(hm, npix) || !try_resize(hv, npix))
+            return fail(c, RT_ERR_OUT_OF_MEMORY, "host moments for %zu pixels", npix);
+        HIP_TRY(c, hipMemcpyAsync(hm.data(), mom, npix * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(hv.data(), var ? var : len, npix * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        mom = hm.data();
+        len = hv.data();
+        if (var) var = hv.data();
+    }
+    for (size_t i = 0; i < npix; i++) {
+        moments_out[2 * i] = var ? var[i].w : tv_var_of_mean(mom[i], len[i].w);
+        moments_out[2 * i + 1] = mom[i].y;
+    }
+    return RT_OK;
+}
+
+int rt_temporal_var_device(rt_context* c, const rt_temporal_params* tp, const rt_denoise_var_params* dv,
+                           void* rgba_device, void* stream) {
+    hipStream_t s;
+    Result out;
+    const int rc = device_call(c, "rt_temporal_var_device", {{rgba_device, "rgba_device", false}}, stream, &s);
+    return rc ? rc : temporal_var_pass(c, tp, dv, s, (unsigned*)rgba_device, out);
+}
+
+float rt_last_temporal_var_ms(rt_context* c) { return c ? c->temporal_var.elapsed_ms() : -1.0f; }
 
 // ---- luminance moment tracking ------------------------------------------------
 // (csrc/rt_moments.h has the update, rt_render.cpp runs

@@ -13,6 +13,7 @@
 //               [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]
 //               [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]
 //               [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]
+//               [--temporal-var [N]]
 //               [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]
 //               [--adaptive TOL] [--adaptive-after 4] [--adaptive-radius R] [--adaptive-floor F]
 //               [--min-frames N] [--max-frames N]
@@ -42,6 +43,15 @@
 // replace the fields of rt_temporal_params_default()).  The file from --out is
 // then the temporal frame of the last render call, filtered when --denoise is
 // also given.
+// --temporal-var [N] calls rt_temporal_var where --temporal calls rt_temporal:
+// the reprojection also carries a per-pixel variance estimate across the camera
+// moves (--max-history, --normal-cos and --plane-tol as above), and the call
+// after the last render runs N variance-guided levels behind it (--sigma-lum,
+// --min-batches, --sigma-normal, --sigma-plane; no N: unfiltered).  It prints
+// the mean standard error over the pixels with degrees of freedom, and with
+// --aov PREFIX writes PREFIX_tvar in PREFIX_var's encoding.  It cannot be
+// combined with --temporal, --denoise, --denoise-var, --adaptive or --gpus
+// above 1.
 // --aov PREFIX writes the first-hit feature buffers (rt_render_aov) as
 // PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5) and PREFIX_depth (1 / (1 +
 // depth), a miss black) images in --out's format (PNG without --out).
@@ -93,6 +103,7 @@ static const char* kUsage =
     "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n"
     "                   [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]\n"
     "                   [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]\n"
+    "                   [--temporal-var [N]]\n"
     "                   [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]\n"
     "                   [--adaptive TOL] [--adaptive-after 4] [--adaptive-radius R] [--adaptive-floor F]\n"
     "                   [--min-frames N] [--max-frames N] [--adaptive-filters]\n"
@@ -159,7 +170,8 @@ int main(int argc, char** argv) {
     double fixed_dt = -1.0;
     bool denoise = false;
     rt_denoise_params dn = rt_denoise_params_default();
-    bool temporal = false;
+    bool temporal = false, temporal_var = false;
+    int temporal_var_levels = 0;
     rt_temporal_params tp = rt_temporal_params_default();
     std::string aov;
     bool moments = false, moments_readout = false, denoise_var = false;
@@ -219,6 +231,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--sigma-lum")) dv.sigma_lum = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--min-batches")) dv.min_batches = std::atoi(next());
         else if (!std::strcmp(argv[i], "--temporal")) temporal = true;
+        else if (!std::strcmp(argv[i], "--temporal-var")) {
+            temporal_var = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') temporal_var_levels = std::atoi(argv[++i]);
+        }
         else if (!std::strcmp(argv[i], "--max-history")) tp.max_history = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--normal-cos")) tp.normal_cos_min = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--plane-tol")) tp.plane_tol = (float)std::atof(next());
@@ -248,6 +264,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr,
                      "--adaptive cannot be combined with --denoise, --denoise-var, --temporal, --precision fast or "
                      "--gpus above 1: the filters and the fast mode take one frame count for all pixels\n");
+        return 2;
+    }
+    if (temporal_var && (temporal || denoise || denoise_var || adaptive || gpus > 1)) {
+        std::fprintf(stderr,
+                     "--temporal-var cannot be combined with --temporal, --denoise, --denoise-var, --adaptive or --gpus "
+                     "above 1: it is the one pass behind every render call, on one uniform full frame\n");
         return 2;
     }
     if (adaptive && adaptive_after < 2) {
@@ -325,6 +347,7 @@ int main(int argc, char** argv) {
     int calls = 0;  // render calls of the current accumulation
     rt_adaptive_stats ast{};
     bool ast_valid = false;
+    std::vector<float> tvar;  // --temporal-var: {variance of the mean luminance, dof} of the last call
     // several contexts: their row shards into one frame on context 0, which the next filter call reads
     auto assemble = [&](int planes) -> int {
         if (gpus == 1) return RT_OK;
@@ -359,6 +382,29 @@ int main(int argc, char** argv) {
             if (last) {
                 std::printf("temporal: %.3f ms\n", rt_last_temporal_ms(ctx));
                 if (denoise) std::printf("denoise: %d levels, %.3f ms\n", dn.iterations, rt_last_denoise_ms(ctx));
+            }
+        }
+        if (temporal_var) {  // likewise; the levels run behind the last call only
+            const bool last = done == frames || (!steps.empty() && (steps[step].keys & RT_KEY_ESCAPE));
+            rt_denoise_var_params lv = dv;
+            lv.iterations = temporal_var_levels;
+            if (last) tvar.resize((size_t)width * height * 2);
+            rc = rt_temporal_var(ctx, &tp, last ? &lv : nullptr, last ? rgba.data() : nullptr, nullptr, nullptr,
+                                 last ? tvar.data() : nullptr);
+            if (rc) return die(ctx, rc, "rt_temporal_var");
+            if (last) {
+                double se = 0.0;
+                size_t known = 0;
+                for (size_t i = 0; i < tvar.size(); i += 2)
+                    if (tvar[i + 1] > 0.0f) {
+                        se += std::sqrt((double)tvar[i]);
+                        known++;
+                    }
+                std::printf("temporal-var: %.3f ms, mean standard error %.4g over %zu pixels with history or moments\n",
+                            rt_last_temporal_var_ms(ctx), known ? se / (double)known : 0.0, known);
+                if (lv.iterations > 0)
+                    std::printf("denoise-var: %d levels behind the reprojection, %.3f ms\n", lv.iterations,
+                                rt_last_denoise_var_ms(ctx));
             }
         }
         bool quit = false;
@@ -469,6 +515,21 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "cannot write %s\n", name.c_str());
                 return 1;
             }
+        }
+    }
+    if (!aov.empty() && !tvar.empty()) {  // the reprojected standard error, as PREFIX_var
+        const size_t npix = (size_t)width * height;
+        const bool ppm = out.size() > 4 && out.compare(out.size() - 4, 4, ".ppm") == 0;
+        std::vector<uint8_t> img(npix * 4, 255);
+        for (size_t i = 0; i < npix; i++) {
+            const float se = std::sqrt(tvar[2 * i]), v = se / (1.0f + se);
+            const uint8_t b = (uint8_t)(v >= 1.0f ? 255 : v > 0.0f ? (int)(v * 255.0f + 0.5f) : 0);
+            img[4 * i] = img[4 * i + 1] = img[4 * i + 2] = b;
+        }
+        const std::string name = aov + "_tvar" + (ppm ? ".ppm" : ".png");
+        if (!(ppm ? bwrt::write_ppm(name, width, height, img.data()) : bwrt::write_png(name, width, height, img.data()))) {
+            std::fprintf(stderr, "cannot write %s\n", name.c_str());
+            return 1;
         }
     }
     if (!out.empty()) {

@@ -25,7 +25,7 @@
  *  - One context = one GPU (HIP device) and one pixel-row shard.  A context
  *    must be used by one host thread at a time.  All calls except
  *    rt_render_device()/rt_render_adaptive_device()/rt_denoise_device()/
- *    rt_denoise_var_device()/rt_temporal_device()/
+ *    rt_denoise_var_device()/rt_temporal_device()/rt_temporal_var_device()/
  *    rt_deinterleave_rows_device() are synchronous.
  *  - Output RGBA8 buffers are row-major, row 0 = BOTTOM of the screen
  *    (the reference draws texcoord (0,0) at the bottom-left, Main.cu:358).
@@ -198,7 +198,7 @@ RT_API void rt_destroy(rt_context* ctx);
  * rt_get_state / rt_set_state, ...; rt_last_kernel_ms gives the last render's
  * wall time) except rt_render_device, rt_render_adaptive_device, rt_adaptive_export_rows_device,
  * rt_render_adaptive_shard_device, rt_denoise_device, rt_denoise_var_device,
- * rt_temporal_device, rt_render_multi and rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no
+ * rt_temporal_device, rt_temporal_var_device, rt_render_multi and rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no
  * device memory).
  * Replaces the reference's config-1 CPU path and is the CPU baseline of
  * bench.py (SURVEY §8(b) rt_render_cpu, §8(d)). */
@@ -610,6 +610,49 @@ RT_API int rt_denoise_var_device(rt_context* ctx, const rt_denoise_var_params* p
                                  void* stream);
 /* Duration (ms) of all passes of the last rt_denoise_var call; -1 when unavailable. */
 RT_API float rt_last_denoise_var_ms(rt_context* ctx);
+
+/* ---- temporal reprojection of the luminance moments ---------------------------------
+ * rt_temporal that also carries a per-pixel estimate of the luminance variance
+ * across camera moves (SVGF's temporal stage with its variance estimate), so a
+ * host that renders one call per view can still ask how noisy a pixel is, and
+ * the variance-guided levels can run behind the reprojection.  Beside colour
+ * and length every history set holds {s2, dof}: the pooled estimate of the
+ * pixel's PER-FRAME luminance variance and its degrees of freedom; s2 / length
+ * is the variance of the mean luminance.  A call merges the history's estimate,
+ * the current frame's tracked moments when rt_set_moments is on and live with
+ * two batches or more (else nothing: tracking may stay off), and the squared
+ * difference between the history's and the current view's luminance (the
+ * pairwise merge of two Welford accumulators; DESIGN.md section 21 and
+ * csrc/rt_temporal_var.h have the exact definition).  Real signal change
+ * between views counts as noise: the estimate errs towards "noisier".
+ *
+ * Colour, length and RGBA of the unfiltered call are rt_temporal's bit for bit.
+ * The call shares rt_temporal's history sets, view counting, promotion rule
+ * and drops, and the two may follow each other in any order: a set that
+ * rt_temporal wrote has no moments, and its taps count with s2 = dof = 0.  The
+ * moment planes (8 bytes per pixel and set) are allocated by the first
+ * rt_temporal_var call.  Neutrality and arithmetic as rt_temporal; the tracked
+ * moments are only read.
+ *
+ * dv == NULL or dv->iterations == 0: no filter.  Else the levels of
+ * rt_denoise_var run over the reprojected colour; their input variance is
+ * s2 / length where dof >= dv->min_batches - 1.5, else the spatial estimate of
+ * rt_denoise_var over the reprojected colours.  The stored history is always
+ * the unfiltered one.  rgba_out, color_out, length_out as rt_temporal;
+ * moments_out: w*h pairs {variance of the mean luminance, dof} or NULL:
+ * unfiltered s2 / length (0 where dof is 0), filtered the levels' final
+ * variance; dof is the unfiltered one in both.
+ * Errors as rt_temporal and rt_denoise_var, and RT_ERR_UNSUPPORTED for a
+ * non-uniform accumulation or a counted assembled frame, with or without
+ * rt_set_adaptive_filters. */
+RT_API int rt_temporal_var(rt_context* ctx, const rt_temporal_params* params, const rt_denoise_var_params* dv,
+                           uint8_t* rgba_out, float* color_out, float* length_out, float* moments_out);
+/* As above into DEVICE memory, with rt_temporal_device's rules. */
+RT_API int rt_temporal_var_device(rt_context* ctx, const rt_temporal_params* params,
+                                  const rt_denoise_var_params* dv, void* rgba_device, void* stream);
+/* Duration (ms) of the reprojection pass alone of the last rt_temporal_var call
+ * (the levels behind it: rt_last_denoise_var_ms); -1 when unavailable. */
+RT_API float rt_last_temporal_var_ms(rt_context* ctx);
 
 /* ---- variance-driven adaptive sampling ---------------------------------------------
  * The tracked moments say how noisy each pixel still is; rt_render_adaptive()
