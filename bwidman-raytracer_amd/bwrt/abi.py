@@ -103,6 +103,12 @@ class AdaptiveParams(C.Structure):
                 ("min_frames", C.c_uint), ("max_frames", C.c_uint)]
 
 
+class AdaptiveReprojectedParams(C.Structure):
+    """rt_adaptive_reprojected_params: rt_adaptive_params' six fields and the
+    degrees of freedom below which a hit pixel is always selected."""
+    _fields_ = AdaptiveParams._fields_ + [("min_dof", C.c_float)]
+
+
 class AdaptiveStats(C.Structure):
     """rt_adaptive_stats: pixels the last adaptive call rendered, the sum of the
     per-pixel frame counts after it, and its three stages' durations (ms)."""
@@ -183,6 +189,12 @@ def _proto(lib):
         "rt_temporal_var": (C.c_int, [vp, P(TemporalParams), P(DenoiseVarParams), vp, vp, vp, vp]),
         "rt_temporal_var_device": (C.c_int, [vp, P(TemporalParams), P(DenoiseVarParams), vp, vp]),
         "rt_last_temporal_var_ms": (C.c_float, [vp]),
+        "rt_temporal_var_counted": (C.c_int, [vp, P(TemporalParams), P(DenoiseVarParams), vp, vp, vp, vp]),
+        "rt_temporal_var_counted_device": (C.c_int, [vp, P(TemporalParams), P(DenoiseVarParams), vp, vp]),
+        "rt_adaptive_reprojected_params_default": (AdaptiveReprojectedParams, []),
+        "rt_render_adaptive_reprojected": (C.c_int, [vp, P(AdaptiveReprojectedParams), C.c_int, vp, vp,
+                                                     P(AdaptiveStats)]),
+        "rt_render_adaptive_reprojected_device": (C.c_int, [vp, P(AdaptiveReprojectedParams), C.c_int, vp, vp]),
         "rt_set_moments": (C.c_int, [vp, C.c_int]),
         "rt_get_moments": (C.c_int, [vp]),
         "rt_moments_batches": (C.c_int, [vp]),

@@ -349,18 +349,37 @@ class Renderer:
         RGBA8 image, with want_color / want_length / want_moments also the
         linear colour (H, W, 3), the effective sample count (H, W) and {variance
         of the mean luminance, degrees of freedom} (H, W, 2), in that order."""
+        return self._temporal_var(self.lib.rt_temporal_var, width, height, denoise_var, want_color, want_length,
+                                  want_moments, tp)
+
+    def _temporal_var(self, fn, width, height, denoise_var, want_color, want_length, want_moments, tp):
         t = self.temporal_params(**tp)
         out = np.empty((height, width, 4), np.uint8)
         col = np.empty((height, width, 3), np.float32) if want_color else None
         ln = np.empty((height, width), np.float32) if want_length else None
         mom = np.empty((height, width, 2), np.float32) if want_moments else None
-        self._check(self.lib.rt_temporal_var(self.ctx, C.byref(t), self._dv(denoise_var), out.ctypes.data,
-                                             col.ctypes.data if col is not None else None,
-                                             ln.ctypes.data if ln is not None else None,
-                                             mom.ctypes.data if mom is not None else None))
+        self._check(fn(self.ctx, C.byref(t), self._dv(denoise_var), out.ctypes.data,
+                       col.ctypes.data if col is not None else None,
+                       ln.ctypes.data if ln is not None else None,
+                       mom.ctypes.data if mom is not None else None))
         res = ((out,) + ((col,) if want_color else ()) + ((ln,) if want_length else ())
                + ((mom,) if want_moments else ()))
         return res if len(res) > 1 else out
+
+    def temporal_var_counted(self, width, height, denoise_var=None, want_color=False, want_length=False,
+                             want_moments=False, **tp):
+        """rt_temporal_var_counted: temporal_var on a non-uniform frame (after an
+        adaptive call, or a counted assembled frame; set_adaptive_filters on):
+        every pixel merges with its own frame and batch counts.  Arguments and
+        results as temporal_var, which it equals on a uniform frame."""
+        return self._temporal_var(self.lib.rt_temporal_var_counted, width, height, denoise_var, want_color,
+                                  want_length, want_moments, tp)
+
+    def temporal_var_counted_device(self, rgba_ptr: int, stream_ptr: int | None = None, denoise_var=None, **tp):
+        """rt_temporal_var_counted_device: as temporal_var_device."""
+        t = self.temporal_params(**tp)
+        self._check(self.lib.rt_temporal_var_counted_device(self.ctx, C.byref(t), self._dv(denoise_var), rgba_ptr,
+                                                            stream_ptr))
 
     def temporal_var_device(self, rgba_ptr: int, stream_ptr: int | None = None, denoise_var=None, **tp):
         """rt_temporal_var_device: the reprojected (and, with `denoise_var`,
@@ -432,6 +451,39 @@ class Renderer:
         device memory on a stream (asynchronous, ordered like render_device)."""
         d = self.adaptive_params(**params)
         self._check(self.lib.rt_render_adaptive_device(self.ctx, C.byref(d), max_bounces, rgba_ptr, stream_ptr))
+
+    def adaptive_reprojected_params(self, min_dof=None, **params):
+        """rt_adaptive_reprojected_params_default() with the given fields
+        replaced (adaptive_params()'s and min_dof)."""
+        d = self.lib.rt_adaptive_reprojected_params_default()
+        for name, v in dict(params, min_dof=min_dof).items():
+            if name not in dict(abi.AdaptiveReprojectedParams._fields_):
+                raise TypeError(f"unknown adaptive parameter {name!r}")
+            if v is not None:
+                setattr(d, name, v)
+        return d
+
+    def render_adaptive_reprojected(self, width, height, max_bounces=-1, want_color=False, **params):
+        """rt_render_adaptive_reprojected: `samples` more frames for the pixels
+        that the pending planes of the current view select (temporal_var's
+        {colour, length, s2, dof}: a moving camera needs one render call per
+        view, not two); `params` are adaptive_reprojected_params() fields.
+        Returns what render_adaptive returns."""
+        d = self.adaptive_reprojected_params(**params)
+        out = np.empty((height, width, 4), np.uint8)
+        col = np.empty((height, width, 3), np.float32) if want_color else None
+        st = abi.AdaptiveStats()
+        self._check(self.lib.rt_render_adaptive_reprojected(self.ctx, C.byref(d), max_bounces, out.ctypes.data,
+                                                            col.ctypes.data if col is not None else None,
+                                                            C.byref(st)))
+        return (out, col, self._stats(st)) if want_color else (out, self._stats(st))
+
+    def render_adaptive_reprojected_device(self, rgba_ptr: int, stream_ptr: int | None = None, max_bounces=-1,
+                                           **params):
+        """rt_render_adaptive_reprojected_device: as render_adaptive_device."""
+        d = self.adaptive_reprojected_params(**params)
+        self._check(self.lib.rt_render_adaptive_reprojected_device(self.ctx, C.byref(d), max_bounces, rgba_ptr,
+                                                                   stream_ptr))
 
     def adaptive_stats(self) -> dict:
         """rt_adaptive_last_stats: the last adaptive call's statistics (synchronises)."""

@@ -30,7 +30,8 @@
 //   uniform render done                    frame = first + samples; if tracked: batches =
 //                                          (first == 1 ? 1 : batches + 1), live, next = first + samples
 //   launch failure                         tracking and non-uniform end; frame unchanged
-//   adaptive call, before it is queued     needs batches >= 2 and `current`, else refused
+//   adaptive call, before it is queued     needs batches >= 2 (rt_render_adaptive_reprojected: >= 1)
+//                                          and `current`, else refused
 //   adaptive call done                     first of an accumulation: max_n = next - 1; then
 //                                          max_n += samples; non-uniform; frame, batches, next unchanged
 //   adaptive launch failure                tracking and non-uniform end

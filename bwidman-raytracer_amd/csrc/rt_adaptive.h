@@ -23,6 +23,28 @@
 // take the step of rt_moments.h with the pixel's own weight
 //   kw_p = rt_div(kf, (float)(n_p + k)),
 // then J_p += 1, n_p += k, prev_p = frameSum_p.
+//
+// Selection from the reprojected variance (rt_render_adaptive_reprojected,
+// DESIGN.md section 22).  The context's pending temporal set of the current view
+// (rt_temporal_var; rt_temporal_var.h) gives per pixel q col_q = {out.rgb, len},
+// mom_q = {s2, dof} and, from its guide copy, prim_q:
+//   v_q = rt_div(s2_q, len_q)        m_q = mom_lum(col_q.rgb)
+//   tap q counts (sv += v_q, sm += m_q, c++) iff dof_q > 0 and v_q, m_q finite
+//   hot_p: the expression above over the window, unchanged (row sums in increasing
+//          x, column sums in increasing y)
+//   fresh_p = prim_p >= 0 && !(dof_p >= min_dof)
+//   selected_p = (max_frames == 0 || n_p + k <= max_frames) &&
+//                (n_p < min_frames || hot_p || fresh_p)
+// fresh: a hit pixel about which the history says nothing (dof 0 or NaN), or too
+// little, is rendered: disocclusions and the first view.  Miss pixels are not
+// forced (the reprojection skips them); a silhouette's noise reaches them
+// through the window.  The planes are only read.
+//
+// Counts.  A non-uniform state that rt_render_adaptive started has J_p >= 2;
+// rt_render_adaptive_reprojected may start from one batch, and the pixels it does
+// not select then keep J_p = 1 (n_p >= 1).  For them ad_var's divisor is 0: v_q
+// is M2_q * inf, not finite (NaN for the M2_q = 0 a single batch leaves), and
+// ad_row_sums skips the tap like any other non-finite one.
 #pragma once
 #include "rt_moments.h"
 
@@ -72,6 +94,42 @@ RT_HD bool ad_selected(const rt_ad_args& A, int x, int y, long p) {
     const float cf = (float)c;
     const float b = A.tolerance * (sm + cf * A.lum_floor);
     return c > 0 && (sv * cf) > (b * b);
+}
+
+// ad_row_sums over the pending planes: per tap 16 bytes of {out.rgb, len} and 8
+// of {s2, dof}
+RT_HD void ad_row_sums_reproj(const rt_ad_reproj_args& R, int x, int y, long p) {
+    const rt_ad_args& A = R.A;
+    float sv = 0.0f, sm = 0.0f;
+    int c = 0;
+    const int x0 = x - A.radius < 0 ? 0 : x - A.radius;
+    const int x1 = x + A.radius >= A.width ? A.width - 1 : x + A.radius;
+    for (int qx = x0; qx <= x1; qx++) {
+        const long q = (long)y * A.width + qx;
+        const float4 col = R.p_col[q];
+        const float2 m = R.p_mom[q];
+        const float v = rt_div(m.x, col.w);
+        const float l = mom_lum(col.x, col.y, col.z);
+        if (!(m.y > 0.0f) || !ad_finite(v) || !ad_finite(l)) continue;
+        sv = sv + v;
+        sm = sm + l;
+        c++;
+    }
+    A.rowv[p] = sv;
+    A.rowm[p] = sm;
+    A.rowc[p] = c;
+}
+
+// ad_selected with the `fresh` term: the pixel's dof and its primitive id, 4
+// bytes each, more (of {s2, dof} only dof is used and the load narrows to it)
+RT_HD bool ad_selected_reproj(const rt_ad_reproj_args& R, int x, int y, long p) {
+    const rt_ad_args& A = R.A;
+    const unsigned n = A.cnt[p].x;
+    if (A.max_frames != 0u && (unsigned long long)n + (unsigned)A.k > A.max_frames) return false;
+    const int prim = rt_f2i(reinterpret_cast<const float*>(R.p_ga + p)[3]);
+    const float dof = R.p_mom[p].y;
+    if (prim >= 0 && !(dof >= R.min_dof)) return true;
+    return ad_selected(A, x, y, p);
 }
 
 // ad_selected for pixel x of shard row j (p = j * width + x in the shard; image

@@ -16,6 +16,11 @@
 // block for the ranks' all-gather (rt_launch_adaptive_rows_block) and the test
 // reads its column taps from the gathered blocks (rt_launch_adaptive_shard);
 // scan, scatter, update and resolve are the same kernels over the shard's rows.
+//
+// For a moving camera (rt_render_adaptive_reprojected) the
+// row sums and the test have twins that read the pending planes of
+// rt_temporal_var instead of the tracked moments (rt_launch_adaptive_reproj);
+// everything behind the test is unchanged.
 #include <hip/hip_runtime.h>
 
 #include "rt_adaptive.h"
@@ -46,6 +51,33 @@ __global__ void __launch_bounds__(256) rt_adaptive_test_kernel(const rt_ad_args 
     const int y = (int)(wi / A.words_per_row);
     const int x = (int)(wi - (long)y * A.words_per_row) * 64 + (int)(threadIdx.x & 63);
     const bool sel = x < A.width && ad_selected(A, x, y, (long)y * A.width + x);
+    const unsigned long long m = __ballot(sel);
+    if ((threadIdx.x & 63) == 0) {
+        A.mask[wi] = m;
+        A.pop[wi] = (unsigned)__popcll(m);
+    }
+}
+
+// rt_adaptive_rows_kernel over the pending planes of the current view
+// (rt_render_adaptive_reprojected): 2 * radius + 1 taps of {out.rgb, len} and
+// {s2, dof} (24 bytes each), 12 bytes written
+__global__ void __launch_bounds__(256) rt_adaptive_rows_reproj_kernel(const rt_ad_reproj_args R) {
+    const rt_ad_args& A = R.A;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= A.npix) return;
+    const int y = (int)(p / A.width);
+    ad_row_sums_reproj(R, (int)(p - (long)y * A.width), y, p);
+}
+
+// rt_adaptive_test_kernel with the `fresh` term of that selection
+__global__ void __launch_bounds__(256) rt_adaptive_test_reproj_kernel(const rt_ad_reproj_args R) {
+    const rt_ad_args& A = R.A;
+    const long wi = ((long)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const long nwords = (long)A.words_per_row * A.height;
+    if (wi >= nwords) return;  // wave-uniform
+    const int y = (int)(wi / A.words_per_row);
+    const int x = (int)(wi - (long)y * A.words_per_row) * 64 + (int)(threadIdx.x & 63);
+    const bool sel = x < A.width && ad_selected_reproj(R, x, y, (long)y * A.width + x);
     const unsigned long long m = __ballot(sel);
     if ((threadIdx.x & 63) == 0) {
         A.mask[wi] = m;
@@ -172,6 +204,18 @@ hipError_t rt_launch_adaptive(const rt_ad_args& A, int stage, hipStream_t stream
     } else {
         hipLaunchKernelGGL(rt_adaptive_resolve_kernel, dim3(blocks_of(A.npix)), dim3(256), 0, stream, A);
     }
+    return hipGetLastError();
+}
+
+// stages 0 and 1 of rt_render_adaptive_reprojected
+hipError_t rt_launch_adaptive_reproj(const rt_ad_reproj_args& R, hipStream_t stream) {
+    const rt_ad_args& A = R.A;
+    if (A.npix <= 0 || A.npix > 0x7fffffffl || !A.cnt || !R.p_col || !R.p_mom || !R.p_ga) return hipErrorInvalidValue;
+    const long nwords = (long)A.words_per_row * A.height;
+    hipLaunchKernelGGL(rt_adaptive_rows_reproj_kernel, dim3(blocks_of(A.npix)), dim3(256), 0, stream, R);
+    hipLaunchKernelGGL(rt_adaptive_test_reproj_kernel, dim3(blocks_of(nwords * 64)), dim3(256), 0, stream, R);
+    hipLaunchKernelGGL(rt_adaptive_scan_kernel, dim3(1), dim3(1024), 0, stream, A);
+    hipLaunchKernelGGL(rt_adaptive_scatter_kernel, dim3(blocks_of(nwords * 64)), dim3(256), 0, stream, A);
     return hipGetLastError();
 }
 

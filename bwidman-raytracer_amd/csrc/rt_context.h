@@ -46,6 +46,8 @@ int rt_cpu_render(const rt_kparams& K, int threads);
 // adaptive sampling on the host (rt_adaptive.h): selection into A.list /
 // *A.list_n, the listed pixels' frames, their update, the resolve pass
 void rt_cpu_adaptive_select(const rt_ad_args& A, int threads);
+// the selection of rt_render_adaptive_reprojected, from the pending planes
+void rt_cpu_adaptive_select_reproj(const rt_ad_reproj_args& R, int threads);
 // on row shards: the row sums of the shard's rows into its block, and the
 // selection from the gathered blocks
 void rt_cpu_adaptive_rows_block(const rt_ad_args& A, long plane, int threads);
@@ -57,7 +59,7 @@ bool rt_cpu_supported();
 void rt_cpu_aov(const rt_kparams& K, int threads, float4* ga, float4* gb, float4* alb);
 void rt_cpu_denoise_level(const rt_dn_level& L, int threads);
 void rt_cpu_temporal(const rt_tp_args& T, int threads);
-void rt_cpu_temporal_var(const rt_tv_args& V, int threads);
+void rt_cpu_temporal_var(const rt_tv_cnt_args& V, int threads);  // V.cnt non-null: the count-aware pass
 void rt_cpu_temporal_var_input(const rt_tv_input& A, int threads);
 void rt_cpu_moments(const rt_mom_args& A, int threads);
 void rt_cpu_denoise_var(const rt_dv_args& A, int stage, int threads);
@@ -68,7 +70,8 @@ hipError_t rt_launch_denoise_level(const rt_dn_level& L, bool tiled, hipStream_t
 // temporal reprojection (rt_temporal.hip)
 hipError_t rt_launch_temporal(const rt_tp_args& T, hipStream_t stream);
 // moment-carrying reprojection and the input stage of the levels behind it (rt_temporal_var.hip)
-hipError_t rt_launch_temporal_var(const rt_tv_args& V, hipStream_t stream);
+// (V.cnt non-null: the count-aware kernel of rt_temporal_var_counted)
+hipError_t rt_launch_temporal_var(const rt_tv_cnt_args& V, hipStream_t stream);
 hipError_t rt_launch_temporal_var_input(const rt_tv_input& A, hipStream_t stream);
 // luminance moment update (rt_moments.hip)
 hipError_t rt_launch_moments(const rt_mom_args& A, hipStream_t stream);
@@ -82,6 +85,9 @@ hipError_t rt_launch_assemble(const rt_asm_args& A, int max_blocks, hipStream_t 
 hipError_t rt_launch_adaptive_fill(uint2* cnt, unsigned long long* total, long npix, unsigned n, unsigned J,
                                    hipStream_t stream);
 hipError_t rt_launch_adaptive(const rt_ad_args& A, int stage, hipStream_t stream);
+// stages 0 and 1 of rt_render_adaptive_reprojected: row sums over the pending
+// planes, column sums + test with the `fresh` term, then scan and scatter as ever
+hipError_t rt_launch_adaptive_reproj(const rt_ad_reproj_args& R, hipStream_t stream);
 // adaptive sampling on row shards: the row sums of a shard's rows into its block
 // (planes of `plane` words, padding rows zeroed), and stage 1 with the column
 // taps from the gathered blocks

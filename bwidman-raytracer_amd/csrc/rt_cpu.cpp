@@ -328,8 +328,13 @@ void rt_cpu_temporal(const rt_tp_args& T, int threads) {
 
 // The moment-carrying reprojection pass and the input stage of the levels
 // behind it (rt_temporal_var.h), on the same pool
-void rt_cpu_temporal_var(const rt_tv_args& V, int threads) {
-    parallel_pixels(V.t.width, V.t.height, threads, [&](int x, int y, long) { tv_run_pixel(V, x, y); });
+void rt_cpu_temporal_var(const rt_tv_cnt_args& V, int threads) {
+    parallel_pixels(V.t.width, V.t.height, threads, [&](int x, int y, long) {
+        if (V.cnt)
+            tv_run_pixel_cnt(V, x, y);
+        else
+            tv_run_pixel(V, x, y);
+    });
 }
 void rt_cpu_temporal_var_input(const rt_tv_input& A, int threads) {
     parallel_pixels(A.f.width, A.f.height, threads, [&](int x, int y, long p) { at_store(A.f, p, tv_input(A, x, y)); });
@@ -380,6 +385,21 @@ void rt_cpu_adaptive_select(const rt_ad_args& A, int threads) {
     std::vector<unsigned char> flags((size_t)A.npix);  // (no ballot on the host: one byte per pixel)
     parallel_pixels(A.width, A.height, threads,
                     [&](int x, int y, long p) { flags[(size_t)p] = ad_selected(A, x, y, p) ? 1 : 0; });
+    unsigned n = 0;
+    for (long p = 0; p < A.npix; p++)
+        if (flags[(size_t)p]) A.list[n++] = (int)p;
+    *A.list_n = n;
+    *A.total = *A.total + (unsigned long long)n * (unsigned)A.k;
+}
+
+// The selection of rt_render_adaptive_reprojected: the same three steps over the
+// pending planes, the test with the `fresh` term
+void rt_cpu_adaptive_select_reproj(const rt_ad_reproj_args& R, int threads) {
+    const rt_ad_args& A = R.A;
+    parallel_pixels(A.width, A.height, threads, [&](int x, int y, long p) { ad_row_sums_reproj(R, x, y, p); });
+    std::vector<unsigned char> flags((size_t)A.npix);
+    parallel_pixels(A.width, A.height, threads,
+                    [&](int x, int y, long p) { flags[(size_t)p] = ad_selected_reproj(R, x, y, p) ? 1 : 0; });
     unsigned n = 0;
     for (long p = 0; p < A.npix; p++)
         if (flags[(size_t)p]) A.list[n++] = (int)p;

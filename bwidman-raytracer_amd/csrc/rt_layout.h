@@ -325,6 +325,14 @@ struct rt_tv_args {
     float2* p_mom;       // pending {s2_out, dof_out}
 };
 
+// The same pass over a non-uniform frame (rt_temporal_var_counted): the counts
+// behind the uniform struct, whose kernel takes rt_tv_args alone and keeps its
+// argument offsets.  `tracked` then says that the frame carries moments at all
+// (the choice J_p >= 2 is per pixel) and dof_c is not read.
+struct rt_tv_cnt_args : rt_tv_args {
+    const uint2* cnt;    // {n_p, J_p}
+};
+
 // The input stage of the variance-guided levels behind that pass: f.dst takes
 // {out.xyz, v0} (f.ga, f.gb, f.in, f.ip: the spatial estimate's window)
 struct rt_tv_input {
@@ -369,6 +377,18 @@ struct rt_ad_args {
     unsigned long long* total;  // sum of n_p over the frame
     unsigned* rgba;          // resolve: tone_map(frameSum, n_p) (may be null)
     float* color;            // resolve: rt_div(1, n_p) * frameSum, interleaved r,g,b (may be null)
+};
+
+// The selection of rt_render_adaptive_reprojected (rt_adaptive.h, ad_row_sums_reproj
+// and ad_selected_reproj): the window's variance and luminance come from the
+// pending planes of the context's current view (rt_temporal_var), which are only
+// read.  The existing kernels take rt_ad_args alone: its layout stays as it is.
+struct rt_ad_reproj_args {
+    rt_ad_args A;            // (mom_in is not read by the selection)
+    const float4* p_col;     // pending {out.rgb, len}
+    const float2* p_mom;     // pending {s2, dof}
+    const float4* p_ga;      // pending guide copy: .w = prim as bits
+    float min_dof;           // a hit pixel with !(dof >= min_dof) is always selected
 };
 
 // The selection of an adaptive call on a row shard (rt_adaptive.h,

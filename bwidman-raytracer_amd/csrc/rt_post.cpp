@@ -448,14 +448,16 @@ int temporal_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_
 // with a filter (dv, iterations >= 1), the variance-guided levels behind the
 // call's own input stage.  out.length and out.moments are the pending planes,
 // out.color the levels' final {colour, variance} or the pending colour.
+// `counted` (rt_temporal_var_counted): a non-uniform frame is taken, behind
+// rt_set_adaptive_filters (full_frame_check), with every pixel's own counts.
 int temporal_var_pass(rt_context* c, const rt_temporal_params* tp, const rt_denoise_var_params* dv, hipStream_t s,
-                      unsigned* rgba, Result& out) {
+                      unsigned* rgba, Result& out, bool counted = false) {
     const HostFpEnv fp;
     int rc = temporal_check(c, tp, nullptr);
     if (!rc && dv) rc = denoise_var_check(c, dv);
     if (!rc) rc = full_frame_check(c, "moment reprojection");
-    // (before anything is allocated or promoted: per-pixel counts in the merge are not defined yet)
-    if (!rc && frame_counts(c))
+    // (before anything is allocated or promoted: per-pixel counts in the merge are rt_temporal_var_counted's)
+    if (!rc && !counted && frame_counts(c))
         return fail(c, RT_ERR_UNSUPPORTED,
                     "the frame is non-uniform (rt_render_adaptive, rt_assemble_adaptive): rt_temporal_var takes one "
                     "frame count for all pixels, with or without rt_set_adaptive_filters");
@@ -469,7 +471,7 @@ int temporal_var_pass(rt_context* c, const rt_temporal_params* tp, const rt_deno
     }
     if (rc) return rc;
     const bool filter = dv && dv->iterations > 0;
-    rt_tv_args V;
+    rt_tv_cnt_args V;
     std::memset(&V, 0, sizeof V);
     rt_kparams K;
     rt_context::TpSet& P = temporal_sets(c, tp, V.t, K);
@@ -480,6 +482,12 @@ int temporal_var_pass(rt_context* c, const rt_temporal_params* tp, const rt_deno
     if (V.tracked) {
         V.dof_c = (float)(src.batches - 1u);
         V.mom = src.mom;
+    }
+    // non-uniform: whether the frame carries moments at all; J_p >= 2 is the pixel's question
+    if ((V.cnt = frame_counts(c))) {
+        V.tracked = src.tracked;
+        V.dof_c = 0.0f;
+        V.mom = src.tracked ? src.mom : nullptr;
     }
     V.h_mom = H.has_mom ? H.mom.as<float2>() : nullptr;
     V.p_mom = P.mom.as<float2>();
@@ -514,6 +522,40 @@ int host_call(rt_context* c, uint8_t* rgba_out, float* color_out, float* length_
     if (const int rc = run(c->stream, rgba_out ? c->dn_rgba.as<unsigned>() : nullptr, out)) return rc;
     if (kept) *kept = out;
     return read_back(c, npix, rgba_out, out.color, color_out, out.length, length_out);
+}
+
+// The host form of rt_temporal_var and rt_temporal_var_counted: the pass, the
+// host copies, and moments_out
+int temporal_var_host(rt_context* c, const rt_temporal_params* tp, const rt_denoise_var_params* dv, uint8_t* rgba_out,
+                      float* color_out, float* length_out, float* moments_out, bool counted) {
+    Result res;
+    int rc = host_call(c, rgba_out, color_out, length_out, [&](hipStream_t s, unsigned* rgba, Result& out) {
+        return temporal_var_pass(c, tp, dv, s, rgba, out, counted);
+    }, &res);
+    if (rc || !moments_out) return rc;
+    // {variance of the mean, dof}: the pending planes, and behind a filter its final .w
+    const HostFpEnv fp;
+    const size_t npix = (size_t)c->height * c->width;
+    const float2* mom = res.moments->as<float2>();
+    const float4* len = res.length->as<float4>();
+    const float4* var = res.filtered ? res.color->as<float4>() : nullptr;
+    std::vector<float2> hm;
+    std::vector<float4> hv;
+    if (!c->cpu) {  // (read_back has synchronised the stream: the buffers are settled)
+        if (!try_resize(hm, npix) || !try_resize(hv, npix))
+            return fail(c, RT_ERR_OUT_OF_MEMORY, "host moments for %zu pixels", npix);
+        HIP_TRY(c, hipMemcpyAsync(hm.data(), mom, npix * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(hv.data(), var ? var : len, npix * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        mom = hm.data();
+        len = hv.data();
+        if (var) var = hv.data();
+    }
+    for (size_t i = 0; i < npix; i++) {
+        moments_out[2 * i] = var ? var[i].w : tv_var_of_mean(mom[i], len[i].w);
+        moments_out[2 * i + 1] = mom[i].y;
+    }
+    return RT_OK;
 }
 
 }  // namespace
@@ -659,34 +701,7 @@ float rt_last_temporal_ms(rt_context* c) { return c ? c->temporal.elapsed_ms() :
 
 int rt_temporal_var(rt_context* c, const rt_temporal_params* tp, const rt_denoise_var_params* dv, uint8_t* rgba_out,
                     float* color_out, float* length_out, float* moments_out) {
-    Result res;
-    int rc = host_call(c, rgba_out, color_out, length_out, [&](hipStream_t s, unsigned* rgba, Result& out) {
-        return temporal_var_pass(c, tp, dv, s, rgba, out);
-    }, &res);
-    if (rc || !moments_out) return rc;
-    // {variance of the mean, dof}: the pending planes, and behind a filter its final .w
-    const HostFpEnv fp;
-    const size_t npix = (size_t)c->height * c->width;
-    const float2* mom = res.moments->as<float2>();
-    const float4* len = res.length->as<float4>();
-    const float4* var = res.filtered ? res.color->as<float4>() : nullptr;
-    std::vector<float2> hm;
-    std::vector<float4> hv;
-    if (!c->cpu) {  // (read_back has synchronised the stream: the buffers are settled)
-        if (!try_resize(hm, npix) || !try_resize(hv, npix))
-            return fail(c, RT_ERR_OUT_OF_MEMORY, "host moments for %zu pixels", npix);
-        HIP_TRY(c, hipMemcpyAsync(hm.data(), mom, npix * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(hv.data(), var ? var : len, npix * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        mom = hm.data();
-        len = hv.data();
-        if (var) var = hv.data();
-    }
-    for (size_t i = 0; i < npix; i++) {
-        moments_out[2 * i] = var ? var[i].w : tv_var_of_mean(mom[i], len[i].w);
-        moments_out[2 * i + 1] = mom[i].y;
-    }
-    return RT_OK;
+    return temporal_var_host(c, tp, dv, rgba_out, color_out, length_out, moments_out, false);
 }
 
 int rt_temporal_var_device(rt_context* c, const rt_temporal_params* tp, const rt_denoise_var_params* dv,
@@ -695,6 +710,20 @@ int rt_temporal_var_device(rt_context* c, const rt_temporal_params* tp, const rt
     Result out;
     const int rc = device_call(c, "rt_temporal_var_device", {{rgba_device, "rgba_device", false}}, stream, &s);
     return rc ? rc : temporal_var_pass(c, tp, dv, s, (unsigned*)rgba_device, out);
+}
+
+// The count-aware form: rt_temporal_var's signatures
+int rt_temporal_var_counted(rt_context* c, const rt_temporal_params* tp, const rt_denoise_var_params* dv,
+                            uint8_t* rgba_out, float* color_out, float* length_out, float* moments_out) {
+    return temporal_var_host(c, tp, dv, rgba_out, color_out, length_out, moments_out, true);
+}
+
+int rt_temporal_var_counted_device(rt_context* c, const rt_temporal_params* tp, const rt_denoise_var_params* dv,
+                                   void* rgba_device, void* stream) {
+    hipStream_t s;
+    Result out;
+    const int rc = device_call(c, "rt_temporal_var_counted_device", {{rgba_device, "rgba_device", false}}, stream, &s);
+    return rc ? rc : temporal_var_pass(c, tp, dv, s, (unsigned*)rgba_device, out, true);
 }
 
 float rt_last_temporal_var_ms(rt_context* c) { return c ? c->temporal_var.elapsed_ms() : -1.0f; }
@@ -719,7 +748,10 @@ int rt_get_variance(rt_context* c, float* var_out, float* lum_out) {
     const HostFpEnv fp;
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     const unsigned J = c->st.batches();
-    if (J < 2u)
+    // (a non-uniform state on a one-batch base, rt_render_adaptive_reprojected's, has pixels with
+    // J_p = 2 and more: they report; a pixel still at J_p = 1 has no estimate and reports ad_var's
+    // own value there, M2 * inf, which is not finite: NaN for the M2 = 0 of a single batch)
+    if (J < 2u && !(J == 1u && c->st.nonuniform()))
         return fail(c, RT_ERR_INVALID_ARGUMENT,
                     "no variance yet: moment tracking %s, %u batches (needs rt_set_moments and two render calls "
                     "of one accumulation)",

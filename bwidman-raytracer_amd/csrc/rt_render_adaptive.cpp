@@ -2,6 +2,8 @@
 // (include/rt_abi.h): rt_render_adaptive*, rt_adaptive_last_stats,
 // rt_get_counts, and the two-phase form on row shards (rt_adaptive_export_rows*,
 // rt_render_adaptive_shard*, rt_render_adaptive_multi).
+// rt_render_adaptive_reprojected* is the same call with the selection made from
+// the pending planes of rt_temporal_var (a moving camera: DESIGN.md section 22).
 // csrc/rt_adaptive.h has the selection's arithmetic, rt_adaptive.hip and
 // rt_kernel_list.h the kernels, rt_cpu.cpp their host twins.
 //
@@ -22,7 +24,10 @@
 
 namespace {
 
-int params_check(rt_context* c, const rt_adaptive_params* p, int& max_bounces, bool shard_ok = false) {
+// min_batches: 2 for the selection from the tracked moments (its variance needs
+// two), 1 for the selection from the pending planes
+int params_check(rt_context* c, const rt_adaptive_params* p, int& max_bounces, bool shard_ok = false,
+                 unsigned min_batches = 2u) {
     if (!c || !p) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
     if (p->samples < 1 || !(p->tolerance > 0.0f) || !(p->lum_floor >= 0.0f) || std::isinf(p->lum_floor) ||
@@ -42,10 +47,11 @@ int params_check(rt_context* c, const rt_adaptive_params* p, int& max_bounces, b
                     "the context holds a row shard (offset %d, stride %d): the selection window needs a full frame",
                     c->row_offset, c->row_stride);
     const rt_accum_state& st = c->st;
-    if (st.batches() < 2u || !c->rng.p)
+    if (st.batches() < min_batches || !c->rng.p)
         return fail(c, RT_ERR_INVALID_ARGUMENT,
-                    "rt_render_adaptive needs live moment tracking with at least 2 batches (rt_set_moments and two "
-                    "render calls of one accumulation): tracking %s, %u batches",
+                    "rt_render_adaptive needs live moment tracking with at least %u batches (rt_set_moments and %s "
+                    "of one accumulation): tracking %s, %u batches",
+                    min_batches, min_batches >= 2u ? "two render calls" : "a render call",
                     st.batches() ? "live" : "not live", st.batches());
     if (!st.current())
         return fail(c, RT_ERR_INVALID_ARGUMENT,
@@ -112,11 +118,26 @@ void kparams(rt_context* c, int samples, int max_bounces, rt_kparams& K) {
 }
 
 // The ranks' gathered row-sum blocks of a phase 2 (p null: a full-frame call,
-// which makes its own row sums)
+// which makes its own row sums), or (col non-null, a full-frame call) the
+// pending planes that rt_render_adaptive_reprojected selects from
 struct Gathered {
-    const float* p;
-    int shards, rows_per_shard;
+    const float* p = nullptr;
+    int shards = 0, rows_per_shard = 0;
+    const float4* col = nullptr;
+    const float2* mom = nullptr;
+    const float4* ga = nullptr;
+    float min_dof = 0.0f;
 };
+
+rt_ad_reproj_args reproj_args(const rt_ad_args& A, const Gathered& g) {
+    rt_ad_reproj_args R;
+    R.A = A;
+    R.p_col = g.col;
+    R.p_mom = g.mom;
+    R.p_ga = g.ga;
+    R.min_dof = g.min_dof;
+    return R;
+}
 
 rt_ad_shard_args shard_args(const rt_context* c, const rt_ad_args& A, const Gathered& g) {
     rt_ad_shard_args S;
@@ -149,6 +170,8 @@ int cpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, fl
     const auto t0 = clock::now();
     if (g.p)
         rt_cpu_adaptive_select_shard(shard_args(c, A, g), c->threads);
+    else if (g.col)
+        rt_cpu_adaptive_select_reproj(reproj_args(A, g), c->threads);
     else
         rt_cpu_adaptive_select(A, c->threads);
     const auto t1 = clock::now();
@@ -194,8 +217,12 @@ int gpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, un
     if (timed) HIP_TRY(c, hipEventRecord(c->ad_ev[0], s));
     hipError_t e = hipSuccess;
     if (fresh) e = rt_launch_adaptive_fill(A.cnt, A.total, A.npix, c->st.tracked_frames(), c->st.batches(), s);
-    if (e == hipSuccess && !g.p) e = rt_launch_adaptive(A, 0, s);
-    if (e == hipSuccess) e = g.p ? rt_launch_adaptive_shard(shard_args(c, A, g), s) : rt_launch_adaptive(A, 1, s);
+    if (e == hipSuccess && g.col) {
+        e = rt_launch_adaptive_reproj(reproj_args(A, g), s);
+    } else {
+        if (e == hipSuccess && !g.p) e = rt_launch_adaptive(A, 0, s);
+        if (e == hipSuccess) e = g.p ? rt_launch_adaptive_shard(shard_args(c, A, g), s) : rt_launch_adaptive(A, 1, s);
+    }
     if (e == hipSuccess && timed) e = hipEventRecord(c->ad_ev[1], s);
     const rt_list_args L = {A.list, A.list_n, A.cnt};
     if (e == hipSuccess) e = rt_launch_render_list(K, L, c->num_cus, which, s);
@@ -213,6 +240,33 @@ int gpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, un
     HIP_TRY(c, c->render.end(s));
     c->ad_timed = timed;
     c->st.adaptive_done(p->samples);
+    return RT_OK;
+}
+
+// What rt_render_adaptive_reprojected needs: rt_render_adaptive's conditions
+// with one tracked batch, min_dof, and a pending temporal set of the current
+// view that carries moments; g then names its planes.  A refusal touches nothing.
+int reprojected_check(rt_context* c, const rt_adaptive_reprojected_params* p, int& max_bounces, Gathered& g,
+                      rt_adaptive_params& base) {
+    if (!c || !p) return fail(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+    base = {p->samples, p->tolerance, p->lum_floor, p->radius, p->min_frames, p->max_frames};
+    if (const int rc = params_check(c, &base, max_bounces, false, 1u)) return rc;
+    if (!(p->min_dof >= 0.0f))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "bad adaptive params: min_dof %g (>= 0)", (double)p->min_dof);
+    const rt_context::TpSet& P = c->tp[c->tp_hist ^ 1];
+    if (!c->tp_has_pending || c->tp_pending_view != c->view || c->tp_w != c->width || c->tp_h != c->height)
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "rt_render_adaptive_reprojected: no pending temporal set of the current view (call "
+                    "rt_temporal_var after the render of this view)");
+    if (!P.has_mom)
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "rt_render_adaptive_reprojected: the pending temporal set was written by rt_temporal and has no "
+                    "moments (call rt_temporal_var)");
+    g = Gathered{};
+    g.col = P.col.as<float4>();
+    g.mom = P.mom.as<float2>();
+    g.ga = P.ga.as<float4>();
+    g.min_dof = p->min_dof;
     return RT_OK;
 }
 
@@ -378,6 +432,63 @@ int rt_render_adaptive_device(rt_context* c, const rt_adaptive_params* p, int ma
     if (const int rc = params_check(c, p, max_bounces)) return rc;
     if (const int rc = device_aligned(c, {{rgba_device, "rgba_device", false}})) return rc;
     return gpu_adaptive(c, p, max_bounces, (unsigned*)rgba_device, nullptr, device_stream(c, stream), {});
+}
+
+// ---- selection from the reprojected variance -----------------------------------
+// (csrc/rt_adaptive.h has the selection)
+
+rt_adaptive_reprojected_params rt_adaptive_reprojected_params_default(void) {
+    rt_adaptive_reprojected_params d;
+    const rt_adaptive_params a = rt_adaptive_params_default();
+    d.samples = a.samples;
+    d.tolerance = a.tolerance;
+    d.lum_floor = a.lum_floor;
+    d.radius = a.radius;
+    d.min_frames = a.min_frames;
+    d.max_frames = a.max_frames;
+    // tools/adaptive_temporal_sweep.py (profiles/adaptive_temporal/sweep.txt): the row
+    // with the smallest mean ratio to uniform renders at equal frames.  rt_temporal_var's estimate is
+    // biased high under motion, so the tolerance is far above rt_adaptive_params_default()'s, and the
+    // window adds nothing there: the term that decides is `fresh`, below four degrees of freedom
+    d.tolerance = 0.4f;
+    d.radius = 0;
+    d.min_dof = 4.0f;
+    return d;
+}
+
+int rt_render_adaptive_reprojected(rt_context* c, const rt_adaptive_reprojected_params* p, int max_bounces,
+                                   uint8_t* rgba_out, float* color_out, rt_adaptive_stats* stats_out) {
+    Gathered g{};
+    rt_adaptive_params base;
+    if (const int rc = reprojected_check(c, p, max_bounces, g, base)) return rc;
+    const size_t npix = (size_t)c->height * c->width;
+    if (c->cpu) {
+        if (const int rc = cpu_adaptive(c, &base, max_bounces, color_out, g)) return rc;
+        if (rgba_out) std::memcpy(rgba_out, c->rgba.p, npix * 4);
+        return stats_out ? read_stats(c, stats_out) : RT_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_buf(c, c->rgba, npix * 4);
+    if (!rc && color_out) rc = ensure_buf(c, c->ad_color, npix * 3 * sizeof(float));
+    if (rc) return rc;
+    rc = gpu_adaptive(c, &base, max_bounces, c->rgba.as<unsigned>(), color_out ? c->ad_color.as<float>() : nullptr,
+                      c->stream, g);
+    if (rc) return rc;
+    if (rgba_out) HIP_TRY(c, hipMemcpyAsync(rgba_out, c->rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    if (color_out)
+        HIP_TRY(c, hipMemcpyAsync(color_out, c->ad_color.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return stats_out ? read_stats(c, stats_out) : RT_OK;
+}
+
+int rt_render_adaptive_reprojected_device(rt_context* c, const rt_adaptive_reprojected_params* p, int max_bounces,
+                                          void* rgba_device, void* stream) {
+    if (const int rc = device_ctx(c, "rt_render_adaptive_reprojected_device")) return rc;
+    Gathered g{};
+    rt_adaptive_params base;
+    if (const int rc = reprojected_check(c, p, max_bounces, g, base)) return rc;
+    if (const int rc = device_aligned(c, {{rgba_device, "rgba_device", false}})) return rc;
+    return gpu_adaptive(c, &base, max_bounces, (unsigned*)rgba_device, nullptr, device_stream(c, stream), g);
 }
 
 int rt_adaptive_last_stats(rt_context* c, rt_adaptive_stats* stats_out) { return read_stats(c, stats_out); }

@@ -14,7 +14,8 @@
 //   Uniform scalars (n, dof_c, the history camera) come from the kernel
 //   arguments.  Per pixel: 44 B read + 56 B written (60 with the RGBA) without history, up to
 //   4 x 56 B of taps more with one (L1 / L2 serve the overlap of neighbouring
-//   lanes' footprints: about 56 B per pixel reach HBM).
+//   lanes' footprints: about 56 B per pixel reach HBM).  On a non-uniform frame
+//   (TvPixelCnt) the lane's {n_p, J_p} is one 8-byte load more.
 // input: one lane per pixel.  Temporal source: the pending colour + length and
 //   moments of the pixel alone (24 B read, 16 B written).  Spatial source: the
 //   7 x 7 window of rt_denoise_var's input stage over the pending colours
@@ -32,6 +33,14 @@ struct TvPixel {
     static __device__ __forceinline__ void run(const rt_tv_args& V, int x, int y) { tv_run_pixel(V, x, y); }
 };
 
+// a non-uniform frame: the lane's {n_p, J_p} (8 bytes) in place of the uniform
+// n, inv and dof_c; the counts' pointer lies behind TvPixel's arguments
+struct TvPixelCnt {
+    using Args = rt_tv_cnt_args;
+    static RT_HD int2 size(const rt_tv_cnt_args& V) { return make_int2(V.t.width, V.t.height); }
+    static __device__ __forceinline__ void run(const rt_tv_cnt_args& V, int x, int y) { tv_run_pixel_cnt(V, x, y); }
+};
+
 struct TvInput {
     using Args = rt_tv_input;
     static RT_HD int2 size(const rt_tv_input& A) { return make_int2(A.f.width, A.f.height); }
@@ -42,7 +51,8 @@ struct TvInput {
 
 }  // namespace
 
-hipError_t rt_launch_temporal_var(const rt_tv_args& V, hipStream_t stream) {
+hipError_t rt_launch_temporal_var(const rt_tv_cnt_args& V, hipStream_t stream) {
+    if (V.cnt) return at_launch_pixels<TvPixelCnt>(V, stream);
     return at_launch_pixels<TvPixel>(V, stream);
 }
 

@@ -13,7 +13,7 @@
 //               [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]
 //               [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]
 //               [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]
-//               [--temporal-var [N]]
+//               [--temporal-var [N]] [--adaptive-temporal TOL] [--adaptive-rounds R]
 //               [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]
 //               [--adaptive TOL] [--adaptive-after 4] [--adaptive-radius R] [--adaptive-floor F]
 //               [--min-frames N] [--max-frames N]
@@ -52,6 +52,19 @@
 // --aov PREFIX writes PREFIX_tvar in PREFIX_var's encoding.  It cannot be
 // combined with --temporal, --denoise, --denoise-var, --adaptive or --gpus
 // above 1.
+// --adaptive-temporal TOL [--adaptive-rounds R], only with --temporal-var [N]:
+// adaptive sampling for a moving camera.  It turns the tracking and
+// rt_set_adaptive_filters on; in each loop iteration, after the uniform render
+// call and the unfiltered rt_temporal_var, it runs R (default 1) rounds of
+// rt_render_adaptive_reprojected with the call's frame count and tolerance TOL
+// (--adaptive-radius, --adaptive-floor, --min-frames, --max-frames and
+// --adaptive-min-dof replace the other fields of
+// rt_adaptive_reprojected_params_default()), each followed by
+// rt_temporal_var_counted.  The N levels and the written image come from the
+// last one of the last iteration; it prints every round's selected share.  An
+// iteration in a view the keys did not leave is the rounds alone (a uniform
+// render cannot continue a non-uniform accumulation).  It
+// cannot be combined with --gpus above 1 or --precision fast.
 // --aov PREFIX writes the first-hit feature buffers (rt_render_aov) as
 // PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5) and PREFIX_depth (1 / (1 +
 // depth), a miss black) images in --out's format (PNG without --out).
@@ -103,7 +116,7 @@ static const char* kUsage =
     "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n"
     "                   [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]\n"
     "                   [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]\n"
-    "                   [--temporal-var [N]]\n"
+    "                   [--temporal-var [N]] [--adaptive-temporal TOL] [--adaptive-rounds R] [--adaptive-min-dof F]\n"
     "                   [--aov PREFIX] [--moments] [--denoise-var [N]] [--sigma-lum F] [--min-batches N]\n"
     "                   [--adaptive TOL] [--adaptive-after 4] [--adaptive-radius R] [--adaptive-floor F]\n"
     "                   [--min-frames N] [--max-frames N] [--adaptive-filters]\n"
@@ -179,6 +192,10 @@ int main(int argc, char** argv) {
     bool adaptive = false, adaptive_filters = false;
     int adaptive_after = 4;
     rt_adaptive_params ad = rt_adaptive_params_default();
+    bool adaptive_temporal = false, rounds_given = false;
+    int adaptive_rounds = 1;
+    rt_adaptive_reprojected_params adr = rt_adaptive_reprojected_params_default();
+    bool radius_given = false, floor_given = false;
     for (int i = 1; i < argc; i++) {
         auto next = [&](void) -> const char* { return i + 1 < argc ? argv[++i] : ""; };
         if (!std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h")) {
@@ -246,8 +263,23 @@ int main(int argc, char** argv) {
         }
         else if (!std::strcmp(argv[i], "--adaptive-filters")) adaptive_filters = true;
         else if (!std::strcmp(argv[i], "--adaptive-after")) adaptive_after = std::atoi(next());
-        else if (!std::strcmp(argv[i], "--adaptive-radius")) ad.radius = std::atoi(next());
-        else if (!std::strcmp(argv[i], "--adaptive-floor")) ad.lum_floor = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--adaptive-temporal")) {
+            adaptive_temporal = true;
+            adr.tolerance = (float)std::atof(next());
+        }
+        else if (!std::strcmp(argv[i], "--adaptive-rounds")) {
+            rounds_given = true;
+            adaptive_rounds = std::atoi(next());
+        }
+        else if (!std::strcmp(argv[i], "--adaptive-min-dof")) adr.min_dof = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--adaptive-radius")) {
+            ad.radius = std::atoi(next());
+            radius_given = true;
+        }
+        else if (!std::strcmp(argv[i], "--adaptive-floor")) {
+            ad.lum_floor = (float)std::atof(next());
+            floor_given = true;
+        }
         else if (!std::strcmp(argv[i], "--min-frames")) ad.min_frames = (unsigned)std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--max-frames")) ad.max_frames = (unsigned)std::strtoul(next(), nullptr, 10);
         else {
@@ -266,11 +298,25 @@ int main(int argc, char** argv) {
                      "--gpus above 1: the filters and the fast mode take one frame count for all pixels\n");
         return 2;
     }
+    if ((adaptive_temporal || rounds_given) &&
+        (!adaptive_temporal || !temporal_var || adaptive_rounds < 1 || gpus > 1 || precision == RT_PRECISION_REFERENCE_FAST)) {
+        std::fprintf(stderr,
+                     "--adaptive-temporal TOL [--adaptive-rounds R >= 1] needs --temporal-var and cannot be combined with "
+                     "--gpus above 1 or --precision fast: it selects from the pending planes of rt_temporal_var on one "
+                     "full frame\n");
+        return 2;
+    }
     if (temporal_var && (temporal || denoise || denoise_var || adaptive || gpus > 1)) {
         std::fprintf(stderr,
                      "--temporal-var cannot be combined with --temporal, --denoise, --denoise-var, --adaptive or --gpus "
                      "above 1: it is the one pass behind every render call, on one uniform full frame\n");
         return 2;
+    }
+    if (adaptive_temporal) {
+        if (radius_given) adr.radius = ad.radius;
+        if (floor_given) adr.lum_floor = ad.lum_floor;
+        adr.min_frames = ad.min_frames;
+        adr.max_frames = ad.max_frames;
     }
     if (adaptive && adaptive_after < 2) {
         std::fprintf(stderr, "--adaptive-after must be at least 2: the selection needs two tracked batches\n");
@@ -334,8 +380,8 @@ int main(int argc, char** argv) {
         if ((rc = rt_set_scene(ctxs[g], &view))) return die(ctxs[g], rc, "rt_set_scene");
         if ((rc = rt_set_max_bounces(ctxs[g], max_bounces))) return die(ctxs[g], rc, "rt_set_max_bounces");
         if ((rc = rt_set_background(ctxs[g], bg[0], bg[1], bg[2]))) return die(ctxs[g], rc, "rt_set_background");
-        if (moments && (rc = rt_set_moments(ctxs[g], 1))) return die(ctxs[g], rc, "rt_set_moments");
-        if (adaptive_filters && (rc = rt_set_adaptive_filters(ctxs[g], 1))) return die(ctxs[g], rc, "rt_set_adaptive_filters");
+        if ((moments || adaptive_temporal) && (rc = rt_set_moments(ctxs[g], 1))) return die(ctxs[g], rc, "rt_set_moments");
+        if ((adaptive_filters || adaptive_temporal) && (rc = rt_set_adaptive_filters(ctxs[g], 1))) return die(ctxs[g], rc, "rt_set_adaptive_filters");
     }
     rt_context* ctx = ctxs[0];
     std::vector<uint8_t> rgba((size_t)width * height * 4);
@@ -359,7 +405,11 @@ int main(int argc, char** argv) {
         const int n = std::min(per_call, frames - done);
         auto t0 = clk::now();
         if (rt_frame_counter(ctx) == 1u) calls = 0;  // the accumulation restarts (controls())
-        if (adaptive && calls >= adaptive_after) {
+        // --adaptive-temporal in a view the keys did not leave: the accumulation is non-uniform and a uniform
+        // render cannot continue it; the iteration is the rounds alone, over the pending set of the last one
+        const bool rounds_only = adaptive_temporal && calls > 0;
+        if (rounds_only) {  // (nothing is rendered before the rounds)
+        } else if (adaptive && calls >= adaptive_after) {
             ad.samples = n;
             if ((rc = rt_render_adaptive(ctx, &ad, -1, rgba.data(), nullptr, &ast))) return die(ctx, rc, "rt_render_adaptive");
             ast_valid = true;
@@ -389,9 +439,27 @@ int main(int argc, char** argv) {
             rt_denoise_var_params lv = dv;
             lv.iterations = temporal_var_levels;
             if (last) tvar.resize((size_t)width * height * 2);
-            rc = rt_temporal_var(ctx, &tp, last ? &lv : nullptr, last ? rgba.data() : nullptr, nullptr, nullptr,
-                                 last ? tvar.data() : nullptr);
-            if (rc) return die(ctx, rc, "rt_temporal_var");
+            if (adaptive_temporal) {
+                // the pending planes of this view, then the rounds: select from them, render, merge again
+                if (!rounds_only && (rc = rt_temporal_var(ctx, &tp, nullptr, nullptr, nullptr, nullptr, nullptr)))
+                    return die(ctx, rc, "rt_temporal_var");
+                adr.samples = n;
+                for (int round = 0; round < adaptive_rounds; round++) {
+                    if ((rc = rt_render_adaptive_reprojected(ctx, &adr, -1, nullptr, nullptr, &ast)))
+                        return die(ctx, rc, "rt_render_adaptive_reprojected");
+                    std::printf("adaptive-temporal: call %d round %d selected %.1f %%, mean %.2f frames per pixel\n", calls,
+                                round + 1, 100.0 * (double)ast.selected / ((double)width * height),
+                                (double)ast.frames_total / ((double)width * height));
+                    const bool final = last && round == adaptive_rounds - 1;
+                    rc = rt_temporal_var_counted(ctx, &tp, final ? &lv : nullptr, final ? rgba.data() : nullptr, nullptr,
+                                                 nullptr, final ? tvar.data() : nullptr);
+                    if (rc) return die(ctx, rc, "rt_temporal_var_counted");
+                }
+            } else {
+                rc = rt_temporal_var(ctx, &tp, last ? &lv : nullptr, last ? rgba.data() : nullptr, nullptr, nullptr,
+                                     last ? tvar.data() : nullptr);
+                if (rc) return die(ctx, rc, "rt_temporal_var");
+            }
             if (last) {
                 double se = 0.0;
                 size_t known = 0;

@@ -26,6 +26,7 @@
  *    must be used by one host thread at a time.  All calls except
  *    rt_render_device()/rt_render_adaptive_device()/rt_denoise_device()/
  *    rt_denoise_var_device()/rt_temporal_device()/rt_temporal_var_device()/
+ *    rt_temporal_var_counted_device()/rt_render_adaptive_reprojected_device()/
  *    rt_deinterleave_rows_device() are synchronous.
  *  - Output RGBA8 buffers are row-major, row 0 = BOTTOM of the screen
  *    (the reference draws texcoord (0,0) at the bottom-left, Main.cu:358).
@@ -198,7 +199,8 @@ RT_API void rt_destroy(rt_context* ctx);
  * rt_get_state / rt_set_state, ...; rt_last_kernel_ms gives the last render's
  * wall time) except rt_render_device, rt_render_adaptive_device, rt_adaptive_export_rows_device,
  * rt_render_adaptive_shard_device, rt_denoise_device, rt_denoise_var_device,
- * rt_temporal_device, rt_temporal_var_device, rt_render_multi and rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no
+ * rt_temporal_device, rt_temporal_var_device, rt_temporal_var_counted_device,
+ * rt_render_adaptive_reprojected_device, rt_render_multi and rt_deinterleave_rows_device (RT_ERR_UNSUPPORTED: no
  * device memory).
  * Replaces the reference's config-1 CPU path and is the CPU baseline of
  * bench.py (SURVEY §8(b) rt_render_cpu, §8(d)). */
@@ -644,7 +646,7 @@ RT_API float rt_last_denoise_var_ms(rt_context* ctx);
  * variance; dof is the unfiltered one in both.
  * Errors as rt_temporal and rt_denoise_var, and RT_ERR_UNSUPPORTED for a
  * non-uniform accumulation or a counted assembled frame, with or without
- * rt_set_adaptive_filters. */
+ * rt_set_adaptive_filters (rt_temporal_var_counted below takes those). */
 RT_API int rt_temporal_var(rt_context* ctx, const rt_temporal_params* params, const rt_denoise_var_params* dv,
                            uint8_t* rgba_out, float* color_out, float* length_out, float* moments_out);
 /* As above into DEVICE memory, with rt_temporal_device's rules. */
@@ -735,6 +737,79 @@ RT_API int rt_adaptive_last_stats(rt_context* ctx, rt_adaptive_stats* stats_out)
  * batches tracked.  In the uniform state every pixel reports the context's
  * (frame counter - 1, rt_moments_batches).  Synchronous. */
 RT_API int rt_get_counts(rt_context* ctx, uint32_t* frames_out, uint32_t* batches_out);
+
+/* ---- adaptive sampling for a moving camera ------------------
+ * rt_render_adaptive needs two batches of one accumulation, which a host that
+ * renders one call per view never has.  rt_temporal_var carries {s2, dof} and a
+ * length per pixel across camera moves; rt_render_adaptive_reprojected selects
+ * from those PENDING planes of the current view and rt_temporal_var_counted
+ * merges the then non-uniform frame with the same history.  Per view:
+ *   1. rt_render: k0 frames, uniform, rt_set_moments on;
+ *   2. rt_temporal_var: the pending {out, len, s2, dof} of this view;
+ *   3. rt_render_adaptive_reprojected: k more frames for the selected pixels;
+ *   4. rt_temporal_var_counted (+ levels): the displayed frame
+ * (rt_set_adaptive_filters on).  Steps 3 and 4 may repeat within a view.
+ *
+ * Selection (csrc/rt_adaptive.h has the float operations): per pixel q of the
+ * pending planes v_q = s2_q / len_q, m_q = luminance of out_q; a tap counts in
+ * the window iff dof_q > 0 and v_q, m_q are finite; hot is rt_render_adaptive's
+ * expression over the window;
+ *     fresh    = prim_p >= 0 && !(dof_p >= min_dof)
+ *     selected = (max_frames == 0 || n_p + samples <= max_frames) &&
+ *                (n_p < min_frames || hot || fresh)
+ * A hit pixel about which the history says nothing or too little is rendered
+ * (disocclusions, the first view); miss pixels are not forced.  Every stage
+ * behind the selection is rt_render_adaptive's, the outputs and
+ * rt_adaptive_last_stats too, and afterwards the accumulation is non-uniform
+ * exactly as after it (the replay property holds).  The pending set is only
+ * read.  Repeated calls in one view read whatever pending set is current.
+ *
+ * From a one-batch base the pixels a call does not select keep J_p = 1: they
+ * have no tracked variance.  rt_get_variance then reports a non-finite value
+ * for them (NaN), rt_denoise_var takes its spatial estimate there,
+ * rt_temporal_var_counted merges no within-view term, rt_get_counts and the
+ * counted export report the 1, and rt_render_adaptive itself keeps refusing
+ * (its base needs two batches).
+ *
+ * Errors: rt_render_adaptive's with one batch in place of two, and
+ * RT_ERR_INVALID_ARGUMENT when min_dof is negative or NaN, or when the context
+ * has no pending temporal set of the current view with moments (none, one of an
+ * older view, one of another frame shape, or one that rt_temporal wrote).  A
+ * refused call touches nothing. */
+typedef struct rt_adaptive_reprojected_params {
+    int samples;         /* these six: rt_adaptive_params' */
+    float tolerance;
+    float lum_floor;
+    int radius;
+    unsigned min_frames;
+    unsigned max_frames;
+    float min_dof;       /* >= 0: a hit pixel whose pending dof is below it (or NaN) is always selected */
+} rt_adaptive_reprojected_params;
+RT_API rt_adaptive_reprojected_params rt_adaptive_reprojected_params_default(void);
+RT_API int rt_render_adaptive_reprojected(rt_context* ctx, const rt_adaptive_reprojected_params* params,
+                                          int max_bounces, uint8_t* rgba_out, float* color_out,
+                                          rt_adaptive_stats* stats_out);
+/* As rt_render_adaptive_device: one stream, inside one render pass, ordered
+ * behind the rt_temporal_var call that wrote the pending set whatever stream
+ * that ran on; no host synchronisation. */
+RT_API int rt_render_adaptive_reprojected_device(rt_context* ctx, const rt_adaptive_reprojected_params* params,
+                                                 int max_bounces, void* rgba_device, void* stream);
+/* rt_temporal_var on a non-uniform frame: a full-frame context after an adaptive
+ * call, or a shard context whose current assembled frame is counted (4 or 7
+ * planes; only 7 carry moments), both with rt_set_adaptive_filters on (off:
+ * RT_ERR_UNSUPPORTED).  Every pixel blends and counts with its own n_p
+ * (rt_temporal's count-aware colour, length and RGBA bit for bit) and brings its
+ * own within-view estimate M2_p / (J_p - 1) with J_p - 1 degrees of freedom where
+ * the frame carries moments and J_p >= 2, else none (csrc/rt_temporal_var.h).
+ * Arguments, outputs, history sets, promotion and errors otherwise as
+ * rt_temporal_var, with which and with rt_temporal it may alternate in any
+ * order; on a uniform frame it is rt_temporal_var.  rt_last_temporal_var_ms
+ * reports this pass too. */
+RT_API int rt_temporal_var_counted(rt_context* ctx, const rt_temporal_params* params,
+                                   const rt_denoise_var_params* dv, uint8_t* rgba_out, float* color_out,
+                                   float* length_out, float* moments_out);
+RT_API int rt_temporal_var_counted_device(rt_context* ctx, const rt_temporal_params* params,
+                                          const rt_denoise_var_params* dv, void* rgba_device, void* stream);
 
 /* ---- adaptive sampling on row shards ------------------------
  * rt_render_adaptive refuses a context that holds a row shard: the window's
