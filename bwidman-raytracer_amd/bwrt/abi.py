@@ -127,6 +127,7 @@ RT_ADAPTIVE_MAX_RADIUS = 4
 RT_DEFAULT_MAX_BOUNCES = 5
 RT_PRECISION_EXACT = 0
 RT_PRECISION_REFERENCE_FAST = 1
+RT_LIGHT_RECORD_FLOATS = 8  # rt_get_lights
 
 _lib = None
 
@@ -152,6 +153,9 @@ def _proto(lib):
         "rt_set_background": (C.c_int, [vp, C.c_float, C.c_float, C.c_float]),
         "rt_set_precision": (C.c_int, [vp, C.c_int]),
         "rt_get_precision": (C.c_int, [vp]),
+        "rt_set_light_sampling": (C.c_int, [vp, C.c_int]),
+        "rt_get_light_sampling": (C.c_int, [vp]),
+        "rt_get_lights": (C.c_int, [vp, C.POINTER(C.c_float), C.c_int]),
         "rt_set_samples_per_pixel": (C.c_int, [vp, C.c_int]),
         "rt_get_camera": (C.c_int, [vp, P(Camera)]),
         "rt_apply_controls": (C.c_int, [P(Camera), C.c_uint, C.c_float]),

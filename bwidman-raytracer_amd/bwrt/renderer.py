@@ -102,6 +102,30 @@ class Renderer:
     def precision(self) -> str:
         return "fast" if self.lib.rt_get_precision(self.ctx) == abi.RT_PRECISION_REFERENCE_FAST else "exact"
 
+    def set_light_sampling(self, on):
+        """rt_set_light_sampling: next-event estimation (sample the emissive
+        spheres at diffuse bounces) for the following render calls.  Another
+        estimator of the same expectation; accumulation, frame counter and RNG
+        streams stay.  Not with precision "fast" (the renders then refuse)."""
+        self._check(self.lib.rt_set_light_sampling(self.ctx, int(on)))
+
+    @property
+    def light_sampling(self) -> bool:
+        return bool(self.lib.rt_get_light_sampling(self.ctx))
+
+    def lights(self):
+        """rt_get_lights: the scene's light table as a structured array with
+        fields centre (3 float32), r2, emitted (3 float32) and prim (int32)."""
+        dt = np.dtype([("centre", np.float32, 3), ("r2", np.float32), ("emitted", np.float32, 3), ("prim", np.int32)])
+        n = self.lib.rt_get_lights(self.ctx, None, 0)
+        if n < 0:
+            self._check(n)
+        raw = np.zeros((max(n, 1), abi.RT_LIGHT_RECORD_FLOATS), np.float32)
+        got = self.lib.rt_get_lights(self.ctx, raw.ctypes.data_as(C.POINTER(C.c_float)), n)
+        if got < 0:
+            self._check(got)
+        return raw[:n].view(dt).reshape(n)
+
     def set_samples_per_pixel(self, n: int):
         """samplesPerPixel (Main.cu:27, 296-299): n paths per frame from one
         jittered camera ray, the last one kept and scaled by 1/n (default 1)."""

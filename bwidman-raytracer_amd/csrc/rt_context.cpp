@@ -284,14 +284,18 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
     const size_t bytes = cs.data.size() * sizeof(float);
     int rc = quiesce(c);  // a render on a caller's stream may still read the scene
     if (!rc) rc = ensure_buf(c, c->scene_buf, bytes, "host scene of %zu bytes", bytes);
+    const size_t lbytes = cs.lights.size() * sizeof(float);
+    if (!rc && lbytes) rc = ensure_buf(c, c->light_buf, lbytes, "host light table of %zu bytes", lbytes);
     if (rc) {
         if (!c->scene_buf.p) c->has_scene = false;  // the old buffer went in the attempt to grow it
         return rc;
     }
     if (c->cpu) {
         std::memcpy(c->scene_buf.p, cs.data.data(), bytes);
+        if (lbytes) std::memcpy(c->light_buf.p, cs.lights.data(), lbytes);
     } else {
         HIP_TRY(c, hipMemcpyAsync(c->scene_buf.p, cs.data.data(), bytes, hipMemcpyHostToDevice, c->stream));
+        if (lbytes) HIP_TRY(c, hipMemcpyAsync(c->light_buf.p, cs.lights.data(), lbytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     rt_sky_collect(*s, cs, c->sky_prims);
@@ -335,6 +339,27 @@ int rt_set_precision(rt_context* c, int precision) {
 }
 
 int rt_get_precision(const rt_context* c) { return c ? c->precision : RT_PRECISION_EXACT; }
+
+// Only the choice of estimator at the next render: accumulation, frame counter
+// and RNG streams stay, as with rt_set_background
+int rt_set_light_sampling(rt_context* c, int on) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (on != 0 && on != 1) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_set_light_sampling: %d is neither 0 nor 1", on);
+    c->light_sampling = on != 0;
+    return RT_OK;
+}
+
+int rt_get_light_sampling(const rt_context* c) { return c && c->light_sampling ? 1 : 0; }
+
+int rt_get_lights(rt_context* c, float* out, int capacity) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    if (capacity < 0 || (capacity > 0 && !out)) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_get_lights: bad capacity / null out");
+    const int n = (int)(c->scene.lights.size() / RT_LIGHT_FLOATS);
+    const int k = n < capacity ? n : capacity;
+    if (k > 0) std::memcpy(out, c->scene.lights.data(), (size_t)k * RT_LIGHT_FLOATS * sizeof(float));
+    return n;
+}
 
 int rt_get_camera(const rt_context* c, rt_camera* cam) {
     if (!c || !cam) return RT_ERR_INVALID_ARGUMENT;

@@ -42,7 +42,8 @@
 
 // ---- kernel launchers (the render units': rt_launch.h) ------------------------
 // scalar C++ CPU fallback (rt_cpu.cpp)
-int rt_cpu_render(const rt_kparams& K, int threads);
+// (N.n_lights > 0: the next-event estimator of rt_light.h, here and in rt_cpu_adaptive_render)
+int rt_cpu_render(const rt_kparams& K, const rt_nee_args& N, int threads);
 // adaptive sampling on the host (rt_adaptive.h): selection into A.list /
 // *A.list_n, the listed pixels' frames, their update, the resolve pass
 void rt_cpu_adaptive_select(const rt_ad_args& A, int threads);
@@ -52,7 +53,7 @@ void rt_cpu_adaptive_select_reproj(const rt_ad_reproj_args& R, int threads);
 // selection from the gathered blocks
 void rt_cpu_adaptive_rows_block(const rt_ad_args& A, long plane, int threads);
 void rt_cpu_adaptive_select_shard(const rt_ad_shard_args& S, int threads);
-void rt_cpu_adaptive_render(const rt_kparams& K, const rt_ad_args& A, int threads);
+void rt_cpu_adaptive_render(const rt_kparams& K, const rt_nee_args& N, const rt_ad_args& A, int threads);
 void rt_cpu_adaptive_finish(const rt_ad_args& A, int threads);
 void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride);
 bool rt_cpu_supported();
@@ -267,6 +268,17 @@ struct rt_context {
     int deint_blocks = 0;        // BWRT_DEINT_BLOCKS: cap on the de-interleave grid (0 = one thread per 16 bytes)
     std::string kernel_name;     // the render kernel of the last launch (rt_last_kernel_name)
     int precision = RT_PRECISION_EXACT;  // rt_set_precision (BWRT_PRECISION): which kernels the next render launches
+    // rt_set_light_sampling: the next render takes the next-event estimation kernel (rt_kernel_nee.h) or its
+    // CPU twin; light_buf holds the scene's light table (scene.lights; rt_set_scene uploads it)
+    bool light_sampling = false;
+    Buf light_buf;
+    // The light table a render at max_bounces takes, or none ({null, 0}: the default estimator, its
+    // kernels and launch policy): the switch, and a scene and a depth where the estimators differ (an
+    // empty table and max_bounces 0 are bit-identical to the default, rt_light.h)
+    rt_nee_args nee_args(int max_bounces) const {
+        if (!light_sampling || scene.lights.empty() || max_bounces <= 0) return {nullptr, 0};
+        return {light_buf.as<const float>(), (int)(scene.lights.size() / RT_LIGHT_FLOATS)};
+    }
     // the frame counter, the moment tracking and the non-uniform state: what
     // frameSum currently holds (rt_accum.h has the rules)
     rt_accum_state st;

@@ -23,6 +23,7 @@
 #include <xmmintrin.h>  // MXCSR
 #include <vector>
 
+#include "rt_light.h"
 #include "rt_path.h"
 
 namespace {
@@ -106,10 +107,74 @@ f3 trace_path(const rt_kparams& K, Xorwow& rs, f3 o, f3 d) {
     return mk(lx, ly, lz);
 }
 
+// The same path under next-event estimation (rt_light.h; the twin of
+// rt_kernel_nee.h): at a diffuse hit whose scattered ray will be traced, the
+// three draws, the direct term of the picked light through a shadow ray, and
+// the suppression of the emission the scattered ray finds on a reachable table
+// light.  N.n_lights > 0 (the caller keeps trace_path otherwise).
+f3 trace_path_nee(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d) {
+    int rec_code[RT_MAX_LEVELS], rec_aux[RT_MAX_LEVELS];
+    float rec_k[RT_MAX_LEVELS], rec_c[RT_MAX_LEVELS];
+    int depth = 0;
+    int nee_prim = -1;  // >= 0: (o, d) is the scattered ray of an NEE level on that primitive
+    auto hit = [&](f3 ro, f3 rd, float& t, int& id) {
+        if (K.bvh_nodes)
+            closest_hit_bvh_cpu(K, ro, rd, t, id);
+        else
+            closest_hit_brute(K, ro, rd, t, id);
+    };
+    while (true) {
+        float t;
+        int id;
+        hit(o, d, t, id);
+        if (id < 0) break;
+        const float* h = K.hit + RT_HIT_FLOATS * id;
+        const f3 P = add(o, scale(t, d));
+        f3 n = mk(h[0], h[1], h[2]);
+        if (h[3] != 0.0f) n = normalize3(sub(P, n));
+        int aux = 0;
+        if (nee_prim >= 0 && light_suppressed(K, N, o, nee_prim, id)) aux = RT_NEE_DROP;
+        nee_prim = -1;
+        f3 scatter;
+        int code = id;
+        float k = 0.0f;
+        if (rand_range(rs, 1.0f) < RT_SPECULAR_CHANCE) {
+            scatter = specular_scatter(rs, d, n, h[8], h[10], h[9], k);
+            code = ~id;
+        } else {
+            scatter = random_direction(rs, n);
+            const int kind = nee_normal_kind(h[3] != 0.0f, n);
+            if (depth + 1 <= K.max_bounces && N.n_lights > 0 && kind) {
+                const NeeSample s = nee_sample(rs, N, P, n, id, kind);
+                aux |= RT_NEE_LEVEL | (s.j << RT_NEE_JSHIFT);
+                k = s.k;
+                nee_prim = id;
+                if (s.trace) {
+                    float ts;
+                    int ids;
+                    hit(P, s.wi, ts, ids);
+                    if (ids == s.prim) aux |= RT_NEE_VISIBLE;
+                }
+            }
+        }
+        rec_code[depth] = code;
+        rec_k[depth] = k;
+        rec_c[depth] = dot(scatter, n);
+        rec_aux[depth] = aux;
+        depth++;
+        o = P;
+        d = scatter;
+        if (depth > K.max_bounces) break;
+    }
+    float lx = K.bg[0], ly = K.bg[1], lz = K.bg[2];
+    for (int l = depth - 1; l >= 0; --l) fold_level_nee(rec_code[l], rec_k[l], rec_c[l], rec_aux[l], K.hit, N, lx, ly, lz);
+    return mk(lx, ly, lz);
+}
+
 // Every frame of shard pixel p (Main.cu:285-312 per frame, frames in order),
 // the first one `first`: K.first_frame, or n_p + 1 of a listed pixel of an
 // adaptive call (rt_adaptive.h), whose image the resolve pass writes
-void render_pixel(const rt_kparams& K, long npix, long p, unsigned first) {
+void render_pixel(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
     const int j = (int)(p / K.width);
     const int x = (int)(p - (long)j * K.width);
     const int y = K.row_offset + j * K.row_stride;
@@ -134,8 +199,9 @@ void render_pixel(const rt_kparams& K, long npix, long p, unsigned first) {
         const f3 jit = random_direction(rs, d0);
         const f3 dcam = normalize3(add(d0, scale(K.jitter, jit)));
         // samplesPerPixel paths from it; the last one is kept (Main.cu:296-298)
-        f3 L = trace_path(K, rs, cam, dcam);
-        for (int i = 1; i < K.spp_inner; i++) L = trace_path(K, rs, cam, dcam);
+        const bool nee = N.n_lights > 0;  // rt_set_light_sampling
+        f3 L = nee ? trace_path_nee(K, N, rs, cam, dcam) : trace_path(K, rs, cam, dcam);
+        for (int i = 1; i < K.spp_inner; i++) L = nee ? trace_path_nee(K, N, rs, cam, dcam) : trace_path(K, rs, cam, dcam);
         float lx = L.x, ly = L.y, lz = L.z;
         if (K.spp_inner != 1) {  // pixel /= samplesPerPixel: (1.0f / k) * pixel (Math.cuh:91-97)
             const float k = 1.0f / (float)K.spp_inner;
@@ -193,7 +259,7 @@ void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int ro
 
 // Render K.samples frames of the shard in K (host pointers) on `threads`
 // threads (>= 1).  Returns the threads actually used.
-int rt_cpu_render(const rt_kparams& K, int threads) {
+int rt_cpu_render(const rt_kparams& K, const rt_nee_args& N, int threads) {
     const long npix = (long)K.rows * K.width;
     constexpr long kChunk = 256;
     const long chunks = (npix + kChunk - 1) / kChunk;
@@ -209,7 +275,7 @@ int rt_cpu_render(const rt_kparams& K, int threads) {
         _mm_setcsr((saved & ~(_MM_ROUND_MASK | _MM_FLUSH_ZERO_MASK | 0x0040u)) | _MM_ROUND_NEAREST);  // 0x40 = DAZ
         for (long c = next.fetch_add(1); c < chunks; c = next.fetch_add(1)) {
             const long end = (c + 1) * kChunk < npix ? (c + 1) * kChunk : npix;
-            for (long p = c * kChunk; p < end; p++) render_pixel(K, npix, p, K.first_frame);
+            for (long p = c * kChunk; p < end; p++) render_pixel(K, N, npix, p, K.first_frame);
         }
         _mm_setcsr(saved);
     };
@@ -429,10 +495,10 @@ void rt_cpu_adaptive_select_shard(const rt_ad_shard_args& S, int threads) {
 }
 
 // A.k more frames of every listed pixel, each from its own frame count
-void rt_cpu_adaptive_render(const rt_kparams& K, const rt_ad_args& A, int threads) {
+void rt_cpu_adaptive_render(const rt_kparams& K, const rt_nee_args& N, const rt_ad_args& A, int threads) {
     parallel_items((long)*A.list_n, threads, [&](long i) {
         const long p = A.list[i];
-        render_pixel(K, A.npix, p, A.cnt[p].x + 1u);
+        render_pixel(K, N, A.npix, p, A.cnt[p].x + 1u);
     });
 }
 

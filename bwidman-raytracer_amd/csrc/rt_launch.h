@@ -23,6 +23,13 @@ hipError_t rt_launch_render_list(const rt_kparams& K, const rt_list_args& L, int
 hipError_t rt_launch_render_list_bvh(const rt_kparams& K, const rt_list_args& L, int block, size_t lds, int num_cus,
                                      hipStream_t s);
 
+// ---- next-event estimation (rt_kernel_nee.h; exact units only) ------------------
+// L null: a uniform render; non-null: the list of an adaptive call
+hipError_t rt_launch_render_nee(const rt_kparams& K, const rt_nee_args& N, const rt_list_args* L, int num_cus, int grid_mult,
+                                hipStream_t s);
+hipError_t rt_launch_render_nee_bvh(const rt_kparams& K, const rt_nee_args& N, const rt_list_args* L, int block, size_t lds,
+                                    int grid_mult, int num_cus, hipStream_t s);
+
 // ---- the same in both modes (rt_kernels_shared.hip) -----------------------------
 // launch policy: hit table in LDS, 64-lane groups (very deep paths), pair
 // kernel (pair_req: 1 / 0 forces it on / off, BWRT_SPREAD; -1 the policy)

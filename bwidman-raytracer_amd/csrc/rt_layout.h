@@ -350,6 +350,18 @@ struct rt_list_args {
     const uint2* cnt;        // {n_p, J_p} per pixel: item i starts at frame n_p + 1
 };
 
+// The light table of next-event estimation (rt_light.h; rt_set_light_sampling):
+// what the NEE render kernel (rt_kernel_nee.h) and its CPU twin take besides
+// rt_kparams, whose layout they leave alone.  One record of RT_LIGHT_FLOATS per
+// sphere with finite emittance > 0 and finite radius > 0, in sphere order:
+//   {cx, cy, cz, r*r, emitted.r, emitted.g, emitted.b, primitive id as int bits}
+// (emitted = the hit table's emittance * albedo, the same floats).
+#define RT_LIGHT_FLOATS 8
+struct rt_nee_args {
+    const float* lights;
+    int n_lights;            // 0: the estimator is the default one, bit for bit
+};
+
 // One adaptive call (rt_adaptive.h) over the full width x height frame of a
 // context in the non-uniform state: the selection passes, the moment update of
 // the listed pixels and the resolve pass share it.

@@ -1,0 +1,210 @@
+// rt_light.h — next-event estimation (rt_set_light_sampling; DESIGN.md section
+// 23): the arithmetic of sampling the scene's emissive spheres at a diffuse
+// bounce, shared by the HIP kernel (rt_kernel_nee.h, device pass) and the CPU
+// twin (rt_cpu.cpp, host pass).  Not from the reference, which finds its lights
+// by chance alone.
+//
+// Exact arithmetic only, written once: one rounding per operation in the
+// written order (every includer is built with -ffp-contract=off), divisions
+// through rt_div, roots through rt_sqrt, the angle through rt_sincos, so a GPU
+// and a CPU context agree bit for bit.
+//
+// The estimator.  A diffuse bounce of the default estimator evaluates
+// 4 albedo cos L under the uniform-hemisphere pdf 1 / 2pi (rt_path.h).  At an
+// NEE LEVEL — a hit whose diffuse branch was taken, whose scattered ray will be
+// traced (depth + 1 <= max_bounces) and with a non-empty light table — the part
+// of that integral over one table light's cone, the light picked uniformly, is
+// estimated directly:
+//   direct = (n_lights * omega * cs) * (diffuse_brdf * emitted_j)
+// with omega = 1 - cos(theta_max) = Omega / 2pi, wi uniform in the cone and
+// cs = dot(wi, n), if the light is REACHABLE (the hit is not on it and lies
+// outside it), cs > 0 and the shadow ray's closest hit is the light; else 0.
+// In exchange the scattered ray of that level, when it hits a table light that
+// is reachable from the level's point, drops that hit's emitted light (the
+// direct term has counted it).  Emission is kept everywhere else.  Both
+// estimators have the same expectation.
+//
+// Non-unit normals.  The reference shades planes and polygons with their
+// un-normalised normal n (rt_path.h): random_direction's flip r - 2 (r.n) n of
+// the lower half of its ball points is then no mirror image but stretches the
+// normal component by g = 2 |n|^2 - 1, and the default estimator's expectation
+// over the upper hemisphere of unit directions u becomes
+//   (1 / 4pi) 4 albedo (u.n) [1 + 1 / (g q^2)] L(u),  q = 1 - un^2 + un^2 / g^2,
+// un = u.n / |n| (the kept half, and the stretched half through the Jacobian of
+// u = A r / |A r|, A = diag(1, 1, g)); |n| = 1 gives the 1 / 2pi above.  The
+// direct term therefore takes (cs / 2) [1 + 1 / (g q^2)] in place of cs on such
+// a surface; sphere normals are normalised and |n|^2 == 1 keeps cs itself.
+// With |n|^2 <= 1/2 (g <= 0: the flip leaves directions below the surface) or
+// NaN a hit is no NEE level.
+//
+// Draws at an NEE level, behind random_direction's: the light pick, u1, u2 —
+// always all three, so the draws do not depend on geometry.
+//
+// Record of a level (four dwords): code, k, cosAngle as the default kernels',
+// and aux; a diffuse level does not use k for a specular scalar, so an NEE
+// level keeps n_lights * omega * cs there.
+#pragma once
+#include "rt_path.h"
+
+// aux of a level's record
+#define RT_NEE_DROP 1     // this hit's emitted light is suppressed
+#define RT_NEE_LEVEL 2    // an NEE level: the fold adds the direct term (possibly 0)
+#define RT_NEE_VISIBLE 4  // the direct term is not 0: the shadow ray reached light j
+#define RT_NEE_JSHIFT 3   // light j from bit 3 up
+
+namespace {
+
+struct LightRec {
+    f3 c;
+    float r2;
+    f3 e;
+    int prim;
+};
+
+RT_HD LightRec light_load(const float* lights, int j) {
+    const float4 a = *reinterpret_cast<const float4*>(lights + RT_LIGHT_FLOATS * (size_t)j);
+    const float4 b = *reinterpret_cast<const float4*>(lights + RT_LIGHT_FLOATS * (size_t)j + 4);
+    LightRec l;
+    l.c = mk(a.x, a.y, a.z);
+    l.r2 = a.w;
+    l.e = mk(b.x, b.y, b.z);
+    l.prim = rt_f2i(b.w);
+    return l;
+}
+
+// A point P on primitive `prim` can be lit by the light through its cone: P is
+// not on the light and lies outside it.  w = C - P, d2 = |w|^2.  The sampling
+// and the suppression both ask this one function.
+RT_HD bool light_reachable(f3 P, int prim, const LightRec& l, f3& w, float& d2) {
+    w = sub(l.c, P);
+    d2 = dot(w, w);
+    return prim != l.prim && d2 > l.r2;
+}
+
+// The table index of sphere `prim`, -1 if it is no table light (records are in
+// sphere order: the ids ascend)
+RT_HD int light_of_prim(const rt_nee_args& N, int prim) {
+    int lo = 0, hi = N.n_lights - 1;
+    while (lo <= hi) {
+        const int mid = (lo + hi) >> 1;
+        const int id = rt_f2i(N.lights[RT_LIGHT_FLOATS * (size_t)mid + 7]);
+        if (id == prim) return mid;
+        if (id < prim)
+            lo = mid + 1;
+        else
+            hi = mid - 1;
+    }
+    return -1;
+}
+
+// Suppression: the scattered ray of an NEE level at P on `prim` hit primitive
+// `id`; true when that hit's emitted light is to be dropped
+RT_HD bool light_suppressed(const rt_kparams& K, const rt_nee_args& N, f3 P, int prim, int id) {
+    if (id >= K.n_sph) return false;
+    const int m = light_of_prim(N, id);
+    if (m < 0) return false;
+    f3 w;
+    float d2;
+    return light_reachable(P, prim, light_load(N.lights, m), w, d2);
+}
+
+// Whether a hit with normal n can be an NEE level, and how its direct term
+// weighs the cosine: 0 not at all, 1 by cs (unit normal), 2 by the stretched form
+RT_HD int nee_normal_kind(bool sphere, f3 n) {
+    if (sphere) return 1;
+    const float s = dot(n, n);
+    if (s == 1.0f) return 1;
+    return s > 0.5f && s < INFINITY ? 2 : 0;
+}
+
+// The three draws of an NEE level and the sample they give at P (normal n as
+// the path has it, on primitive `prim`): light j, and, when `trace`, the shadow
+// ray's direction wi, the weight k = n_lights * omega * cs (kind 2: the stretched form of cs) and the id the shadow
+// ray must return.  !trace: the direct term is 0 without a shadow ray.
+struct NeeSample {
+    int j, prim;
+    bool trace;
+    float k;
+    f3 wi;
+};
+
+RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int prim, int kind) {
+    const float u = rand_range(rs, 1.0f);
+    const float u1 = rand_range(rs, 1.0f);
+    const float u2 = rand_range(rs, 1.0f);
+    const float nf = (float)N.n_lights;
+    NeeSample s;
+    s.j = (int)(u * nf);
+    if (s.j > N.n_lights - 1) s.j = N.n_lights - 1;
+    s.trace = false;
+    s.k = 0.0f;
+    s.wi = mk(0.0f, 0.0f, 0.0f);
+    const LightRec l = light_load(N.lights, s.j);
+    s.prim = l.prim;
+    f3 w;
+    float d2;
+    if (!light_reachable(P, prim, l, w, d2)) return s;
+    const float s2 = rt_div(l.r2, d2);
+    const float cm = rt_sqrt(1.0f - s2);
+    const float omega = rt_div(s2, 1.0f + cm);  // 1 - cos(theta_max) without the cancellation
+    const float ct = 1.0f - u1 * omega;
+    const float st = rt_sqrt(fmaxf(0.0f, 1.0f - ct * ct));
+    const float phi = 2.0f * RT_PI * u2;
+    float sp, cp;
+    rt_sincos(phi, sp, cp);
+    const f3 loc = mk(st * cp, st * sp, ct);
+    // frame around the axis, combined as specular_scatter combines its own; the
+    // tangents here are orthonormal (a cone-uniform wi of unit length needs
+    // them so: specular_scatter's cross products are not normalised, and its
+    // helper axis is parallel to a y-aligned normal)
+    const f3 a = normalize3(w);
+    f3 some = mk(1.0f, 0.0f, 0.0f);
+    if (fabsf(a.x) > 0.9f) some = mk(0.0f, 1.0f, 0.0f);
+    const f3 t1 = normalize3(cross(a, some));
+    const f3 t2 = cross(a, t1);
+    s.wi = mk(dot(mk(t1.x, t2.x, a.x), loc), dot(mk(t1.y, t2.y, a.y), loc), dot(mk(t1.z, t2.z, a.z), loc));
+    const float cs = dot(s.wi, n);
+    if (!(cs > 0.0f)) return s;
+    float wc = cs;
+    if (kind == 2) {
+        const float nn = dot(n, n);
+        const float g = 2.0f * nn - 1.0f;
+        const float un2 = rt_div(cs * cs, nn);
+        const float q = (1.0f - un2) + rt_div(un2, g * g);
+        wc = (0.5f * cs) * (1.0f + rt_div(1.0f, g * (q * q)));
+    }
+    s.k = (nf * omega) * wc;
+    s.trace = true;
+    return s;
+}
+
+// fold_level (rt_path.h) with the level's aux: innermost-first
+//   L = (keep ? emitted : 0) [+ direct] + (brdf * L) * cosAngle
+// aux = 0 is fold_level's own expression.
+RT_HD void fold_level_nee(int c0, float k, float c, int aux, const float* hit_tab, const rt_nee_args& N, float& lx,
+                          float& ly, float& lz) {
+    const bool spec = c0 < 0;
+    const float* h = hit_tab + RT_HIT_FLOATS * (spec ? ~c0 : c0);
+    const float4 e = *reinterpret_cast<const float4*>(h + 4);
+    const float4 da = *reinterpret_cast<const float4*>(h + 12);
+    const float bx = spec ? k : da.x, by = spec ? k : da.y, bz = spec ? k : da.z;
+    float ex = e.x, ey = e.y, ez = e.z;
+    if (aux & RT_NEE_DROP) ex = ey = ez = 0.0f;
+    if (aux & RT_NEE_LEVEL) {
+        float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+        if (aux & RT_NEE_VISIBLE) {
+            const float4 le = *reinterpret_cast<const float4*>(N.lights + RT_LIGHT_FLOATS * (size_t)(aux >> RT_NEE_JSHIFT) + 4);
+            dx = k * (da.x * le.x);
+            dy = k * (da.y * le.y);
+            dz = k * (da.z * le.z);
+        }
+        ex = ex + dx;
+        ey = ey + dy;
+        ez = ez + dz;
+    }
+    lx = ex + (bx * lx) * c;
+    ly = ey + (by * ly) * c;
+    lz = ez + (bz * lz) * c;
+}
+
+}  // namespace

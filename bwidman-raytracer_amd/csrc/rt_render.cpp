@@ -20,6 +20,10 @@ static int prepare(rt_context* c, const rt_render_params* p, rt_kparams& K, unsi
     if (p->max_bounces < 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "max_bounces < 0");
     if (p->max_bounces > RT_MAX_BOUNCES)
         return fail(c, RT_ERR_UNSUPPORTED, "max_bounces %d > %d", p->max_bounces, RT_MAX_BOUNCES);
+    if (c->light_sampling && c->precision == RT_PRECISION_REFERENCE_FAST)
+        return fail(c, RT_ERR_UNSUPPORTED,
+                    "light sampling (rt_set_light_sampling) is not available in RT_PRECISION_REFERENCE_FAST (its "
+                    "estimator is specified in exact arithmetic only)");
     if (c->width != p->width || c->height != p->height || c->row_offset != p->row_offset ||
         c->row_stride != stride || !c->rng.p) {
         int rc = rt_init_rand(c, p->width, p->height, p->row_offset, stride);
@@ -141,7 +145,7 @@ static int cpu_render(rt_context* c, const rt_render_params* p, int threads, uin
     bool track = false;
     if ((rc = moments_prepare(c, first, p->samples, MA, track))) return rc;
     (void)c->render.begin(nullptr, true);
-    rt_cpu_render(K, threads > 0 ? threads : c->threads);
+    rt_cpu_render(K, c->nee_args(K.max_bounces), threads > 0 ? threads : c->threads);
     if (track) rt_cpu_moments(MA, threads > 0 ? threads : c->threads);
     (void)c->render.end(nullptr);
     c->st.uniform_done(first, p->samples, track);
@@ -201,13 +205,17 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     // ends with the slowest waves) batch later
     K.leaf_batch = c->leaf_batch > 0 ? c->leaf_batch : small ? RT_LEAF_BATCH_SMALL : RT_LEAF_BATCH;
     K.refill = c->refill > 0 ? c->refill : small ? RT_REFILL_SMALL : RT_REFILL;
+    // next-event estimation: its own kernel (rt_kernel_nee.h), which takes no
+    // global records, no launch-order feedback and no sky table
+    const rt_nee_args N = c->nee_args(K.max_bounces);
+    const bool nee = N.n_lights > 0;
     // deep paths: the sorted kernel's record stack in global memory (launch policy)
     K.rec = nullptr;
     // the render units of the precision mode
     const bool fast = c->precision == RT_PRECISION_REFERENCE_FAST;
     const auto wants_global_records = fast ? rt_fast::rt_render_wants_global_records : rt_render_wants_global_records;
     const auto launch_render = fast ? rt_fast::rt_launch_render : rt_launch_render;
-    if (!c->simple && (c->grec == 1 || (c->grec < 0 && wants_global_records(K, c->num_cus)))) {
+    if (!c->simple && !nee && (c->grec == 1 || (c->grec < 0 && wants_global_records(K, c->num_cus)))) {
         const int rc = ensure_buf(c, c->rec, rt_render_rec_floats(K) * sizeof(float));
         if (rc) return rc;
         K.rec = c->rec.as<float>();
@@ -228,7 +236,7 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     }
     // launch-order feedback: room for a grid of 64-lane groups over the
     // padded wave tiles (any block size needs fewer groups)
-    if (c->order_feedback && !c->simple) {
+    if (c->order_feedback && !c->simple && !nee) {
         const size_t cap = ((size_t)K.width + 128) * ((size_t)K.rows + 128) / 64 + 1;  // tiles padded to 2 x 2
         const void* before = c->gorder.p;
         int rc = ensure_buf(c, c->gcost, cap * sizeof(unsigned));
@@ -257,7 +265,7 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     // unchanged view costs the key compare; a view's first launch goes without
     // a table (rt_context.h sky_eager), its second builds and uploads one
     // ahead of the kernel on its stream
-    bool sky = c->sky_on && rt_render_takes_sorted(K, c->num_cus, c->simple, c->block, c->spread);
+    bool sky = !nee && c->sky_on && rt_render_takes_sorted(K, c->num_cus, c->simple, c->block, c->spread);
     if (sky && !c->sky_eager) {
         const rt_context::SkyKey k = sky_key_of(c, K);
         if (!(k == c->sky_key) && !(k == c->sky_seen)) {
@@ -282,7 +290,8 @@ static int launch(rt_context* c, rt_kparams& K, hipStream_t s, unsigned first, i
     // the start marker only with kernel timing on; the one end event serves
     // both the ordering of later calls and the timing (Pass::end)
     HIP_TRY(c, c->render.begin(s, c->ktiming));
-    hipError_t e = launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread);
+    hipError_t e = nee ? rt_launch_render_nee(K, N, nullptr, c->num_cus, c->grid_mult, s)
+                       : launch_render(K, c->num_cus, c->grid_mult, c->simple, c->block, s, c->spread);
     if (e == hipSuccess && rt_order_groups_last > 0) c->order_n = rt_order_groups_last;
     c->kernel_name = rt_launched_kernel;
     c->launches++;

@@ -175,7 +175,7 @@ int cpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, fl
     else
         rt_cpu_adaptive_select(A, c->threads);
     const auto t1 = clock::now();
-    rt_cpu_adaptive_render(K, A, c->threads);
+    rt_cpu_adaptive_render(K, c->nee_args(K.max_bounces), A, c->threads);
     const auto t2 = clock::now();
     rt_cpu_adaptive_finish(A, c->threads);
     const auto t3 = clock::now();
@@ -202,7 +202,8 @@ int gpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, un
     rt_kparams K;
     kparams(c, p->samples, max_bounces, K);
     const int which = c->ad_kernel;
-    if (rt_render_list_queued(K, which) && (c->grec == 1 || (c->grec < 0 && rt_render_wants_global_records(K, c->num_cus)))) {
+    const rt_nee_args N = c->nee_args(K.max_bounces);  // a table: the list render is the NEE kernel's
+    if (!N.n_lights && rt_render_list_queued(K, which) && (c->grec == 1 || (c->grec < 0 && rt_render_wants_global_records(K, c->num_cus)))) {
         if (const int rc = ensure_buf(c, c->rec, rt_render_rec_floats(K) * sizeof(float))) return rc;
         K.rec = c->rec.as<float>();
     }
@@ -225,7 +226,8 @@ int gpu_adaptive(rt_context* c, const rt_adaptive_params* p, int max_bounces, un
     }
     if (e == hipSuccess && timed) e = hipEventRecord(c->ad_ev[1], s);
     const rt_list_args L = {A.list, A.list_n, A.cnt};
-    if (e == hipSuccess) e = rt_launch_render_list(K, L, c->num_cus, which, s);
+    if (e == hipSuccess)
+        e = N.n_lights ? rt_launch_render_nee(K, N, &L, c->num_cus, 0, s) : rt_launch_render_list(K, L, c->num_cus, which, s);
     c->kernel_name = rt_launched_kernel;
     if (e == hipSuccess && timed) e = hipEventRecord(c->ad_ev[2], s);
     if (e == hipSuccess) e = rt_launch_adaptive(A, 2, s);

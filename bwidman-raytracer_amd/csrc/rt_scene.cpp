@@ -700,6 +700,12 @@ int rt_compile_scene(const rt_scene& scene, const rt_scene_options& opt, rt_comp
         hh[2] = sp.position.z;
         hh[3] = 1.0f;  // sphere: normal = normalize(P - centre)
         put_material(hh, sp.mat);
+        // light table (rt_layout.h rt_nee_args): emitted as the hit table has it
+        if (std::isfinite(sp.mat.emittance) && sp.mat.emittance > 0.0f && std::isfinite(sp.radius) && sp.radius > 0.0f) {
+            float rec[RT_LIGHT_FLOATS] = {q[0], q[1], q[2], q[3], hh[4], hh[5], hh[6], 0.0f};
+            std::memcpy(&rec[7], &id, 4);
+            r.lights.insert(r.lights.end(), rec, rec + RT_LIGHT_FLOATS);
+        }
     }
     for (int i = 0; i < np; i++, id++) {  // Intersection.cuh:69,83
         const rt_plane& pl = s->planes[i];

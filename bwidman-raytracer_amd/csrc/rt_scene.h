@@ -40,6 +40,9 @@ struct rt_compiled_scene {
     int bvh_order_mask = 7;
     float cull_omax = 0.0f, cull_dmax = -1.0f;          // polygon culling bounds (rt_layout.h)
     float ovf_sc = 0.0f, ovf_nm = 0.0f, ovf_im = 0.0f;  // overflow bounds (rt_layout.h)
+    // light table of next-event estimation (rt_layout.h rt_nee_args): RT_LIGHT_FLOATS per emissive sphere;
+    // not part of `data` (a buffer of its own on the context)
+    std::vector<float> lights;
 };
 
 // RT_OK, or RT_ERR_UNSUPPORTED with the reason in err; `out` is written only on

@@ -34,6 +34,9 @@
 // accumulatedFrames * samplesPerPixel like Main.cu:491.  --precision fast
 // renders with the reference's fast-math trade-off (rt_set_precision: GPU
 // only; the default, exact, is bit-identical to the CPU fallback).
+// --light-sampling turns next-event estimation on (rt_set_light_sampling): every
+// render call, the adaptive ones included, samples the emissive spheres at its
+// diffuse bounces; it combines with every other flag but --precision fast.
 // --denoise [N] filters the final frame with rt_denoise (N a-trous levels,
 // default rt_denoise_params_default(); the --sigma-* flags replace its
 // sigmas): the file from --out is then the denoised frame.
@@ -112,7 +115,8 @@ static const char* kUsage =
     "usage: bwrt_render [--scene 07|01|04|04_box | --scene-file FILE] [--save-scene FILE]\n"
     "                   [--width 1920] [--height 1080] [--frames 8] [--frames-per-call 1]\n"
     "                   [--max-bounces 5] [--background r,g,b] [--spp 1] [--device 0] [--gpus 1]\n"
-    "                   [--cpu [THREADS]] [--precision exact|fast] [--keys \"W*10,W+LEFT*5,*3\"]\n"
+    "                   [--cpu [THREADS]] [--precision exact|fast] [--light-sampling]\n"
+    "                   [--keys \"W*10,W+LEFT*5,*3\"]\n"
     "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n"
     "                   [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]\n"
     "                   [--temporal] [--max-history F] [--normal-cos F] [--plane-tol F]\n"
@@ -179,6 +183,7 @@ int main(int argc, char** argv) {
     int width = 1920, height = 1080, frames = 8, per_call = 1, max_bounces = RT_DEFAULT_MAX_BOUNCES, device = 0;
     int gpus = 1, spp = 1, cpu_threads = -1;  // -1: GPU
     int precision = RT_PRECISION_EXACT;
+    bool light_sampling = false;
     float bg[3] = {0.0f, 0.0f, 0.0f};
     double fixed_dt = -1.0;
     bool denoise = false;
@@ -230,6 +235,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (!std::strcmp(argv[i], "--light-sampling")) light_sampling = true;
         else if (!std::strcmp(argv[i], "--keys")) keys_spec = next();
         else if (!std::strcmp(argv[i], "--dt")) fixed_dt = std::atof(next());
         else if (!std::strcmp(argv[i], "--out")) out = next();
@@ -286,6 +292,10 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "unknown option %s\n%s", argv[i], kUsage);
             return 2;
         }
+    }
+    if (light_sampling && precision == RT_PRECISION_REFERENCE_FAST) {
+        std::fprintf(stderr, "--light-sampling cannot be combined with --precision fast: its estimator is exact arithmetic only\n");
+        return 2;
     }
     if (denoise && denoise_var) {
         std::fprintf(stderr, "--denoise and --denoise-var cannot be combined: one filter writes the frame\n");
@@ -376,6 +386,7 @@ int main(int argc, char** argv) {
             return die(ctxs[g], rc, "rt_create");
         }
         if ((rc = rt_set_precision(ctxs[g], precision))) return die(ctxs[g], rc, "rt_set_precision");
+        if ((rc = rt_set_light_sampling(ctxs[g], light_sampling ? 1 : 0))) return die(ctxs[g], rc, "rt_set_light_sampling");
         if ((rc = rt_set_samples_per_pixel(ctxs[g], spp))) return die(ctxs[g], rc, "rt_set_samples_per_pixel");
         if ((rc = rt_set_scene(ctxs[g], &view))) return die(ctxs[g], rc, "rt_set_scene");
         if ((rc = rt_set_max_bounces(ctxs[g], max_bounces))) return die(ctxs[g], rc, "rt_set_max_bounces");

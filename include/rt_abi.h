@@ -265,6 +265,35 @@ typedef enum rt_precision { RT_PRECISION_EXACT = 0, RT_PRECISION_REFERENCE_FAST 
 RT_API int rt_set_precision(rt_context* ctx, int precision);
 RT_API int rt_get_precision(const rt_context* ctx);
 
+/* Next-event estimation: with the switch on (1; 0 the
+ * default, everything as without it) the render calls — rt_render*, shards,
+ * BVH scenes, and the rt_render_adaptive* family's list renders — sample the
+ * scene's emissive spheres directly at every diffuse bounce whose scattered ray
+ * will be traced, and in exchange drop the emission such a scattered ray finds
+ * on a light it could have sampled.  It is another estimator of the same
+ * expectation with far less noise where small lights dominate; GPU and CPU
+ * contexts agree bit for bit.  With an empty light table, or max_bounces 0, a
+ * render is bit-identical to the default estimator's.
+ * Frames of both estimators may share one accumulation: both are unbiased for
+ * the same value.  Moment tracking (rt_set_moments) assumes equally noisy
+ * frames, so restart the accumulation when toggling while tracking.
+ * Per context; takes effect at the next render; resets neither the
+ * accumulation, nor the frame counter, nor the RNG streams.  Values other than
+ * 0 / 1 return RT_ERR_INVALID_ARGUMENT.  With RT_PRECISION_REFERENCE_FAST and
+ * the switch on (set in either order), render calls return RT_ERR_UNSUPPORTED
+ * and touch nothing. */
+RT_API int rt_set_light_sampling(rt_context* ctx, int on);
+RT_API int rt_get_light_sampling(const rt_context* ctx);
+/* The light table the scene compiler built at rt_set_scene: one record of
+ * RT_LIGHT_RECORD_FLOATS floats per sphere with finite emittance > 0 and finite
+ * radius > 0, in sphere order: {cx, cy, cz, r*r, emitted.r, emitted.g,
+ * emitted.b, primitive id as int32 bits}, emitted = emittance * albedo.  (Other
+ * emitters are found by chance as ever.)  Returns the number of records (or a
+ * negative error) and copies at most `capacity` of them to `out` (may be null
+ * with capacity 0). */
+#define RT_LIGHT_RECORD_FLOATS 8
+RT_API int rt_get_lights(rt_context* ctx, float* out, int capacity);
+
 /* samplesPerPixel (Main.cu:27, a compile-time constant 1 there): each
  * progressive frame traces n paths from the frame's one jittered camera ray
  * and, like the reference's loop (Main.cu:296-299, `pixel = tracePath(...)`
