@@ -65,58 +65,20 @@ void closest_hit_bvh_cpu(const rt_kparams& K, f3 o, f3 d, float& best_t, int& be
 }
 
 // One path from (o, d) (tracePath, Main.cu:208-272, iteratively): the
-// per-level records, folded innermost-first into the returned radiance
-f3 trace_path(const rt_kparams& K, Xorwow& rs, f3 o, f3 d) {
-    // recursion records (code, kspec, cosAngle): at most max_bounces + 1 hits
+// per-level records, folded innermost-first into the returned radiance; the
+// twin of rt_kernel_lane.h's lane_loop, statement for statement.
+// NEE: next-event estimation (rt_light.h) — at a diffuse hit whose scattered
+// ray will be traced, the three draws, the direct term of the picked light
+// through a shadow ray, and the suppression of the emission the scattered ray
+// finds on a reachable table light.  The caller takes NEE iff N.n_lights > 0.
+template <bool NEE>
+f3 trace_path(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d) {
+    // recursion records (code, k, cosAngle; NEE: aux): at most max_bounces + 1 hits
     int rec_code[RT_MAX_LEVELS];
     float rec_k[RT_MAX_LEVELS], rec_c[RT_MAX_LEVELS];
+    [[maybe_unused]] int rec_aux[NEE ? RT_MAX_LEVELS : 1];
     int depth = 0;
-    while (true) {
-        float t;
-        int id;
-        if (K.bvh_nodes)
-            closest_hit_bvh_cpu(K, o, d, t, id);
-        else
-            closest_hit_brute(K, o, d, t, id);
-        if (id < 0) break;  // miss: backgroundColor (Main.cu:269-271)
-        // shade (Main.cu:237-264)
-        const float* h = K.hit + RT_HIT_FLOATS * id;
-        const f3 P = add(o, scale(t, d));
-        f3 n = mk(h[0], h[1], h[2]);
-        if (h[3] != 0.0f) n = normalize3(sub(P, n));  // sphere: centre -> normal
-        f3 scatter;
-        int code = id;
-        float kspec = 0.0f;
-        if (rand_range(rs, 1.0f) < RT_SPECULAR_CHANCE) {  // brdfChoice (Main.cu:243)
-            scatter = specular_scatter(rs, d, n, h[8], h[10], h[9], kspec);
-            code = ~id;
-        } else {
-            scatter = random_direction(rs, n);  // brdf = 4 * albedo
-        }
-        rec_code[depth] = code;
-        rec_k[depth] = kspec;
-        rec_c[depth] = dot(scatter, n);  // cosAngle, Main.cu:264
-        depth++;
-        o = P;
-        d = scatter;
-        if (depth > K.max_bounces) break;  // the next call returns background (Main.cu:210)
-    }
-    // fold the recursion innermost-first (Main.cu:262-268)
-    float lx = K.bg[0], ly = K.bg[1], lz = K.bg[2];
-    for (int l = depth - 1; l >= 0; --l) fold_level(rec_code[l], rec_k[l], rec_c[l], K.hit, lx, ly, lz);
-    return mk(lx, ly, lz);
-}
-
-// The same path under next-event estimation (rt_light.h; the twin of
-// rt_kernel_nee.h): at a diffuse hit whose scattered ray will be traced, the
-// three draws, the direct term of the picked light through a shadow ray, and
-// the suppression of the emission the scattered ray finds on a reachable table
-// light.  N.n_lights > 0 (the caller keeps trace_path otherwise).
-f3 trace_path_nee(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d) {
-    int rec_code[RT_MAX_LEVELS], rec_aux[RT_MAX_LEVELS];
-    float rec_k[RT_MAX_LEVELS], rec_c[RT_MAX_LEVELS];
-    int depth = 0;
-    int nee_prim = -1;  // >= 0: (o, d) is the scattered ray of an NEE level on that primitive
+    [[maybe_unused]] int nee_prim = -1;  // >= 0: (o, d) is the scattered ray of an NEE level on that primitive
     auto hit = [&](f3 ro, f3 rd, float& t, int& id) {
         if (K.bvh_nodes)
             closest_hit_bvh_cpu(K, ro, rd, t, id);
@@ -127,54 +89,66 @@ f3 trace_path_nee(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f
         float t;
         int id;
         hit(o, d, t, id);
-        if (id < 0) break;
+        if (id < 0) break;  // miss: backgroundColor (Main.cu:269-271)
+        // shade (Main.cu:237-264)
         const float* h = K.hit + RT_HIT_FLOATS * id;
         const f3 P = add(o, scale(t, d));
         f3 n = mk(h[0], h[1], h[2]);
-        if (h[3] != 0.0f) n = normalize3(sub(P, n));
-        int aux = 0;
-        if (nee_prim >= 0 && light_suppressed(K, N, o, nee_prim, id)) aux = RT_NEE_DROP;
-        nee_prim = -1;
+        if (h[3] != 0.0f) n = normalize3(sub(P, n));  // sphere: centre -> normal
+        [[maybe_unused]] int aux = 0;
+        if constexpr (NEE) {
+            if (nee_prim >= 0 && light_suppressed(K, N, o, nee_prim, id)) aux = RT_NEE_DROP;
+            nee_prim = -1;
+        }
         f3 scatter;
         int code = id;
-        float k = 0.0f;
-        if (rand_range(rs, 1.0f) < RT_SPECULAR_CHANCE) {
+        float k = 0.0f;  // specular brdf scalar, or an NEE level's weight
+        if (rand_range(rs, 1.0f) < RT_SPECULAR_CHANCE) {  // brdfChoice (Main.cu:243)
             scatter = specular_scatter(rs, d, n, h[8], h[10], h[9], k);
             code = ~id;
         } else {
-            scatter = random_direction(rs, n);
-            const int kind = nee_normal_kind(h[3] != 0.0f, n);
-            if (depth + 1 <= K.max_bounces && N.n_lights > 0 && kind) {
-                const NeeSample s = nee_sample(rs, N, P, n, id, kind);
-                aux |= RT_NEE_LEVEL | (s.j << RT_NEE_JSHIFT);
-                k = s.k;
-                nee_prim = id;
-                if (s.trace) {
-                    float ts;
-                    int ids;
-                    hit(P, s.wi, ts, ids);
-                    if (ids == s.prim) aux |= RT_NEE_VISIBLE;
+            scatter = random_direction(rs, n);  // brdf = 4 * albedo
+            if constexpr (NEE) {
+                const int kind = nee_normal_kind(h[3] != 0.0f, n);
+                if (depth + 1 <= K.max_bounces && N.n_lights > 0 && kind) {
+                    const NeeSample s = nee_sample(rs, N, P, n, id, kind);
+                    aux |= RT_NEE_LEVEL | (s.j << RT_NEE_JSHIFT);
+                    k = s.k;
+                    nee_prim = id;
+                    if (s.trace) {
+                        float ts;
+                        int ids;
+                        hit(P, s.wi, ts, ids);
+                        if (ids == s.prim) aux |= RT_NEE_VISIBLE;
+                    }
                 }
             }
         }
         rec_code[depth] = code;
         rec_k[depth] = k;
-        rec_c[depth] = dot(scatter, n);
-        rec_aux[depth] = aux;
+        rec_c[depth] = dot(scatter, n);  // cosAngle, Main.cu:264
+        if constexpr (NEE) rec_aux[depth] = aux;
         depth++;
         o = P;
         d = scatter;
-        if (depth > K.max_bounces) break;
+        if (depth > K.max_bounces) break;  // the next call returns background (Main.cu:210)
     }
+    // fold the recursion innermost-first (Main.cu:262-268)
     float lx = K.bg[0], ly = K.bg[1], lz = K.bg[2];
-    for (int l = depth - 1; l >= 0; --l) fold_level_nee(rec_code[l], rec_k[l], rec_c[l], rec_aux[l], K.hit, N, lx, ly, lz);
+    for (int l = depth - 1; l >= 0; --l) {
+        if constexpr (NEE)
+            fold_level_nee(rec_code[l], rec_k[l], rec_c[l], rec_aux[l], K.hit, N, lx, ly, lz);
+        else
+            fold_level(rec_code[l], rec_k[l], rec_c[l], K.hit, lx, ly, lz);
+    }
     return mk(lx, ly, lz);
 }
 
 // Every frame of shard pixel p (Main.cu:285-312 per frame, frames in order),
 // the first one `first`: K.first_frame, or n_p + 1 of a listed pixel of an
 // adaptive call (rt_adaptive.h), whose image the resolve pass writes
-void render_pixel(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
+template <bool NEE>
+void render_pixel_as(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
     const int j = (int)(p / K.width);
     const int x = (int)(p - (long)j * K.width);
     const int y = K.row_offset + j * K.row_stride;
@@ -199,9 +173,8 @@ void render_pixel(const rt_kparams& K, const rt_nee_args& N, long npix, long p, 
         const f3 jit = random_direction(rs, d0);
         const f3 dcam = normalize3(add(d0, scale(K.jitter, jit)));
         // samplesPerPixel paths from it; the last one is kept (Main.cu:296-298)
-        const bool nee = N.n_lights > 0;  // rt_set_light_sampling
-        f3 L = nee ? trace_path_nee(K, N, rs, cam, dcam) : trace_path(K, rs, cam, dcam);
-        for (int i = 1; i < K.spp_inner; i++) L = nee ? trace_path_nee(K, N, rs, cam, dcam) : trace_path(K, rs, cam, dcam);
+        f3 L = trace_path<NEE>(K, N, rs, cam, dcam);
+        for (int i = 1; i < K.spp_inner; i++) L = trace_path<NEE>(K, N, rs, cam, dcam);
         float lx = L.x, ly = L.y, lz = L.z;
         if (K.spp_inner != 1) {  // pixel /= samplesPerPixel: (1.0f / k) * pixel (Math.cuh:91-97)
             const float k = 1.0f / (float)K.spp_inner;
@@ -230,6 +203,52 @@ void render_pixel(const rt_kparams& K, const rt_nee_args& N, long npix, long p, 
     K.accum[1 * npix + p] = ay;
     K.accum[2 * npix + p] = az;
     if (K.rgba) K.rgba[p] = tone_map(ax, ay, az, frame - 1u);
+}
+
+// (the estimator is picked once per pixel: rt_set_light_sampling)
+void render_pixel(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
+    if (N.n_lights > 0)
+        render_pixel_as<true>(K, N, npix, p, first);
+    else
+        render_pixel_as<false>(K, N, npix, p, first);
+}
+
+// fn(p) for p = 0 .. n-1 in 256-item chunks, which `threads` threads (>= 1; the
+// calling thread works too) take from an atomic counter; returns the threads
+// used when all are done (the barrier between two filter levels).  Every item
+// writes only its own outputs, so the result does not depend on the thread count.
+template <class Fn>
+int parallel_items(long n, int threads, const Fn& fn) {
+    constexpr long kChunk = 256;
+    const long chunks = (n + kChunk - 1) / kChunk;
+    if (threads < 1) threads = 1;
+    if ((long)threads > chunks) threads = (int)(chunks > 0 ? chunks : 1);
+    std::atomic<long> next(0);
+    auto work = [&]() {
+        // IEEE float state for the whole pass, whatever the calling thread
+        // holds (a -ffast-math library or torch.set_flush_denormal may have
+        // set FTZ / DAZ, and new threads inherit it): round to nearest, no
+        // denormal flushing — the GPU keeps f32 denormals — restored after
+        const unsigned saved = _mm_getcsr();
+        _mm_setcsr((saved & ~(_MM_ROUND_MASK | _MM_FLUSH_ZERO_MASK | 0x0040u)) | _MM_ROUND_NEAREST);  // 0x40 = DAZ
+        for (long c = next.fetch_add(1); c < chunks; c = next.fetch_add(1)) {
+            const long end = (c + 1) * kChunk < n ? (c + 1) * kChunk : n;
+            for (long p = c * kChunk; p < end; p++) fn(p);
+        }
+        _mm_setcsr(saved);
+    };
+    std::vector<std::thread> pool;
+    pool.reserve((size_t)threads - 1);
+    for (int t = 1; t < threads; t++) {
+        try {
+            pool.emplace_back(work);
+        } catch (...) {  // no more threads: the ones running (and this one) finish the work
+            break;
+        }
+    }
+    work();
+    for (std::thread& t : pool) t.join();
+    return (int)pool.size() + 1;
 }
 
 }  // namespace
@@ -261,36 +280,7 @@ void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int ro
 // threads (>= 1).  Returns the threads actually used.
 int rt_cpu_render(const rt_kparams& K, const rt_nee_args& N, int threads) {
     const long npix = (long)K.rows * K.width;
-    constexpr long kChunk = 256;
-    const long chunks = (npix + kChunk - 1) / kChunk;
-    if (threads < 1) threads = 1;
-    if ((long)threads > chunks) threads = (int)(chunks > 0 ? chunks : 1);
-    std::atomic<long> next(0);
-    auto work = [&]() {
-        // IEEE float state for the whole render, whatever the calling thread
-        // holds (a -ffast-math library or torch.set_flush_denormal may have
-        // set FTZ / DAZ, and new threads inherit it): round to nearest, no
-        // denormal flushing — the GPU keeps f32 denormals — restored after
-        const unsigned saved = _mm_getcsr();
-        _mm_setcsr((saved & ~(_MM_ROUND_MASK | _MM_FLUSH_ZERO_MASK | 0x0040u)) | _MM_ROUND_NEAREST);  // 0x40 = DAZ
-        for (long c = next.fetch_add(1); c < chunks; c = next.fetch_add(1)) {
-            const long end = (c + 1) * kChunk < npix ? (c + 1) * kChunk : npix;
-            for (long p = c * kChunk; p < end; p++) render_pixel(K, N, npix, p, K.first_frame);
-        }
-        _mm_setcsr(saved);
-    };
-    std::vector<std::thread> pool;
-    pool.reserve((size_t)threads - 1);
-    for (int t = 1; t < threads; t++) {
-        try {
-            pool.emplace_back(work);
-        } catch (...) {  // no more threads: the ones running (and this one) finish the work
-            break;
-        }
-    }
-    work();
-    for (std::thread& t : pool) t.join();
-    return (int)pool.size() + 1;
+    return parallel_items(npix, threads, [&](long p) { render_pixel(K, N, npix, p, K.first_frame); });
 }
 
 // ---- first-hit features and the a-trous filter on the host -------------------
@@ -301,39 +291,6 @@ int rt_cpu_render(const rt_kparams& K, const rt_nee_args& N, int threads) {
 #include "rt_temporal_var.h"
 
 namespace {
-
-// fn(p) for p = 0 .. n-1 in 256-item chunks on `threads` threads (the calling
-// thread works too), under the render's IEEE float state; returns when all are
-// done (the barrier between two filter levels).  Every item writes only its own
-// outputs, so the result does not depend on the thread count.
-template <class Fn>
-void parallel_items(long n, int threads, const Fn& fn) {
-    constexpr long kChunk = 256;
-    const long chunks = (n + kChunk - 1) / kChunk;
-    if (threads < 1) threads = 1;
-    if ((long)threads > chunks) threads = (int)(chunks > 0 ? chunks : 1);
-    std::atomic<long> next(0);
-    auto work = [&]() {
-        const unsigned saved = _mm_getcsr();
-        _mm_setcsr((saved & ~(_MM_ROUND_MASK | _MM_FLUSH_ZERO_MASK | 0x0040u)) | _MM_ROUND_NEAREST);  // 0x40 = DAZ
-        for (long c = next.fetch_add(1); c < chunks; c = next.fetch_add(1)) {
-            const long end = (c + 1) * kChunk < n ? (c + 1) * kChunk : n;
-            for (long p = c * kChunk; p < end; p++) fn(p);
-        }
-        _mm_setcsr(saved);
-    };
-    std::vector<std::thread> pool;
-    pool.reserve((size_t)threads - 1);
-    for (int t = 1; t < threads; t++) {
-        try {
-            pool.emplace_back(work);
-        } catch (...) {
-            break;
-        }
-    }
-    work();
-    for (std::thread& t : pool) t.join();
-}
 
 // fn(x, y, p) for every pixel p = y * width + x of a width x height image, as
 // parallel_items
@@ -444,18 +401,26 @@ void rt_cpu_assemble(const rt_asm_args& A, int threads) {
 // ---- adaptive sampling on the host (rt_adaptive.h) -----------------------------
 #include "rt_adaptive.h"
 
-// The selection: row sums, then column sums and the test, then the list in
-// ascending pixel order (one thread: the order is the specification)
-void rt_cpu_adaptive_select(const rt_ad_args& A, int threads) {
-    parallel_pixels(A.width, A.height, threads, [&](int x, int y, long p) { ad_row_sums(A, x, y, p); });
+namespace {
+// The tail of every selection: selected(x, y, p) of every pixel, then the list
+// in ascending pixel order (one thread: the order is the specification), its
+// length, and the frames it adds to the total
+template <class Sel>
+void build_list(const rt_ad_args& A, int threads, const Sel& selected) {
     std::vector<unsigned char> flags((size_t)A.npix);  // (no ballot on the host: one byte per pixel)
-    parallel_pixels(A.width, A.height, threads,
-                    [&](int x, int y, long p) { flags[(size_t)p] = ad_selected(A, x, y, p) ? 1 : 0; });
+    parallel_pixels(A.width, A.height, threads, [&](int x, int y, long p) { flags[(size_t)p] = selected(x, y, p) ? 1 : 0; });
     unsigned n = 0;
     for (long p = 0; p < A.npix; p++)
         if (flags[(size_t)p]) A.list[n++] = (int)p;
     *A.list_n = n;
     *A.total = *A.total + (unsigned long long)n * (unsigned)A.k;
+}
+}  // namespace
+
+// The selection: row sums, then column sums and the test, then the list
+void rt_cpu_adaptive_select(const rt_ad_args& A, int threads) {
+    parallel_pixels(A.width, A.height, threads, [&](int x, int y, long p) { ad_row_sums(A, x, y, p); });
+    build_list(A, threads, [&](int x, int y, long p) { return ad_selected(A, x, y, p); });
 }
 
 // The selection of rt_render_adaptive_reprojected: the same three steps over the
@@ -463,14 +428,7 @@ void rt_cpu_adaptive_select(const rt_ad_args& A, int threads) {
 void rt_cpu_adaptive_select_reproj(const rt_ad_reproj_args& R, int threads) {
     const rt_ad_args& A = R.A;
     parallel_pixels(A.width, A.height, threads, [&](int x, int y, long p) { ad_row_sums_reproj(R, x, y, p); });
-    std::vector<unsigned char> flags((size_t)A.npix);
-    parallel_pixels(A.width, A.height, threads,
-                    [&](int x, int y, long p) { flags[(size_t)p] = ad_selected_reproj(R, x, y, p) ? 1 : 0; });
-    unsigned n = 0;
-    for (long p = 0; p < A.npix; p++)
-        if (flags[(size_t)p]) A.list[n++] = (int)p;
-    *A.list_n = n;
-    *A.total = *A.total + (unsigned long long)n * (unsigned)A.k;
+    build_list(A, threads, [&](int x, int y, long p) { return ad_selected_reproj(R, x, y, p); });
 }
 
 // A shard's row sums into its block, padding rows zeroed
@@ -483,15 +441,7 @@ void rt_cpu_adaptive_rows_block(const rt_ad_args& A, long plane, int threads) {
 // The selection of a shard from the gathered blocks: every pixel's flag depends
 // on that pixel alone, the list is made by one thread in ascending order
 void rt_cpu_adaptive_select_shard(const rt_ad_shard_args& S, int threads) {
-    const rt_ad_args& A = S.A;
-    std::vector<unsigned char> flags((size_t)A.npix);
-    parallel_pixels(A.width, A.height, threads,
-                    [&](int x, int j, long p) { flags[(size_t)p] = ad_selected_shard(S, x, j, p) ? 1 : 0; });
-    unsigned n = 0;
-    for (long p = 0; p < A.npix; p++)
-        if (flags[(size_t)p]) A.list[n++] = (int)p;
-    *A.list_n = n;
-    *A.total = *A.total + (unsigned long long)n * (unsigned)A.k;
+    build_list(S.A, threads, [&](int x, int j, long p) { return ad_selected_shard(S, x, j, p); });
 }
 
 // A.k more frames of every listed pixel, each from its own frame count

@@ -16,164 +16,26 @@
 //                                  those to the simple kernel), and the A/B
 //                                  reference of the queued one
 //
-// Both keep their own copies of the loops of rt_kernel_sorted.h and
-// rt_kernel_simple.h: shared fragments would change those kernels' instruction
-// streams (as the pair kernel's would, profiles/kernel_split/dropped.txt).
+// The one-path-per-lane kernel is rt_kernel_lane.h's lane_loop with LIST, the
+// text the NEE kernel takes too; load_list_item and store_list_pixel live there
+// and serve the queued kernel as well.  The queued kernel keeps its own copy of
+// rt_kernel_sorted.h's round loop: shared fragments would change that product
+// kernel's instruction stream (as the pair kernel's would,
+// profiles/kernel_split/dropped.txt).
 // Exact units only: the reference-fast mode has no adaptive render.
 #pragma once
 #include <cstdio>
 
-#include "rt_hit.h"
+#include "rt_kernel_lane.h"
 #include "rt_kernel_sorted.h"  // RT_GREC_*, RT_SPEC_PRIO
 #include "rt_launch.h"
 
 #ifndef RT_FAST
-namespace {
-// item i of the list (i >= n_list: none)
-__device__ __forceinline__ void load_list_item(const rt_kparams& K, const rt_list_args& L, long npix, long n_list,
-                                               long i, PixelState& s) {
-    s.w = i;
-    s.valid = i < n_list;
-    s.passes_left = 0;
-    s.frame = 0u;
-    s.p = npix;
-    if (!s.valid) return;
-    const long p = (long)L.list[i];
-    s.p = p;
-    const int j = (int)(p / K.width);
-    const int x = (int)(p - (long)j * K.width);
-    const int y = K.row_offset + j * K.row_stride;
-    s.rs.d = px_ld(&K.rng[0 * npix + p]);
-    s.rs.v0 = px_ld(&K.rng[1 * npix + p]);
-    s.rs.v1 = px_ld(&K.rng[2 * npix + p]);
-    s.rs.v2 = px_ld(&K.rng[3 * npix + p]);
-    s.rs.v3 = px_ld(&K.rng[4 * npix + p]);
-    s.rs.v4 = px_ld(&K.rng[5 * npix + p]);
-    s.ax = px_ld(&K.accum[0 * npix + p]);
-    s.ay = px_ld(&K.accum[1 * npix + p]);
-    s.az = px_ld(&K.accum[2 * npix + p]);
-    s.d0 = primary_dir(K, x, y);
-    s.frame = L.cnt[p].x + 1u;
-    s.passes_left = K.samples;
-}
-
-__device__ __forceinline__ void store_list_pixel(const rt_kparams& K, long npix, const PixelState& s) {
-    const long p = s.p;
-    px_st(&K.rng[0 * npix + p], s.rs.d);
-    px_st(&K.rng[1 * npix + p], s.rs.v0);
-    px_st(&K.rng[2 * npix + p], s.rs.v1);
-    px_st(&K.rng[3 * npix + p], s.rs.v2);
-    px_st(&K.rng[4 * npix + p], s.rs.v3);
-    px_st(&K.rng[5 * npix + p], s.rs.v4);
-    px_st(&K.accum[0 * npix + p], s.ax);
-    px_st(&K.accum[1 * npix + p], s.ay);
-    px_st(&K.accum[2 * npix + p], s.az);
-}
-}  // namespace
-
-// ---- one path per lane (rt_kernel_simple.h's loop over list items) -------------
+// ---- one path per lane ----------------------------------------------------------
 template <int BLOCK, bool HIT_LDS, bool BVH>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PER_EU)))
 rt_render_list_simple_kernel(rt_kparams K, rt_list_args L) {
-    extern __shared__ float smem[];
-    const int tid = threadIdx.x;
-    const long n_list = (long)*L.list_n;  // one scalar load
-    if ((long)blockIdx.x * BLOCK >= n_list) return;  // group-uniform, before the first barrier
-    const float* hit_tab = K.hit;
-    float* rec_base = smem;
-    if (HIT_LDS) {
-        rec_base = stage_hit_table<BLOCK>(K, smem, tid);
-        __syncthreads();
-        hit_tab = smem;
-    }
-    int* rec_code = reinterpret_cast<int*>(rec_base) + tid;
-    float* rec_k = rec_base + (K.max_bounces + 1) * BLOCK + tid;
-    float* rec_c = rec_base + 2 * (K.max_bounces + 1) * BLOCK + tid;
-
-    const long npix = (long)K.rows * K.width;
-    const long T = (long)gridDim.x * BLOCK;
-    PixelState px;
-    load_list_item(K, L, npix, n_list, (long)blockIdx.x * BLOCK + tid, px);
-
-    f3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
-    int depth = -1;  // -1: needs a camera ray for its next frame
-    const f3 cam = mk(K.cam_pos[0], K.cam_pos[1], K.cam_pos[2]);
-    f3 dcam = d;
-    int inner = 1;
-
-    while (true) {
-        // (1) regenerate: jittered camera ray (Main.cu:290-292)
-        if (depth < 0 && px.passes_left > 0) {
-            f3 jit = random_direction(px.rs, px.d0);
-            d = normalize3(add(px.d0, scale(K.jitter, jit)));
-            o = cam;
-            depth = 0;
-            dcam = d;
-            inner = K.spp_inner;
-        }
-        const bool active = depth >= 0;
-        if (__ballot(active) == 0ull) break;
-        if (active) {
-            // (2) closest hit (Main.cu:214-234)
-            float t;
-            int id;
-            closest_hit<BVH>(K, o, d, t, id);
-
-            bool finished = true;
-            if (id >= 0) {
-                // (3) shade (Main.cu:237-264)
-                const float* h = hit_tab + RT_HIT_FLOATS * id;
-                const float4 h0 = *reinterpret_cast<const float4*>(h);
-                const float4 h2 = *reinterpret_cast<const float4*>(h + 8);
-                const f3 P = add(o, scale(t, d));
-                f3 n = mk(h0.x, h0.y, h0.z);
-                if (h0.w != 0.0f) n = normalize3(sub(P, n));  // sphere: centre -> normal
-                f3 scatter;
-                int code = id;
-                float kspec = 0.0f;
-                const float choice = rand_range(px.rs, 1.0f);
-                if (choice < RT_SPECULAR_CHANCE) {
-                    scatter = specular_scatter(px.rs, d, n, h2.x, h2.z, h2.y, kspec);
-                    code = ~id;
-                } else {
-                    scatter = random_direction(px.rs, n);  // brdf = 4 * albedo
-                }
-                rec_code[depth * BLOCK] = code;
-                rec_k[depth * BLOCK] = kspec;
-                rec_c[depth * BLOCK] = dot(scatter, n);  // cosAngle, Main.cu:264
-                depth++;
-                o = P;
-                d = scatter;
-                finished = depth > K.max_bounces;  // Main.cu:210
-            }
-            if (finished) {
-                // (4) fold the recursion innermost-first (Main.cu:262-268)
-                float lx = K.bg[0], ly = K.bg[1], lz = K.bg[2];  // backgroundColor
-                for (int l = depth - 1; l >= 0; --l)
-                    fold_level(rec_code[l * BLOCK], rec_k[l * BLOCK], rec_c[l * BLOCK], hit_tab, lx, ly, lz);
-                if (inner > 1) {  // `pixel = tracePath(...)` again from the same camera ray
-                    inner--;
-                    o = cam;
-                    d = dcam;
-                    depth = 0;
-                    continue;
-                }
-                if (K.spp_inner != 1) {  // pixel /= samplesPerPixel: (1.0f / k) * pixel
-                    const float k = rt_div(1.0f, (float)K.spp_inner);
-                    lx = k * lx;
-                    ly = k * ly;
-                    lz = k * lz;
-                }
-                // (5) progressive accumulation (Main.cu:299-304)
-                accumulate_frame(px, lx, ly, lz);
-                depth = -1;
-                if (px.passes_left == 0) {  // pixel done: write back, take the next item
-                    store_list_pixel(K, npix, px);
-                    load_list_item(K, L, npix, n_list, px.w + T, px);
-                }
-            }
-        }
-    }
+    lane_loop<BLOCK, HIT_LDS, BVH, true, false>(K, rt_nee_args{nullptr, 0}, L);
 }
 
 // ---- queued (rt_kernel_sorted.h's round loop over list items) ------------------
@@ -389,19 +251,10 @@ namespace {
 template <int BLOCK, bool HIT_LDS, bool BVH>
 hipError_t launch_list_simple(const rt_kparams& K0, const rt_list_args& L, size_t lds, int num_cus, hipStream_t stream) {
     rt_kparams K = K0;
-    const long npix = (long)K.rows * K.width;
-    long grid = (npix + BLOCK - 1) / BLOCK;
     // persistent lanes: at most the resident groups (the list is usually a
     // fraction of the frame, and a group behind it returns at once)
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, reinterpret_cast<const void*>(&rt_render_list_simple_kernel<BLOCK, HIT_LDS, BVH>), BLOCK, lds) ==
-            hipSuccess &&
-        per_cu > 0) {
-        const long cap = (long)per_cu * num_cus;
-        if (grid > cap) grid = cap;
-    }
-    if (grid < 1) grid = 1;
+    const long grid = rt_lane_grid(reinterpret_cast<const void*>(&rt_render_list_simple_kernel<BLOCK, HIT_LDS, BVH>), BLOCK,
+                                   lds, (long)K.rows * K.width, 1, num_cus);
     K.rec = nullptr;
     K.group_cost = nullptr;
     K.group_order = nullptr;

@@ -12,6 +12,16 @@
 // decides when the wave is done.  Each pixel still consumes its RNG stream
 // and accumulates its frames strictly in order, so results are identical to
 // the frame-by-frame reference.
+//
+// The list and NEE kernels run the same loop from one text, rt_kernel_lane.h's
+// lane_loop.  This kernel is not routed through it: it is the A/B reference of
+// the product kernels in both precision modes, held to "identical instruction
+// stream or put back" (profiles/kernel_split/dropped.txt), and it inlines the
+// microfacet bounce where lane_loop calls specular_scatter, which changes its
+// stream in all four units (dropped.txt item 2; profiles/lane_loop/simple_kernel.txt).
+// Shared with them: the per-pixel helpers of rt_pixel.h and rt_path.h, the
+// record layout (RT_LANE_REC_DWORDS(false) = the 3 dwords below, sized by
+// rt_lane_lds_bytes) and the grid rule (rt_lane_grid).
 #pragma once
 #include <cstdio>
 
@@ -163,21 +173,12 @@ rt_render_kernel(rt_kparams K) {
 namespace {
 // Launch of the one-path-per-lane kernel: the grid covers every item once, or
 // with grid_mult > 0 (persistent lanes) at most grid_mult x resident groups
-// per CU x CUs.  It takes no launch-order feedback.
+// per CU x CUs (rt_lane_grid).  It takes no launch-order feedback.
 template <int BLOCK, bool HIT_LDS, bool BVH>
 hipError_t launch_simple(const rt_kparams& K0, size_t lds, int grid_mult, int num_cus, hipStream_t stream) {
     rt_kparams K = K0;
-    long grid = (launch_items(K) + BLOCK - 1) / BLOCK;
-    if (grid_mult > 0) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &per_cu, reinterpret_cast<const void*>(&rt_render_kernel<BLOCK, HIT_LDS, BVH>), BLOCK, lds) == hipSuccess &&
-            per_cu > 0) {
-            const long cap = (long)per_cu * num_cus * grid_mult;
-            if (grid > cap) grid = cap;
-        }
-    }
-    if (grid < 1) grid = 1;
+    const long grid = rt_lane_grid(reinterpret_cast<const void*>(&rt_render_kernel<BLOCK, HIT_LDS, BVH>), BLOCK, lds,
+                                   launch_items(K), grid_mult, num_cus);
     K.rec_stride = (int)(grid * BLOCK);
     K.group_cost = nullptr;
     K.group_order = nullptr;

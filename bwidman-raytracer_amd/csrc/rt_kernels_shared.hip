@@ -96,7 +96,9 @@ bool rt_hit_in_lds(const rt_kparams& K) {
     const int n_prim = K.n_sph + K.n_pln + K.n_tri + K.n_quad;
     return !K.bvh_nodes && (size_t)n_prim * RT_HIT_FLOATS * sizeof(float) <= 16384;
 }
-bool rt_small_block(const rt_kparams& K) { return (size_t)3 * (K.max_bounces + 1) * 256 * sizeof(float) > 49152; }
+bool rt_small_block(const rt_kparams& K) {
+    return (size_t)RT_LANE_REC_DWORDS(false) * (K.max_bounces + 1) * 256 * sizeof(float) > 49152;
+}
 
 // Frames and shards of at most RT_SPREAD_PIX pixels per CU (about 1.5
 // generations of 7 waves per SIMD, 32 pixels per wave) take 128-lane pair
@@ -122,6 +124,18 @@ bool rt_takes_pair(const rt_kparams& K, bool hit_lds, int num_cus, int block_req
 bool rt_render_takes_sorted(const rt_kparams& K, int num_cus, bool simple, int block_req, int pair_req) {
     if (simple || K.spp_inner > 1 || K.bvh_nodes) return false;
     return rt_small_block(K) || !rt_takes_pair(K, rt_hit_in_lds(K), num_cus, block_req, pair_req);
+}
+
+long rt_lane_grid(const void* kernel, int block, size_t lds, long items, int grid_mult, int num_cus) {
+    long grid = (items + block - 1) / block;
+    if (grid_mult > 0) {
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds) == hipSuccess && per_cu > 0) {
+            const long cap = (long)per_cu * num_cus * grid_mult;
+            if (grid > cap) grid = cap;
+        }
+    }
+    return grid < 1 ? 1 : grid;
 }
 
 // launch-order feedback applies to grids of more than RT_ORDER_MIN_GEN
@@ -182,17 +196,26 @@ size_t rt_render_rec_floats(const rt_kparams& K) {
     return planes ? planes * (size_t)((nitems + 255) / 256 * 256) : 1;
 }
 
-// LDS bytes of one workgroup: hit table (if staged) + 3 record dwords per
-// level per lane + 13 task-slot dwords per lane and 4 queue counters (sorted).
-size_t rt_render_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool sorted) {
+// LDS bytes of one workgroup of a one-path-per-lane kernel (rt_render_kernel,
+// rt_kernel_lane.h; nee: next-event estimation): hit table (if staged) + the
+// record stack of max_bounces + 1 levels
+size_t rt_lane_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool nee) {
     const int n_prim = K.n_sph + K.n_pln + K.n_tri + K.n_quad;
     const size_t hit = hit_lds ? (size_t)((n_prim * RT_HIT_FLOATS + 3) & ~3) * sizeof(float) : 0;
-    // record stack: max_bounces + 1 levels (simple kernel), max_bounces (sorted)
-    const int lds_levels = sorted && K.rec ? (K.max_bounces < RT_GREC_LDS_LEVELS ? K.max_bounces : RT_GREC_LDS_LEVELS)
-                                           : K.max_bounces + (sorted ? 0 : 1);
-    size_t b = hit + (size_t)3 * (lds_levels > 0 ? lds_levels : 0) * block * sizeof(float);
-    if (sorted) b += (size_t)13 * block * sizeof(float) + 8 * sizeof(int);  // + queue counters
-    return b;
+    const int levels = K.max_bounces + 1;
+    return hit + (size_t)RT_LANE_REC_DWORDS(nee) * (levels > 0 ? levels : 0) * block * sizeof(float);
+}
+
+// LDS bytes of one workgroup.  Sorted: hit table (if staged) + 3 record dwords
+// per level per lane (max_bounces levels) + 13 task-slot dwords per lane and 4
+// queue counters; else rt_lane_lds_bytes.
+size_t rt_render_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool sorted) {
+    if (!sorted) return rt_lane_lds_bytes(K, block, hit_lds, false);
+    const int n_prim = K.n_sph + K.n_pln + K.n_tri + K.n_quad;
+    const size_t hit = hit_lds ? (size_t)((n_prim * RT_HIT_FLOATS + 3) & ~3) * sizeof(float) : 0;
+    const int lds_levels = K.rec ? (K.max_bounces < RT_GREC_LDS_LEVELS ? K.max_bounces : RT_GREC_LDS_LEVELS) : K.max_bounces;
+    return hit + (size_t)3 * (lds_levels > 0 ? lds_levels : 0) * block * sizeof(float) +
+           (size_t)13 * block * sizeof(float) + 8 * sizeof(int);  // + queue counters
 }
 
 thread_local long rt_order_groups_last = 0;

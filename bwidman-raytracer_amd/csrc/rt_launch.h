@@ -39,6 +39,10 @@ bool rt_takes_pair(const rt_kparams& K, bool hit_lds, int num_cus, int block_req
 // Whether rt_launch_render takes the sorted brute-force kernel for K (K.rec
 // as the launch will have it): the only kernel that reads K.sky
 bool rt_render_takes_sorted(const rt_kparams& K, int num_cus, bool simple, int block_req, int pair_req);
+// The grid of a one-path-per-lane kernel (rt_render_kernel, the list and NEE
+// kernels): `items` work items in groups of `block` lanes, or with grid_mult > 0
+// (persistent lanes) at most grid_mult x resident groups per CU x CUs; at least 1
+long rt_lane_grid(const void* kernel, int block, size_t lds, long items, int grid_mult, int num_cus);
 // launch-order feedback around a launch of `grid` groups: the launch's
 // parameters, and the sort behind it (K: what begin returned)
 rt_kparams rt_order_begin(const rt_kparams& K0, long grid, const void* kernel, int block, size_t lds, int num_cus,
@@ -51,6 +55,7 @@ extern thread_local long rt_order_groups_last;
 extern thread_local char rt_launched_kernel[96];
 size_t rt_render_rec_floats(const rt_kparams& K);
 size_t rt_render_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool sorted);
+size_t rt_lane_lds_bytes(const rt_kparams& K, int block, bool hit_lds, bool nee);
 size_t rt_pair_lds_bytes(const rt_kparams& K);
 hipError_t rt_launch_order_groups(const unsigned* cost, int* order, long n, hipStream_t stream);
 hipError_t rt_launch_init_rand(unsigned* rng, int width, int rows, int row_offset, int row_stride,

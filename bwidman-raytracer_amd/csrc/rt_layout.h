@@ -48,6 +48,10 @@
 #define RT_SPECULAR_CHANCE 0.5f    // Main.cu:29
 #define RT_PI 3.1415926535f        // Math.cuh:5
 #define RT_MAX_LEVELS 33           // recursion records per path: RT_MAX_BOUNCES (rt_abi.h) + 1
+// dwords per level per lane of the one-path-per-lane kernels' LDS record stack
+// (max_bounces + 1 levels): code, k, cosAngle, and under next-event estimation
+// aux (rt_light.h).  The kernels' layout and the host's LDS sizes both take it.
+#define RT_LANE_REC_DWORDS(nee) ((nee) ? 4 : 3)
 
 // diagnostic builds (-DRT_GTIMES, BWRT_GTIMES): words of the group / lane
 // time buffer (rt_diag.h; rt_render.cpp allocates it)

@@ -86,6 +86,26 @@ def test_samples_per_pixel(bwrt_lib):
     both(bwrt_lib, scenes.scene_07(), 67, 45, 4, kernel="rt_render_kernel<256,list>", spp=2)
 
 
+# the one-path-per-lane list kernel's other instantiations (samplesPerPixel 2
+# takes it whatever the scene): 64-lane groups from 16 bounces on (the record
+# stack of 256 lanes passes 48 KB), the hit table in global memory, both on the BVH
+@pytest.mark.parametrize("name,w,h,bounces,kernel", [
+    ("07", 67, 45, 16, "rt_render_kernel<64,list>"),
+    ("big", 24, 16, 4, "rt_render_kernel<256,hit_global,list>"),
+    ("big", 24, 16, 16, "rt_render_kernel<64,hit_global,list>"),
+    ("stress", 96, 54, 16, "rt_render_kernel<64,hit_global,bvh,list>"),
+])
+def test_simple_kernel_instantiations(bwrt_lib, monkeypatch, name, w, h, bounces, kernel):
+    if name == "big":  # 408 primitives, no BVH: over 16 KB of hit table
+        monkeypatch.setenv("BWRT_BVH_MIN", "100000000")
+        scene = scenes.stress_scene(n_triangles=400, n_spheres=8)
+    else:
+        scene = scenes.SCENES[name]()
+    got, got_name = both(bwrt_lib, scene, w, h, bounces, spp=2)
+    assert got_name == kernel
+    assert got["stats"][0][0] > 0  # the list kernel did run
+
+
 def test_forced_kernels_equal_the_policy(bwrt_lib, monkeypatch):
     scene = scenes.scene_07()
     w, h, mb = 67, 45, 4

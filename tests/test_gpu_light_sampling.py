@@ -116,6 +116,32 @@ def test_adaptive_calls_equal_cpu(bwrt_lib, name, w, h, mb, kernel):
     assert 0 < got["stats"][0][0] < w * h
 
 
+# the list instantiations the cases above do not reach: 64-lane groups (12
+# bounces: the 4-dword record stack of 256 lanes passes 48 KB), the hit table in
+# global memory (test_hit_table_in_global_memory's scene), both on the BVH
+@pytest.mark.parametrize("name,w,h,mb,kernel", [
+    ("07", 67, 45, 12, "rt_render_nee_kernel<64,list>"),
+    ("stress", 96, 54, 12, "rt_render_nee_kernel<64,hit_global,bvh,list>"),
+    ("big", 24, 16, 4, "rt_render_nee_kernel<256,hit_global,list>"),
+    ("big", 24, 16, 12, "rt_render_nee_kernel<64,hit_global,list>"),
+])
+def test_adaptive_list_instantiations(bwrt_lib, monkeypatch, name, w, h, mb, kernel):
+    if name == "big":
+        monkeypatch.setenv("BWRT_BVH_MIN", "100000000")
+        scene = scenes.stress_scene(n_triangles=400, n_spheres=8)
+    else:
+        scene = scenes.SCENES[name]()
+    with Renderer(0, lib=bwrt_lib) as g:
+        g.set_light_sampling(True)
+        got = adaptive_sequence(g, scene, w, h, mb)
+        assert g.last_kernel_name() == kernel
+    with Renderer.cpu(0, lib=bwrt_lib) as c:
+        c.set_light_sampling(True)
+        want = adaptive_sequence(c, scene, w, h, mb)
+    same(got, want)
+    assert got["stats"][0][0] > 0  # the list kernel did run
+
+
 def test_device_entry_point_with_a_filter_behind(bwrt_lib):
     """rt_render_device on the context's stream, rt_denoise_var_device queued
     directly behind it."""
