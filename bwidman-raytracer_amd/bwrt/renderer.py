@@ -113,6 +113,22 @@ class Renderer:
     def light_sampling(self) -> bool:
         return bool(self.lib.rt_get_light_sampling(self.ctx))
 
+    _LIGHT_PICKS = {"uniform": abi.RT_LIGHT_PICK_UNIFORM, "weighted": abi.RT_LIGHT_PICK_WEIGHTED}
+
+    def set_light_picking(self, mode: str):
+        """rt_set_light_picking: how light sampling picks the light of a bounce,
+        "uniform" (default) or "weighted" (by emitted power, solid angle and a
+        cosine bound at the shading point: less noise where the lights' shares
+        differ, two passes over the light table per bounce).  Acts only while
+        light sampling is on; accumulation, frame counter and RNG streams stay."""
+        if mode not in self._LIGHT_PICKS:
+            raise ValueError(f"light picking {mode!r}: expected 'uniform' or 'weighted'")
+        self._check(self.lib.rt_set_light_picking(self.ctx, self._LIGHT_PICKS[mode]))
+
+    @property
+    def light_picking(self) -> str:
+        return "weighted" if self.lib.rt_get_light_picking(self.ctx) == abi.RT_LIGHT_PICK_WEIGHTED else "uniform"
+
     def lights(self):
         """rt_get_lights: the scene's light table as a structured array with
         fields centre (3 float32), r2, emitted (3 float32) and prim (int32)."""

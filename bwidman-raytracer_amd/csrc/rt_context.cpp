@@ -351,6 +351,19 @@ int rt_set_light_sampling(rt_context* c, int on) {
 
 int rt_get_light_sampling(const rt_context* c) { return c && c->light_sampling ? 1 : 0; }
 
+// Likewise only a choice at the next render, and only where light sampling acts
+// (rt_context::nee_args)
+int rt_set_light_picking(rt_context* c, int mode) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_LIGHT_PICK_UNIFORM && mode != RT_LIGHT_PICK_WEIGHTED)
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "rt_set_light_picking: %d is neither RT_LIGHT_PICK_UNIFORM nor RT_LIGHT_PICK_WEIGHTED", mode);
+    c->light_picking = mode;
+    return RT_OK;
+}
+
+int rt_get_light_picking(const rt_context* c) { return c ? c->light_picking : RT_LIGHT_PICK_UNIFORM; }
+
 int rt_get_lights(rt_context* c, float* out, int capacity) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");

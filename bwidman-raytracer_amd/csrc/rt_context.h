@@ -272,12 +272,16 @@ struct rt_context {
     // CPU twin; light_buf holds the scene's light table (scene.lights; rt_set_scene uploads it)
     bool light_sampling = false;
     Buf light_buf;
+    // rt_set_light_picking: how an NEE level picks its light (rt_light.h); acts only where nee_args
+    // returns a table
+    int light_picking = RT_LIGHT_PICK_UNIFORM;
+    static_assert(RT_PICK_UNIFORM == RT_LIGHT_PICK_UNIFORM && RT_PICK_WEIGHTED == RT_LIGHT_PICK_WEIGHTED, "rt_layout.h / rt_abi.h");
     // The light table a render at max_bounces takes, or none ({null, 0}: the default estimator, its
     // kernels and launch policy): the switch, and a scene and a depth where the estimators differ (an
     // empty table and max_bounces 0 are bit-identical to the default, rt_light.h)
     rt_nee_args nee_args(int max_bounces) const {
-        if (!light_sampling || scene.lights.empty() || max_bounces <= 0) return {nullptr, 0};
-        return {light_buf.as<const float>(), (int)(scene.lights.size() / RT_LIGHT_FLOATS)};
+        if (!light_sampling || scene.lights.empty() || max_bounces <= 0) return {nullptr, 0, 0};
+        return {light_buf.as<const float>(), (int)(scene.lights.size() / RT_LIGHT_FLOATS), light_picking};
     }
     // the frame counter, the moment tracking and the non-uniform state: what
     // frameSum currently holds (rt_accum.h has the rules)

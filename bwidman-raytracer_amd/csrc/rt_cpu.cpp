@@ -70,8 +70,9 @@ void closest_hit_bvh_cpu(const rt_kparams& K, f3 o, f3 d, float& best_t, int& be
 // NEE: next-event estimation (rt_light.h) — at a diffuse hit whose scattered
 // ray will be traced, the three draws, the direct term of the picked light
 // through a shadow ray, and the suppression of the emission the scattered ray
-// finds on a reachable table light.  The caller takes NEE iff N.n_lights > 0.
-template <bool NEE>
+// finds on a reachable table light.  The caller takes NEE iff N.n_lights > 0,
+// and PICK (how nee_sample picks its light, rt_light.h) from N.pick.
+template <bool NEE, int PICK>
 f3 trace_path(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d) {
     // recursion records (code, k, cosAngle; NEE: aux): at most max_bounces + 1 hits
     int rec_code[RT_MAX_LEVELS];
@@ -111,7 +112,7 @@ f3 trace_path(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d)
             if constexpr (NEE) {
                 const int kind = nee_normal_kind(h[3] != 0.0f, n);
                 if (depth + 1 <= K.max_bounces && N.n_lights > 0 && kind) {
-                    const NeeSample s = nee_sample(rs, N, P, n, id, kind);
+                    const NeeSample s = nee_sample<PICK>(rs, N, P, n, id, kind);
                     aux |= RT_NEE_LEVEL | (s.j << RT_NEE_JSHIFT);
                     k = s.k;
                     nee_prim = id;
@@ -147,7 +148,7 @@ f3 trace_path(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d)
 // Every frame of shard pixel p (Main.cu:285-312 per frame, frames in order),
 // the first one `first`: K.first_frame, or n_p + 1 of a listed pixel of an
 // adaptive call (rt_adaptive.h), whose image the resolve pass writes
-template <bool NEE>
+template <bool NEE, int PICK>
 void render_pixel_as(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
     const int j = (int)(p / K.width);
     const int x = (int)(p - (long)j * K.width);
@@ -173,8 +174,8 @@ void render_pixel_as(const rt_kparams& K, const rt_nee_args& N, long npix, long 
         const f3 jit = random_direction(rs, d0);
         const f3 dcam = normalize3(add(d0, scale(K.jitter, jit)));
         // samplesPerPixel paths from it; the last one is kept (Main.cu:296-298)
-        f3 L = trace_path<NEE>(K, N, rs, cam, dcam);
-        for (int i = 1; i < K.spp_inner; i++) L = trace_path<NEE>(K, N, rs, cam, dcam);
+        f3 L = trace_path<NEE, PICK>(K, N, rs, cam, dcam);
+        for (int i = 1; i < K.spp_inner; i++) L = trace_path<NEE, PICK>(K, N, rs, cam, dcam);
         float lx = L.x, ly = L.y, lz = L.z;
         if (K.spp_inner != 1) {  // pixel /= samplesPerPixel: (1.0f / k) * pixel (Math.cuh:91-97)
             const float k = 1.0f / (float)K.spp_inner;
@@ -205,12 +206,14 @@ void render_pixel_as(const rt_kparams& K, const rt_nee_args& N, long npix, long 
     if (K.rgba) K.rgba[p] = tone_map(ax, ay, az, frame - 1u);
 }
 
-// (the estimator is picked once per pixel: rt_set_light_sampling)
+// (the estimator is picked once per pixel: rt_set_light_sampling, rt_set_light_picking)
 void render_pixel(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
-    if (N.n_lights > 0)
-        render_pixel_as<true>(K, N, npix, p, first);
+    if (N.n_lights > 0 && N.pick == RT_PICK_WEIGHTED)
+        render_pixel_as<true, RT_PICK_WEIGHTED>(K, N, npix, p, first);
+    else if (N.n_lights > 0)
+        render_pixel_as<true, RT_PICK_UNIFORM>(K, N, npix, p, first);
     else
-        render_pixel_as<false>(K, N, npix, p, first);
+        render_pixel_as<false, RT_PICK_UNIFORM>(K, N, npix, p, first);
 }
 
 // fn(p) for p = 0 .. n-1 in 256-item chunks, which `threads` threads (>= 1; the

@@ -35,7 +35,7 @@
 template <int BLOCK, bool HIT_LDS, bool BVH>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PER_EU)))
 rt_render_list_simple_kernel(rt_kparams K, rt_list_args L) {
-    lane_loop<BLOCK, HIT_LDS, BVH, true, false>(K, rt_nee_args{nullptr, 0}, L);
+    lane_loop<BLOCK, HIT_LDS, BVH, true, false>(K, rt_nee_args{nullptr, 0, 0}, L);
 }
 
 // ---- queued (rt_kernel_sorted.h's round loop over list items) ------------------

@@ -361,9 +361,15 @@ struct rt_list_args {
 //   {cx, cy, cz, r*r, emitted.r, emitted.g, emitted.b, primitive id as int bits}
 // (emitted = the hit table's emittance * albedo, the same floats).
 #define RT_LIGHT_FLOATS 8
+// pick modes of nee_sample (rt_light.h; include/rt_abi.h RT_LIGHT_PICK_*)
+#define RT_PICK_UNIFORM 0
+#define RT_PICK_WEIGHTED 1
 struct rt_nee_args {
     const float* lights;
     int n_lights;            // 0: the estimator is the default one, bit for bit
+    int pick;                // rt_set_light_picking (RT_LIGHT_PICK_*), for the host: the launcher picks the
+                             // instantiation and the CPU twin its path by it; no kernel reads it (the
+                             // struct's tail padding before: size and the fields in front unchanged)
 };
 
 // One adaptive call (rt_adaptive.h) over the full width x height frame of a

@@ -43,6 +43,24 @@
 // Record of a level (four dwords): code, k, cosAngle as the default kernels',
 // and aux; a diffuse level does not use k for a specular scalar, so an NEE
 // level keeps n_lights * omega * cs there.
+//
+// Weighted picking (rt_set_light_picking, RT_LIGHT_PICK_WEIGHTED; DESIGN.md
+// section 24).  The same three draws in the same order, but light j is picked
+// with probability w_j / W, W the float sum of the weights in table order, and
+// the direct term takes W / w_j where the uniform pick takes n_lights.  The
+// weight of table light j at the level's point P (normal n):
+//   w_j = 0                       if !light_reachable(P, prim, l_j, w, d2), else
+//   s2 = r2 / d2,  omega_j = s2 / (1 + sqrt(1 - s2))
+//   cc = (w . n) / (sqrt(d2) nl)  nl = 1 (kind 1), sqrt(n . n) (kind 2)
+//   cb = max(0, cc) + sqrt(s2)    >= cos(theta_c - theta_max), the largest
+//                                 cosine inside the cone; > 0 where one is
+//   pw = |e.x| + |e.y| + |e.z|
+//   w_j = (pw omega_j) cb         and 0 unless that is > 0 (zero, NaN, underflow)
+// !(W > 0): the direct term is 0 without a shadow ray; the level stays an NEE
+// level (the suppression stays on) and j is the uniform formula's.  Else j is
+// the first positive-weight light whose running sum (the additions of W, in
+// their order) exceeds u W, or the last positive-weight light.  The path does
+// not depend on the pick: same draws, same rays, same RNG state.
 #pragma once
 #include "rt_path.h"
 
@@ -70,6 +88,26 @@ RT_HD LightRec light_load(const float* lights, int j) {
     l.e = mk(b.x, b.y, b.z);
     l.prim = rt_f2i(b.w);
     return l;
+}
+
+// The same record for the weight passes of weighted picking, whose index m is
+// uniform across a wave: the device pass reads it through the constant address
+// space, which makes the loads scalar ones (one per wave through the scalar
+// data cache, no vector memory instruction).  The table is never written while
+// a render kernel runs.
+RT_HD LightRec light_load_uniform(const float* lights, int m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(4))) const float cfloat;
+    cfloat* p = (cfloat*)(lights + RT_LIGHT_FLOATS * (size_t)m);
+    LightRec l;
+    l.c = mk(p[0], p[1], p[2]);
+    l.r2 = p[3];
+    l.e = mk(p[4], p[5], p[6]);
+    l.prim = rt_f2i(p[7]);
+    return l;
+#else
+    return light_load(lights, m);
+#endif
 }
 
 // A point P on primitive `prim` can be lit by the light through its cone: P is
@@ -119,7 +157,8 @@ RT_HD int nee_normal_kind(bool sphere, f3 n) {
 
 // The three draws of an NEE level and the sample they give at P (normal n as
 // the path has it, on primitive `prim`): light j, and, when `trace`, the shadow
-// ray's direction wi, the weight k = n_lights * omega * cs (kind 2: the stretched form of cs) and the id the shadow
+// ray's direction wi, the weight k = n_lights * omega * cs (kind 2: the stretched form of cs; PICK weighted:
+// W / w_j in place of n_lights, see the head of this file) and the id the shadow
 // ray must return.  !trace: the direct term is 0 without a shadow ray.
 struct NeeSample {
     int j, prim;
@@ -128,6 +167,22 @@ struct NeeSample {
     f3 wi;
 };
 
+// The weight of table light l at P (normal n of length nl, on primitive `prim`)
+// under weighted picking (see the head of this file); > 0 or exactly 0
+RT_HD float nee_pick_weight(const LightRec& l, f3 P, f3 n, float nl, int prim) {
+    f3 w;
+    float d2;
+    if (!light_reachable(P, prim, l, w, d2)) return 0.0f;
+    const float s2 = rt_div(l.r2, d2);
+    const float omega = rt_div(s2, 1.0f + rt_sqrt(1.0f - s2));
+    const float cc = rt_div(dot(w, n), rt_sqrt(d2) * nl);
+    const float cb = fmaxf(0.0f, cc) + rt_sqrt(s2);
+    const float pw = fabsf(l.e.x) + fabsf(l.e.y) + fabsf(l.e.z);
+    const float wt = (pw * omega) * cb;
+    return wt > 0.0f ? wt : 0.0f;
+}
+
+template <int PICK>
 RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int prim, int kind) {
     const float u = rand_range(rs, 1.0f);
     const float u1 = rand_range(rs, 1.0f);
@@ -139,6 +194,32 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
     s.trace = false;
     s.k = 0.0f;
     s.wi = mk(0.0f, 0.0f, 0.0f);
+    // what multiplies omega * cs: 1 / (the probability of picking light j)
+    float inv_pick = nf;
+    if constexpr (PICK == RT_PICK_WEIGHTED) {
+        // two passes over the table, the index uniform across a wave; the
+        // second one computes the same weights again (the same expressions
+        // give the same bits), so none is kept anywhere
+        const float nl = kind == 2 ? rt_sqrt(dot(n, n)) : 1.0f;
+        float W = 0.0f;
+        for (int m = 0; m < N.n_lights; m++) W = W + nee_pick_weight(light_load_uniform(N.lights, m), P, n, nl, prim);
+        if (!(W > 0.0f)) {
+            s.prim = -1;
+            return s;
+        }
+        const float target = u * W;
+        float run = 0.0f, wj = 0.0f;
+        for (int m = 0; m < N.n_lights; m++) {
+            const float wt = nee_pick_weight(light_load_uniform(N.lights, m), P, n, nl, prim);
+            if (wt > 0.0f) {
+                run = run + wt;
+                s.j = m;
+                wj = wt;
+                if (run > target) break;
+            }
+        }
+        inv_pick = rt_div(W, wj);
+    }
     const LightRec l = light_load(N.lights, s.j);
     s.prim = l.prim;
     f3 w;
@@ -173,7 +254,7 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
         const float q = (1.0f - un2) + rt_div(un2, g * g);
         wc = (0.5f * cs) * (1.0f + rt_div(1.0f, g * (q * q)));
     }
-    s.k = (nf * omega) * wc;
+    s.k = (inv_pick * omega) * wc;
     s.trace = true;
     return s;
 }

@@ -37,6 +37,8 @@
 // --light-sampling turns next-event estimation on (rt_set_light_sampling): every
 // render call, the adaptive ones included, samples the emissive spheres at its
 // diffuse bounces; it combines with every other flag but --precision fast.
+// --light-picking uniform|weighted (rt_set_light_picking) chooses how such a
+// bounce picks its light; it needs --light-sampling.
 // --denoise [N] filters the final frame with rt_denoise (N a-trous levels,
 // default rt_denoise_params_default(); the --sigma-* flags replace its
 // sigmas): the file from --out is then the denoised frame.
@@ -115,7 +117,8 @@ static const char* kUsage =
     "usage: bwrt_render [--scene 07|01|04|04_box | --scene-file FILE] [--save-scene FILE]\n"
     "                   [--width 1920] [--height 1080] [--frames 8] [--frames-per-call 1]\n"
     "                   [--max-bounces 5] [--background r,g,b] [--spp 1] [--device 0] [--gpus 1]\n"
-    "                   [--cpu [THREADS]] [--precision exact|fast] [--light-sampling]\n"
+    "                   [--cpu [THREADS]] [--precision exact|fast]\n"
+    "                   [--light-sampling [--light-picking uniform|weighted]]\n"
     "                   [--keys \"W*10,W+LEFT*5,*3\"]\n"
     "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n"
     "                   [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]\n"
@@ -184,6 +187,7 @@ int main(int argc, char** argv) {
     int gpus = 1, spp = 1, cpu_threads = -1;  // -1: GPU
     int precision = RT_PRECISION_EXACT;
     bool light_sampling = false;
+    int light_picking = -1;  // -1: not given
     float bg[3] = {0.0f, 0.0f, 0.0f};
     double fixed_dt = -1.0;
     bool denoise = false;
@@ -236,6 +240,15 @@ int main(int argc, char** argv) {
             }
         }
         else if (!std::strcmp(argv[i], "--light-sampling")) light_sampling = true;
+        else if (!std::strcmp(argv[i], "--light-picking")) {
+            const char* v = next();
+            if (!std::strcmp(v, "uniform")) light_picking = RT_LIGHT_PICK_UNIFORM;
+            else if (!std::strcmp(v, "weighted")) light_picking = RT_LIGHT_PICK_WEIGHTED;
+            else {
+                std::fprintf(stderr, "unknown --light-picking '%s'\n%s", v, kUsage);
+                return 2;
+            }
+        }
         else if (!std::strcmp(argv[i], "--keys")) keys_spec = next();
         else if (!std::strcmp(argv[i], "--dt")) fixed_dt = std::atof(next());
         else if (!std::strcmp(argv[i], "--out")) out = next();
@@ -295,6 +308,10 @@ int main(int argc, char** argv) {
     }
     if (light_sampling && precision == RT_PRECISION_REFERENCE_FAST) {
         std::fprintf(stderr, "--light-sampling cannot be combined with --precision fast: its estimator is exact arithmetic only\n");
+        return 2;
+    }
+    if (light_picking >= 0 && !light_sampling) {
+        std::fprintf(stderr, "--light-picking needs --light-sampling: it chooses how light sampling picks its light\n");
         return 2;
     }
     if (denoise && denoise_var) {
@@ -387,6 +404,7 @@ int main(int argc, char** argv) {
         }
         if ((rc = rt_set_precision(ctxs[g], precision))) return die(ctxs[g], rc, "rt_set_precision");
         if ((rc = rt_set_light_sampling(ctxs[g], light_sampling ? 1 : 0))) return die(ctxs[g], rc, "rt_set_light_sampling");
+        if (light_picking >= 0 && (rc = rt_set_light_picking(ctxs[g], light_picking))) return die(ctxs[g], rc, "rt_set_light_picking");
         if ((rc = rt_set_samples_per_pixel(ctxs[g], spp))) return die(ctxs[g], rc, "rt_set_samples_per_pixel");
         if ((rc = rt_set_scene(ctxs[g], &view))) return die(ctxs[g], rc, "rt_set_scene");
         if ((rc = rt_set_max_bounces(ctxs[g], max_bounces))) return die(ctxs[g], rc, "rt_set_max_bounces");

@@ -284,6 +284,24 @@ RT_API int rt_get_precision(const rt_context* ctx);
  * and touch nothing. */
 RT_API int rt_set_light_sampling(rt_context* ctx, int on);
 RT_API int rt_get_light_sampling(const rt_context* ctx);
+/* How next-event estimation picks the light of a bounce (DESIGN.md section
+ * 24).  RT_LIGHT_PICK_UNIFORM (the default): every table light with the same
+ * probability.  RT_LIGHT_PICK_WEIGHTED: with a probability proportional to a
+ * bound of what the light can contribute at the shading point — its emitted
+ * power, the solid angle of its cone and the largest cosine inside the cone —
+ * so shadow rays go to the lights that matter there.  The path itself does not
+ * change (same draws, same rays, same RNG state); both picks are unbiased for
+ * the same image, the weighted one with less noise where the lights' shares
+ * differ, and frames of both may share one accumulation.  Cost: two passes
+ * over the light table per diffuse bounce, linear in the number of lights.
+ * The mode acts only while light sampling is on; with it off the value is
+ * stored and changes nothing, bit for bit.  GPU and CPU contexts agree bit for
+ * bit.  Per context; takes effect at the next render; resets neither the
+ * accumulation, nor the frame counter, nor the RNG streams.  Other values
+ * return RT_ERR_INVALID_ARGUMENT. */
+typedef enum rt_light_pick { RT_LIGHT_PICK_UNIFORM = 0, RT_LIGHT_PICK_WEIGHTED = 1 } rt_light_pick;
+RT_API int rt_set_light_picking(rt_context* ctx, int mode);
+RT_API int rt_get_light_picking(const rt_context* ctx);
 /* The light table the scene compiler built at rt_set_scene: one record of
  * RT_LIGHT_RECORD_FLOATS floats per sphere with finite emittance > 0 and finite
  * radius > 0, in sphere order: {cx, cy, cz, r*r, emitted.r, emitted.g,
