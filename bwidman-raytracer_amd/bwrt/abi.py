@@ -130,6 +130,8 @@ RT_PRECISION_REFERENCE_FAST = 1
 RT_LIGHT_RECORD_FLOATS = 8  # rt_get_lights
 RT_LIGHT_PICK_UNIFORM = 0  # rt_set_light_picking
 RT_LIGHT_PICK_WEIGHTED = 1
+RT_LIGHT_SHAPES_SPHERES = 0  # rt_set_light_shapes
+RT_LIGHT_SHAPES_ALL = 1
 
 _lib = None
 
@@ -159,6 +161,8 @@ def _proto(lib):
         "rt_get_light_sampling": (C.c_int, [vp]),
         "rt_set_light_picking": (C.c_int, [vp, C.c_int]),
         "rt_get_light_picking": (C.c_int, [vp]),
+        "rt_set_light_shapes": (C.c_int, [vp, C.c_int]),
+        "rt_get_light_shapes": (C.c_int, [vp]),
         "rt_get_lights": (C.c_int, [vp, C.POINTER(C.c_float), C.c_int]),
         "rt_set_samples_per_pixel": (C.c_int, [vp, C.c_int]),
         "rt_get_camera": (C.c_int, [vp, P(Camera)]),

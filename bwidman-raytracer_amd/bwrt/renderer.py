@@ -129,6 +129,22 @@ class Renderer:
     def light_picking(self) -> str:
         return "weighted" if self.lib.rt_get_light_picking(self.ctx) == abi.RT_LIGHT_PICK_WEIGHTED else "uniform"
 
+    _LIGHT_SHAPES = {"spheres": abi.RT_LIGHT_SHAPES_SPHERES, "all": abi.RT_LIGHT_SHAPES_ALL}
+
+    def set_light_shapes(self, mode: str):
+        """rt_set_light_shapes: which emitters light sampling samples, "spheres"
+        (default) or "all" (emissive triangles and convex quads as well, by
+        area).  Acts only while light sampling is on; accumulation, frame
+        counter and RNG streams stay.  lights() returns the table of the
+        current mode."""
+        if mode not in self._LIGHT_SHAPES:
+            raise ValueError(f"light shapes {mode!r}: expected 'spheres' or 'all'")
+        self._check(self.lib.rt_set_light_shapes(self.ctx, self._LIGHT_SHAPES[mode]))
+
+    @property
+    def light_shapes(self) -> str:
+        return "all" if self.lib.rt_get_light_shapes(self.ctx) == abi.RT_LIGHT_SHAPES_ALL else "spheres"
+
     def lights(self):
         """rt_get_lights: the scene's light table as a structured array with
         fields centre (3 float32), r2, emitted (3 float32) and prim (int32)."""

@@ -284,7 +284,10 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
     const size_t bytes = cs.data.size() * sizeof(float);
     int rc = quiesce(c);  // a render on a caller's stream may still read the scene
     if (!rc) rc = ensure_buf(c, c->scene_buf, bytes, "host scene of %zu bytes", bytes);
-    const size_t lbytes = cs.lights.size() * sizeof(float);
+    // the light table: every record, then the polygon lights' sampling blocks
+    std::vector<float> ltab(cs.lights);
+    ltab.insert(ltab.end(), cs.light_polys.begin(), cs.light_polys.end());
+    const size_t lbytes = ltab.size() * sizeof(float);
     if (!rc && lbytes) rc = ensure_buf(c, c->light_buf, lbytes, "host light table of %zu bytes", lbytes);
     if (rc) {
         if (!c->scene_buf.p) c->has_scene = false;  // the old buffer went in the attempt to grow it
@@ -292,10 +295,10 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
     }
     if (c->cpu) {
         std::memcpy(c->scene_buf.p, cs.data.data(), bytes);
-        if (lbytes) std::memcpy(c->light_buf.p, cs.lights.data(), lbytes);
+        if (lbytes) std::memcpy(c->light_buf.p, ltab.data(), lbytes);
     } else {
         HIP_TRY(c, hipMemcpyAsync(c->scene_buf.p, cs.data.data(), bytes, hipMemcpyHostToDevice, c->stream));
-        if (lbytes) HIP_TRY(c, hipMemcpyAsync(c->light_buf.p, cs.lights.data(), lbytes, hipMemcpyHostToDevice, c->stream));
+        if (lbytes) HIP_TRY(c, hipMemcpyAsync(c->light_buf.p, ltab.data(), lbytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     rt_sky_collect(*s, cs, c->sky_prims);
@@ -364,11 +367,23 @@ int rt_set_light_picking(rt_context* c, int mode) {
 
 int rt_get_light_picking(const rt_context* c) { return c ? c->light_picking : RT_LIGHT_PICK_UNIFORM; }
 
+// Likewise: how many records of the scene's table a render sees
+int rt_set_light_shapes(rt_context* c, int mode) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_LIGHT_SHAPES_SPHERES && mode != RT_LIGHT_SHAPES_ALL)
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "rt_set_light_shapes: %d is neither RT_LIGHT_SHAPES_SPHERES nor RT_LIGHT_SHAPES_ALL", mode);
+    c->light_shapes = mode;
+    return RT_OK;
+}
+
+int rt_get_light_shapes(const rt_context* c) { return c ? c->light_shapes : RT_LIGHT_SHAPES_SPHERES; }
+
 int rt_get_lights(rt_context* c, float* out, int capacity) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
     if (capacity < 0 || (capacity > 0 && !out)) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_get_lights: bad capacity / null out");
-    const int n = (int)(c->scene.lights.size() / RT_LIGHT_FLOATS);
+    const int n = c->n_lights();
     const int k = n < capacity ? n : capacity;
     if (k > 0) std::memcpy(out, c->scene.lights.data(), (size_t)k * RT_LIGHT_FLOATS * sizeof(float));
     return n;

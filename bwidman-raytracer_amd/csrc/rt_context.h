@@ -276,12 +276,21 @@ struct rt_context {
     // returns a table
     int light_picking = RT_LIGHT_PICK_UNIFORM;
     static_assert(RT_PICK_UNIFORM == RT_LIGHT_PICK_UNIFORM && RT_PICK_WEIGHTED == RT_LIGHT_PICK_WEIGHTED, "rt_layout.h / rt_abi.h");
+    // rt_set_light_shapes: which records of the scene's table a render sees, the sphere lights alone or
+    // the polygon lights behind them as well
+    int light_shapes = RT_LIGHT_SHAPES_SPHERES;
+    static_assert(RT_SHAPES_SPHERES == RT_LIGHT_SHAPES_SPHERES && RT_SHAPES_ALL == RT_LIGHT_SHAPES_ALL, "rt_layout.h / rt_abi.h");
+    int n_lights() const {
+        return light_shapes == RT_LIGHT_SHAPES_ALL ? (int)(scene.lights.size() / RT_LIGHT_FLOATS) : scene.n_sphere_lights;
+    }
     // The light table a render at max_bounces takes, or none ({null, 0}: the default estimator, its
     // kernels and launch policy): the switch, and a scene and a depth where the estimators differ (an
     // empty table and max_bounces 0 are bit-identical to the default, rt_light.h)
     rt_nee_args nee_args(int max_bounces) const {
-        if (!light_sampling || scene.lights.empty() || max_bounces <= 0) return {nullptr, 0, 0};
-        return {light_buf.as<const float>(), (int)(scene.lights.size() / RT_LIGHT_FLOATS), light_picking};
+        const int n = n_lights();
+        if (!light_sampling || n == 0 || max_bounces <= 0) return {nullptr, 0, 0, nullptr, 0};
+        const float* tab = light_buf.as<const float>();
+        return {tab, n, light_picking, tab + scene.lights.size(), scene.n_sphere_lights};
     }
     // the frame counter, the moment tracking and the non-uniform state: what
     // frameSum currently holds (rt_accum.h has the rules)

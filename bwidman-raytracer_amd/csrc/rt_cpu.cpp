@@ -71,8 +71,9 @@ void closest_hit_bvh_cpu(const rt_kparams& K, f3 o, f3 d, float& best_t, int& be
 // ray will be traced, the three draws, the direct term of the picked light
 // through a shadow ray, and the suppression of the emission the scattered ray
 // finds on a reachable table light.  The caller takes NEE iff N.n_lights > 0,
-// and PICK (how nee_sample picks its light, rt_light.h) from N.pick.
-template <bool NEE, int PICK>
+// PICK (how nee_sample picks its light, rt_light.h) from N.pick and SHAPES
+// (RT_SHAPES_ALL: the table holds polygon lights) from its record counts.
+template <bool NEE, int PICK, int SHAPES>
 f3 trace_path(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d) {
     // recursion records (code, k, cosAngle; NEE: aux): at most max_bounces + 1 hits
     int rec_code[RT_MAX_LEVELS];
@@ -98,7 +99,7 @@ f3 trace_path(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d)
         if (h[3] != 0.0f) n = normalize3(sub(P, n));  // sphere: centre -> normal
         [[maybe_unused]] int aux = 0;
         if constexpr (NEE) {
-            if (nee_prim >= 0 && light_suppressed(K, N, o, nee_prim, id)) aux = RT_NEE_DROP;
+            if (nee_prim >= 0 && light_suppressed<SHAPES>(K, N, o, nee_prim, id)) aux = RT_NEE_DROP;
             nee_prim = -1;
         }
         f3 scatter;
@@ -112,7 +113,7 @@ f3 trace_path(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d)
             if constexpr (NEE) {
                 const int kind = nee_normal_kind(h[3] != 0.0f, n);
                 if (depth + 1 <= K.max_bounces && N.n_lights > 0 && kind) {
-                    const NeeSample s = nee_sample<PICK>(rs, N, P, n, id, kind);
+                    const NeeSample s = nee_sample<PICK, SHAPES>(rs, N, P, n, id, kind);
                     aux |= RT_NEE_LEVEL | (s.j << RT_NEE_JSHIFT);
                     k = s.k;
                     nee_prim = id;
@@ -148,7 +149,7 @@ f3 trace_path(const rt_kparams& K, const rt_nee_args& N, Xorwow& rs, f3 o, f3 d)
 // Every frame of shard pixel p (Main.cu:285-312 per frame, frames in order),
 // the first one `first`: K.first_frame, or n_p + 1 of a listed pixel of an
 // adaptive call (rt_adaptive.h), whose image the resolve pass writes
-template <bool NEE, int PICK>
+template <bool NEE, int PICK, int SHAPES>
 void render_pixel_as(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
     const int j = (int)(p / K.width);
     const int x = (int)(p - (long)j * K.width);
@@ -174,8 +175,8 @@ void render_pixel_as(const rt_kparams& K, const rt_nee_args& N, long npix, long 
         const f3 jit = random_direction(rs, d0);
         const f3 dcam = normalize3(add(d0, scale(K.jitter, jit)));
         // samplesPerPixel paths from it; the last one is kept (Main.cu:296-298)
-        f3 L = trace_path<NEE, PICK>(K, N, rs, cam, dcam);
-        for (int i = 1; i < K.spp_inner; i++) L = trace_path<NEE, PICK>(K, N, rs, cam, dcam);
+        f3 L = trace_path<NEE, PICK, SHAPES>(K, N, rs, cam, dcam);
+        for (int i = 1; i < K.spp_inner; i++) L = trace_path<NEE, PICK, SHAPES>(K, N, rs, cam, dcam);
         float lx = L.x, ly = L.y, lz = L.z;
         if (K.spp_inner != 1) {  // pixel /= samplesPerPixel: (1.0f / k) * pixel (Math.cuh:91-97)
             const float k = 1.0f / (float)K.spp_inner;
@@ -206,14 +207,22 @@ void render_pixel_as(const rt_kparams& K, const rt_nee_args& N, long npix, long 
     if (K.rgba) K.rgba[p] = tone_map(ax, ay, az, frame - 1u);
 }
 
-// (the estimator is picked once per pixel: rt_set_light_sampling, rt_set_light_picking)
-void render_pixel(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
-    if (N.n_lights > 0 && N.pick == RT_PICK_WEIGHTED)
-        render_pixel_as<true, RT_PICK_WEIGHTED>(K, N, npix, p, first);
-    else if (N.n_lights > 0)
-        render_pixel_as<true, RT_PICK_UNIFORM>(K, N, npix, p, first);
+// (the estimator is picked once per pixel: rt_set_light_sampling, rt_set_light_picking, rt_set_light_shapes)
+template <int SHAPES>
+void render_pixel_nee(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
+    if (N.pick == RT_PICK_WEIGHTED)
+        render_pixel_as<true, RT_PICK_WEIGHTED, SHAPES>(K, N, npix, p, first);
     else
-        render_pixel_as<false, RT_PICK_UNIFORM>(K, N, npix, p, first);
+        render_pixel_as<true, RT_PICK_UNIFORM, SHAPES>(K, N, npix, p, first);
+}
+
+void render_pixel(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
+    if (N.n_lights > N.n_sphere_lights)
+        render_pixel_nee<RT_SHAPES_ALL>(K, N, npix, p, first);
+    else if (N.n_lights > 0)
+        render_pixel_nee<RT_SHAPES_SPHERES>(K, N, npix, p, first);
+    else
+        render_pixel_as<false, RT_PICK_UNIFORM, RT_SHAPES_SPHERES>(K, N, npix, p, first);
 }
 
 // fn(p) for p = 0 .. n-1 in 256-item chunks, which `threads` threads (>= 1; the

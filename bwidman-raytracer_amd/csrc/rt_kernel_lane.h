@@ -86,8 +86,11 @@ __device__ __forceinline__ void store_list_pixel(const rt_kparams& K, long npix,
 // The body of a one-path-per-lane kernel of BLOCK lanes.  N is read only with
 // NEE, L only with LIST.  PICK (NEE only): how nee_sample picks its light
 // (rt_light.h); the weighted pick walks the light table with a wave-uniform
-// index, so its records come through the scalar data path.
-template <int BLOCK, bool HIT_LDS, bool BVH, bool LIST, bool NEE, int PICK = RT_PICK_UNIFORM>
+// index, so its records come through the scalar data path.  SHAPES (NEE only):
+// RT_SHAPES_ALL where the table holds polygon lights (rt_set_light_shapes); the
+// lanes of a wave then pick lights of both kinds, and what follows the sampled
+// direction (the cs test, wc, k, the shadow ray) is nee_sample's one tail.
+template <int BLOCK, bool HIT_LDS, bool BVH, bool LIST, bool NEE, int PICK = RT_PICK_UNIFORM, int SHAPES = RT_SHAPES_SPHERES>
 __device__ __forceinline__ void lane_loop(const rt_kparams& K, const rt_nee_args& N, const rt_list_args& L) {
     constexpr bool INLINE = BVH ? RT_NEE_INLINE_BVH != 0 : RT_NEE_INLINE_BRUTE != 0;
     extern __shared__ float smem[];
@@ -173,7 +176,7 @@ __device__ __forceinline__ void lane_loop(const rt_kparams& K, const rt_nee_args
                 if (h0.w != 0.0f) n = normalize3(sub(P, n));  // sphere: centre -> normal
                 [[maybe_unused]] int aux = 0;
                 if constexpr (NEE) {
-                    if (nee_prim >= 0 && light_suppressed(K, N, o, nee_prim, id)) aux = RT_NEE_DROP;
+                    if (nee_prim >= 0 && light_suppressed<SHAPES>(K, N, o, nee_prim, id)) aux = RT_NEE_DROP;
                     nee_prim = -1;
                 }
                 f3 scatter;
@@ -188,7 +191,7 @@ __device__ __forceinline__ void lane_loop(const rt_kparams& K, const rt_nee_args
                     if constexpr (NEE) {
                         const int kind = nee_normal_kind(h0.w != 0.0f, n);
                         if (depth + 1 <= K.max_bounces && N.n_lights > 0 && kind) {
-                            const NeeSample s = nee_sample<PICK>(px.rs, N, P, n, id, kind);
+                            const NeeSample s = nee_sample<PICK, SHAPES>(px.rs, N, P, n, id, kind);
                             aux |= RT_NEE_LEVEL | (s.j << RT_NEE_JSHIFT);
                             k = s.k;
                             nee_prim = id;

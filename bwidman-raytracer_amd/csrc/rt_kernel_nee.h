@@ -7,7 +7,9 @@
 // the list render takes.  What is this header's own: the entry point with its
 // occupancy target (RT_NEE_WAVES), the launch policy with its 4-dword block-size
 // rule, the kernel's name, and the choice between the uniform and the weighted
-// instantiation (PICK, rt_set_light_picking).  It shares
+// instantiation (PICK, rt_set_light_picking) and between
+// the sphere-only and the polygon-aware one (SHAPES, rt_set_light_shapes;
+// DESIGN.md section 25).  It shares
 // no text with rt_kernel_simple.h's rt_render_kernel, whose instruction stream
 // stays as it is (see there).
 #pragma once
@@ -22,10 +24,10 @@
 #endif
 
 #ifndef RT_FAST
-template <int BLOCK, bool HIT_LDS, bool BVH, bool LIST, int PICK = RT_PICK_UNIFORM>
+template <int BLOCK, bool HIT_LDS, bool BVH, bool LIST, int PICK = RT_PICK_UNIFORM, int SHAPES = RT_SHAPES_SPHERES>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(RT_NEE_WAVES)))
 rt_render_nee_kernel(rt_kparams K, rt_nee_args N, rt_list_args L) {
-    lane_loop<BLOCK, HIT_LDS, BVH, LIST, true, PICK>(K, N, L);
+    lane_loop<BLOCK, HIT_LDS, BVH, LIST, true, PICK, SHAPES>(K, N, L);
 }
 
 namespace {
@@ -33,36 +35,46 @@ namespace {
 // for a list, which is usually a fraction of the frame) at most the resident
 // groups per CU x CUs (rt_lane_grid).  No launch-order feedback, no sky table.
 // PICK: N.pick, which the kernel takes at compile time (rt_set_light_picking).
-template <int BLOCK, bool HIT_LDS, bool BVH, bool LIST, int PICK>
+// SHAPES: RT_SHAPES_ALL iff the table the render sees holds a polygon record.
+template <int BLOCK, bool HIT_LDS, bool BVH, bool LIST, int PICK, int SHAPES>
 hipError_t launch_nee(const rt_kparams& K0, const rt_nee_args& N, const rt_list_args& L, size_t lds, int grid_mult,
                       int num_cus, hipStream_t stream) {
     rt_kparams K = K0;
     if (LIST && grid_mult <= 0) grid_mult = 1;
-    const long grid = rt_lane_grid(reinterpret_cast<const void*>(&rt_render_nee_kernel<BLOCK, HIT_LDS, BVH, LIST, PICK>), BLOCK, lds,
+    const long grid = rt_lane_grid(reinterpret_cast<const void*>(&rt_render_nee_kernel<BLOCK, HIT_LDS, BVH, LIST, PICK, SHAPES>), BLOCK, lds,
                                    LIST ? (long)K.rows * K.width : launch_items(K), grid_mult, num_cus);
     K.rec = nullptr;
     K.rec_stride = (int)(grid * BLOCK);
     K.group_cost = nullptr;
     K.group_order = nullptr;
     K.sky = nullptr;
-    hipLaunchKernelGGL((rt_render_nee_kernel<BLOCK, HIT_LDS, BVH, LIST, PICK>), dim3((unsigned)grid), dim3(BLOCK), lds, stream, K,
-                       N, L);
-    std::snprintf(rt_launched_kernel, sizeof rt_launched_kernel, "rt_render_nee_kernel<%d%s%s%s%s>", BLOCK,
+    hipLaunchKernelGGL((rt_render_nee_kernel<BLOCK, HIT_LDS, BVH, LIST, PICK, SHAPES>), dim3((unsigned)grid), dim3(BLOCK), lds,
+                       stream, K, N, L);
+    std::snprintf(rt_launched_kernel, sizeof rt_launched_kernel, "rt_render_nee_kernel<%d%s%s%s%s%s>", BLOCK,
                   HIT_LDS ? "" : ",hit_global", BVH ? ",bvh" : "", LIST ? ",list" : "",
-                  PICK == RT_PICK_WEIGHTED ? ",weighted" : "");
+                  PICK == RT_PICK_WEIGHTED ? ",weighted" : "", SHAPES == RT_SHAPES_ALL ? ",polygons" : "");
     return hipGetLastError();
 }
 
-template <int BLOCK, bool HIT_LDS, bool BVH>
-hipError_t launch_nee_form(const rt_kparams& K, const rt_nee_args& N, const rt_list_args* L, size_t lds, int grid_mult,
+template <int BLOCK, bool HIT_LDS, bool BVH, int SHAPES>
+hipError_t launch_nee_pick(const rt_kparams& K, const rt_nee_args& N, const rt_list_args* L, size_t lds, int grid_mult,
                            int num_cus, hipStream_t s) {
     const rt_list_args none = {nullptr, nullptr, nullptr};
     if (N.pick == RT_PICK_WEIGHTED) {
-        if (L) return launch_nee<BLOCK, HIT_LDS, BVH, true, RT_PICK_WEIGHTED>(K, N, *L, lds, grid_mult, num_cus, s);
-        return launch_nee<BLOCK, HIT_LDS, BVH, false, RT_PICK_WEIGHTED>(K, N, none, lds, grid_mult, num_cus, s);
+        if (L) return launch_nee<BLOCK, HIT_LDS, BVH, true, RT_PICK_WEIGHTED, SHAPES>(K, N, *L, lds, grid_mult, num_cus, s);
+        return launch_nee<BLOCK, HIT_LDS, BVH, false, RT_PICK_WEIGHTED, SHAPES>(K, N, none, lds, grid_mult, num_cus, s);
     }
-    if (L) return launch_nee<BLOCK, HIT_LDS, BVH, true, RT_PICK_UNIFORM>(K, N, *L, lds, grid_mult, num_cus, s);
-    return launch_nee<BLOCK, HIT_LDS, BVH, false, RT_PICK_UNIFORM>(K, N, none, lds, grid_mult, num_cus, s);
+    if (L) return launch_nee<BLOCK, HIT_LDS, BVH, true, RT_PICK_UNIFORM, SHAPES>(K, N, *L, lds, grid_mult, num_cus, s);
+    return launch_nee<BLOCK, HIT_LDS, BVH, false, RT_PICK_UNIFORM, SHAPES>(K, N, none, lds, grid_mult, num_cus, s);
+}
+
+// (a table without a polygon record, whatever the mode: the sphere-only kernel)
+template <int BLOCK, bool HIT_LDS, bool BVH>
+hipError_t launch_nee_form(const rt_kparams& K, const rt_nee_args& N, const rt_list_args* L, size_t lds, int grid_mult,
+                           int num_cus, hipStream_t s) {
+    if (N.n_lights > N.n_sphere_lights)
+        return launch_nee_pick<BLOCK, HIT_LDS, BVH, RT_SHAPES_ALL>(K, N, L, lds, grid_mult, num_cus, s);
+    return launch_nee_pick<BLOCK, HIT_LDS, BVH, RT_SHAPES_SPHERES>(K, N, L, lds, grid_mult, num_cus, s);
 }
 }  // namespace
 

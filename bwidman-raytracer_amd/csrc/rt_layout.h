@@ -364,12 +364,32 @@ struct rt_list_args {
 // pick modes of nee_sample (rt_light.h; include/rt_abi.h RT_LIGHT_PICK_*)
 #define RT_PICK_UNIFORM 0
 #define RT_PICK_WEIGHTED 1
+// shape modes of nee_sample (rt_light.h; include/rt_abi.h RT_LIGHT_SHAPES_*)
+#define RT_SHAPES_SPHERES 0
+#define RT_SHAPES_ALL 1
+// Polygon lights (rt_set_light_shapes, RT_LIGHT_SHAPES_ALL; DESIGN.md section
+// 25).  The sphere records come first and stay as above; behind them one record
+// per admissible emissive triangle and then per admissible emissive quad
+// (rt_scene.cpp has the rules), in primitive-id order, so the ids of the whole
+// table ascend:
+//   {bounding-sphere centre, R*R, emitted.r, emitted.g, emitted.b, primitive id}
+// What the sampler needs besides lies in `poly`, RT_POLY_LIGHT_FLOATS per
+// polygon record (record n_sphere_lights + i takes block i):
+//   {v0.xyz, A0,  v1.xyz, A1,  v2.xyz, |n|,  v3'.xyz, 0,  n.xyz, 0}
+// v3' = the quad's fourth vertex projected along n into the plane through v0
+// (a triangle: v2 again), A0 and A1 the areas of the halves (v0, v1, v2) and
+// (v0, v2, v3') (a triangle: A1 = 0), n the hit table's normal floats and |n|
+// its float length.
+#define RT_POLY_LIGHT_FLOATS 20
 struct rt_nee_args {
     const float* lights;
     int n_lights;            // 0: the estimator is the default one, bit for bit
     int pick;                // rt_set_light_picking (RT_LIGHT_PICK_*), for the host: the launcher picks the
                              // instantiation and the CPU twin its path by it; no kernel reads it (the
                              // struct's tail padding before: size and the fields in front unchanged)
+    const float* poly;       // polygon lights' sampling data; read only where n_lights > n_sphere_lights
+    int n_sphere_lights;     // records [0, n_sphere_lights) are spheres, [n_sphere_lights, n_lights) polygons; the
+                             // launcher and the CPU twin take the polygon-aware form iff the latter is not empty
 };
 
 // One adaptive call (rt_adaptive.h) over the full width x height frame of a

@@ -61,6 +61,30 @@
 // the first positive-weight light whose running sum (the additions of W, in
 // their order) exceeds u W, or the last positive-weight light.  The path does
 // not depend on the pick: same draws, same rays, same RNG state.
+//
+// Polygon lights (rt_set_light_shapes, RT_LIGHT_SHAPES_ALL; DESIGN.md section
+// 25; SHAPES = RT_SHAPES_ALL below).  Records [n_sphere_lights, n_lights) of the
+// table are emissive triangles and quads (rt_layout.h has the record and the
+// sampling block, rt_scene.cpp which polygons are admitted).  A level draws the
+// same three numbers whatever the kind of the picked light.  For a polygon:
+//   A = A0 + A1, t = u1 A; a quad's second half (v0, v2, v3') is taken when
+//   t >= A0, with u1' = min(1, (t - A0) / A1); else the half (v0, v1, v2) with
+//   u1' = min(1, t / A0)                       (a triangle: A1 = 0, always this)
+//   su = sqrt(u1'), b1 = u2 su, b2 = 1 - su
+//   Q = a + b1 (b - a) + b2 (c - a)            the half (a, b, c); area-uniform
+//   w = Q - P, d2 = w . w, wi = normalize3(w)
+//   cos_l = |n_l . w| / (|n_l| sqrt(d2))       polygons are hit from both sides
+//   omega = A cos_l / (2pi d2)                 the sample's measure in the unit
+//                                              of the sphere's Omega / 2pi
+//   k = (inv_pick omega) wc                    wc as for a sphere
+// and no shadow ray (trace = false, k = 0) unless d2 > 0, cos_l > 0, cs > 0 and
+// k is finite.  The sample is visible iff the shadow ray's closest hit is the
+// polygon.  A polygon light is REACHABLE from a level on primitive `prim` iff
+// prim is not the polygon itself; the suppression asks the same rule, so the
+// direct term integrates exactly the directions on which the scattered ray
+// drops the emission.  Weighted picking weighs a polygon by the sphere formula
+// on the record's bounding sphere with s2 = min(1, R^2 / d2): positive wherever
+// the polygon can contribute (a point inside that sphere included).
 #pragma once
 #include "rt_path.h"
 
@@ -119,8 +143,15 @@ RT_HD bool light_reachable(f3 P, int prim, const LightRec& l, f3& w, float& d2) 
     return prim != l.prim && d2 > l.r2;
 }
 
-// The table index of sphere `prim`, -1 if it is no table light (records are in
-// sphere order: the ids ascend)
+// The same question for a polygon light (record index >= n_sphere_lights)
+RT_HD bool poly_light_reachable(f3 P, int prim, const LightRec& l, f3& w, float& d2) {
+    w = sub(l.c, P);
+    d2 = dot(w, w);
+    return prim != l.prim;
+}
+
+// The table index of primitive `prim`, -1 if it is no table light (records are in
+// primitive order: the ids ascend)
 RT_HD int light_of_prim(const rt_nee_args& N, int prim) {
     int lo = 0, hi = N.n_lights - 1;
     while (lo <= hi) {
@@ -137,12 +168,16 @@ RT_HD int light_of_prim(const rt_nee_args& N, int prim) {
 
 // Suppression: the scattered ray of an NEE level at P on `prim` hit primitive
 // `id`; true when that hit's emitted light is to be dropped
+template <int SHAPES = RT_SHAPES_SPHERES>
 RT_HD bool light_suppressed(const rt_kparams& K, const rt_nee_args& N, f3 P, int prim, int id) {
-    if (id >= K.n_sph) return false;
+    if constexpr (SHAPES == RT_SHAPES_SPHERES)
+        if (id >= K.n_sph) return false;
     const int m = light_of_prim(N, id);
     if (m < 0) return false;
     f3 w;
     float d2;
+    if constexpr (SHAPES == RT_SHAPES_ALL)
+        if (m >= N.n_sphere_lights) return prim != id;
     return light_reachable(P, prim, light_load(N.lights, m), w, d2);
 }
 
@@ -182,7 +217,67 @@ RT_HD float nee_pick_weight(const LightRec& l, f3 P, f3 n, float nl, int prim) {
     return wt > 0.0f ? wt : 0.0f;
 }
 
-template <int PICK>
+// The same weight for a polygon light, on the record's bounding sphere with
+// s2 = min(1, R^2 / d2): P may lie inside that sphere and still be lit
+RT_HD float nee_pick_weight_poly(const LightRec& l, f3 P, f3 n, float nl, int prim) {
+    f3 w;
+    float d2;
+    if (!poly_light_reachable(P, prim, l, w, d2)) return 0.0f;
+    const float s2 = fminf(1.0f, rt_div(l.r2, d2));
+    const float omega = rt_div(s2, 1.0f + rt_sqrt(1.0f - s2));
+    const float cc = rt_div(dot(w, n), rt_sqrt(d2) * nl);
+    const float cb = fmaxf(0.0f, cc) + rt_sqrt(s2);
+    const float pw = fabsf(l.e.x) + fabsf(l.e.y) + fabsf(l.e.z);
+    const float wt = (pw * omega) * cb;
+    return wt > 0.0f ? wt : 0.0f;
+}
+
+// The weight of table light m, whatever its kind (m uniform across a wave)
+template <int SHAPES>
+RT_HD float nee_weight_of(const rt_nee_args& N, int m, f3 P, f3 n, float nl, int prim) {
+    const LightRec l = light_load_uniform(N.lights, m);
+    if constexpr (SHAPES == RT_SHAPES_ALL)
+        if (m >= N.n_sphere_lights) return nee_pick_weight_poly(l, P, n, nl, prim);
+    return nee_pick_weight(l, P, n, nl, prim);
+}
+
+// The direction towards a polygon light's area sample (see the head of this
+// file; q: the light's sampling block): wi and the sample's measure omega;
+// false: not reachable, or the sample cannot contribute (d2 or cos_l not > 0)
+RT_HD bool nee_poly_dir(const float* q, int lprim, f3 P, int prim, float u1, float u2, f3& wi, float& omega) {
+    if (prim == lprim) return false;
+    const float4 q0 = *reinterpret_cast<const float4*>(q);
+    const float4 q1 = *reinterpret_cast<const float4*>(q + 4);
+    const float4 q2 = *reinterpret_cast<const float4*>(q + 8);
+    const float4 q3 = *reinterpret_cast<const float4*>(q + 12);
+    const float4 q4 = *reinterpret_cast<const float4*>(q + 16);
+    const f3 a = mk(q0.x, q0.y, q0.z);
+    f3 b = mk(q1.x, q1.y, q1.z), c = mk(q2.x, q2.y, q2.z);
+    const float a0 = q0.w, a1 = q1.w, nl = q2.w;
+    const float area = a0 + a1;
+    const float t = u1 * area;
+    float uh;
+    if (a1 > 0.0f && t >= a0) {
+        b = c;
+        c = mk(q3.x, q3.y, q3.z);
+        uh = rt_div(t - a0, a1);
+    } else {
+        uh = rt_div(t, a0);
+    }
+    const float su = rt_sqrt(fminf(1.0f, uh));
+    const float b1 = u2 * su, b2 = 1.0f - su;
+    const f3 Q = add(add(a, scale(b1, sub(b, a))), scale(b2, sub(c, a)));
+    const f3 w = sub(Q, P);
+    const float d2 = dot(w, w);
+    if (!(d2 > 0.0f)) return false;
+    const float cl = rt_div(fabsf(dot(mk(q4.x, q4.y, q4.z), w)), nl * rt_sqrt(d2));
+    if (!(cl > 0.0f)) return false;
+    omega = rt_div(area * cl, (2.0f * RT_PI) * d2);
+    wi = normalize3(w);
+    return true;
+}
+
+template <int PICK, int SHAPES = RT_SHAPES_SPHERES>
 RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int prim, int kind) {
     const float u = rand_range(rs, 1.0f);
     const float u1 = rand_range(rs, 1.0f);
@@ -202,7 +297,7 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
         // give the same bits), so none is kept anywhere
         const float nl = kind == 2 ? rt_sqrt(dot(n, n)) : 1.0f;
         float W = 0.0f;
-        for (int m = 0; m < N.n_lights; m++) W = W + nee_pick_weight(light_load_uniform(N.lights, m), P, n, nl, prim);
+        for (int m = 0; m < N.n_lights; m++) W = W + nee_weight_of<SHAPES>(N, m, P, n, nl, prim);
         if (!(W > 0.0f)) {
             s.prim = -1;
             return s;
@@ -210,7 +305,7 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
         const float target = u * W;
         float run = 0.0f, wj = 0.0f;
         for (int m = 0; m < N.n_lights; m++) {
-            const float wt = nee_pick_weight(light_load_uniform(N.lights, m), P, n, nl, prim);
+            const float wt = nee_weight_of<SHAPES>(N, m, P, n, nl, prim);
             if (wt > 0.0f) {
                 run = run + wt;
                 s.j = m;
@@ -222,28 +317,37 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
     }
     const LightRec l = light_load(N.lights, s.j);
     s.prim = l.prim;
-    f3 w;
-    float d2;
-    if (!light_reachable(P, prim, l, w, d2)) return s;
-    const float s2 = rt_div(l.r2, d2);
-    const float cm = rt_sqrt(1.0f - s2);
-    const float omega = rt_div(s2, 1.0f + cm);  // 1 - cos(theta_max) without the cancellation
-    const float ct = 1.0f - u1 * omega;
-    const float st = rt_sqrt(fmaxf(0.0f, 1.0f - ct * ct));
-    const float phi = 2.0f * RT_PI * u2;
-    float sp, cp;
-    rt_sincos(phi, sp, cp);
-    const f3 loc = mk(st * cp, st * sp, ct);
-    // frame around the axis, combined as specular_scatter combines its own; the
-    // tangents here are orthonormal (a cone-uniform wi of unit length needs
-    // them so: specular_scatter's cross products are not normalised, and its
-    // helper axis is parallel to a y-aligned normal)
-    const f3 a = normalize3(w);
-    f3 some = mk(1.0f, 0.0f, 0.0f);
-    if (fabsf(a.x) > 0.9f) some = mk(0.0f, 1.0f, 0.0f);
-    const f3 t1 = normalize3(cross(a, some));
-    const f3 t2 = cross(a, t1);
-    s.wi = mk(dot(mk(t1.x, t2.x, a.x), loc), dot(mk(t1.y, t2.y, a.y), loc), dot(mk(t1.z, t2.z, a.z), loc));
+    float omega;
+    [[maybe_unused]] bool poly = false;
+    if constexpr (SHAPES == RT_SHAPES_ALL) poly = s.j >= N.n_sphere_lights;
+    // (the two kinds meet in one wave: what follows the direction is written once)
+    if (poly) {
+        if (!nee_poly_dir(N.poly + RT_POLY_LIGHT_FLOATS * (size_t)(s.j - N.n_sphere_lights), l.prim, P, prim, u1, u2, s.wi, omega))
+            return s;
+    } else {
+        f3 w;
+        float d2;
+        if (!light_reachable(P, prim, l, w, d2)) return s;
+        const float s2 = rt_div(l.r2, d2);
+        const float cm = rt_sqrt(1.0f - s2);
+        omega = rt_div(s2, 1.0f + cm);  // 1 - cos(theta_max) without the cancellation
+        const float ct = 1.0f - u1 * omega;
+        const float st = rt_sqrt(fmaxf(0.0f, 1.0f - ct * ct));
+        const float phi = 2.0f * RT_PI * u2;
+        float sp, cp;
+        rt_sincos(phi, sp, cp);
+        const f3 loc = mk(st * cp, st * sp, ct);
+        // frame around the axis, combined as specular_scatter combines its own; the
+        // tangents here are orthonormal (a cone-uniform wi of unit length needs
+        // them so: specular_scatter's cross products are not normalised, and its
+        // helper axis is parallel to a y-aligned normal)
+        const f3 a = normalize3(w);
+        f3 some = mk(1.0f, 0.0f, 0.0f);
+        if (fabsf(a.x) > 0.9f) some = mk(0.0f, 1.0f, 0.0f);
+        const f3 t1 = normalize3(cross(a, some));
+        const f3 t2 = cross(a, t1);
+        s.wi = mk(dot(mk(t1.x, t2.x, a.x), loc), dot(mk(t1.y, t2.y, a.y), loc), dot(mk(t1.z, t2.z, a.z), loc));
+    }
     const float cs = dot(s.wi, n);
     if (!(cs > 0.0f)) return s;
     float wc = cs;
@@ -255,6 +359,13 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
         wc = (0.5f * cs) * (1.0f + rt_div(1.0f, g * (q * q)));
     }
     s.k = (inv_pick * omega) * wc;
+    if constexpr (SHAPES == RT_SHAPES_ALL) {
+        // a polygon's omega has no bound (d2 -> 0): an overflown k is no sample
+        if (poly && !(s.k < INFINITY)) {
+            s.k = 0.0f;
+            return s;
+        }
+    }
     s.trace = true;
     return s;
 }

@@ -137,6 +137,103 @@ void compile_polygon(float* q, float* h, const rt_vec3* verts, int nv, const rt_
     cull_sphere(cs, verts, nv, scale);
 }
 
+// The light-table record and the sampling block (rt_layout.h rt_nee_args) of
+// polygon `id`, whose hit-table row is h; false: the polygon is not admissible
+// and stays an emitter that paths find by chance (always unbiased).
+// Admissible: emittance finite and > 0, every vertex finite, the compiled
+// normal n = cross(e0, e1) with finite |n|^2 > 0, both halves of positive area,
+// and for a quad convexity of what polygon_test accepts.  That test intersects
+// the plane through v0 with normal n and asks dot(cross(n, e_k), P - v_k) >= 0
+// of every edge: the accepted region is the quad projected along n into that
+// plane, and it is the projected quad itself exactly when every projected
+// vertex passes every edge's test.  Checked here in double on v0, v1, v2 and
+// v3' (v3 projected); vertex j against edge k for j = k and j = k + 1 is on the
+// edge's line identically (0 up to rounding) and is not asked.
+bool polygon_light(const float* h, const rt_vec3* verts, int nv, const rt_material& m, int id, float* rec, float* blk) {
+    if (!(std::isfinite(m.emittance) && m.emittance > 0.0f)) return false;
+    double v[4][3];
+    for (int k = 0; k < nv; k++) {
+        if (!(std::isfinite(verts[k].x) && std::isfinite(verts[k].y) && std::isfinite(verts[k].z))) return false;
+        v[k][0] = verts[k].x;
+        v[k][1] = verts[k].y;
+        v[k][2] = verts[k].z;
+    }
+    const float nn = h[0] * h[0] + h[1] * h[1] + h[2] * h[2];
+    if (!(std::isfinite(nn) && nn > 0.0f)) return false;
+    const double n[3] = {h[0], h[1], h[2]};
+    auto dot3 = [](const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+    auto cross3 = [](const double* a, const double* b, double* c) {
+        c[0] = a[1] * b[2] - a[2] * b[1];
+        c[1] = a[2] * b[0] - a[0] * b[2];
+        c[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    auto diff = [](const double* a, const double* b, double* c) {
+        for (int i = 0; i < 3; i++) c[i] = a[i] - b[i];
+    };
+    auto half_area = [&](const double* a, const double* b, const double* c) {
+        double p[3], q[3], x[3];
+        diff(b, a, p);
+        diff(c, a, q);
+        cross3(p, q, x);
+        return 0.5 * std::sqrt(dot3(x, x));
+    };
+    double v3p[3] = {v[2][0], v[2][1], v[2][2]};  // a triangle: v2 again
+    if (nv == 4) {
+        double w[3];
+        diff(v[3], v[0], w);
+        const double s = dot3(n, w) / dot3(n, n);
+        for (int i = 0; i < 3; i++) v3p[i] = v[3][i] - s * n[i];
+        const double* pv[4] = {v[0], v[1], v[2], v3p};
+        for (int k = 0; k < 4; k++) {
+            double e[3], in[3];
+            diff(pv[(k + 1) % 4], pv[k], e);
+            cross3(n, e, in);
+            for (int j = 0; j < 4; j++) {
+                if (j == k || j == (k + 1) % 4) continue;
+                double w2[3];
+                diff(pv[j], pv[k], w2);
+                if (!(dot3(in, w2) >= 0.0)) return false;
+            }
+        }
+    }
+    const float a0 = (float)half_area(v[0], v[1], v[2]);
+    const float a1 = nv == 4 ? (float)half_area(v[0], v[2], v3p) : 0.0f;
+    if (!(std::isfinite(a0) && a0 > 0.0f) || (nv == 4 && !(std::isfinite(a1) && a1 > 0.0f))) return false;
+    if (!std::isfinite(a0 + a1)) return false;
+    if (!(std::isfinite((float)v3p[0]) && std::isfinite((float)v3p[1]) && std::isfinite((float)v3p[2]))) return false;
+    const float nl = std::sqrt(nn);
+    // bounding sphere: the vertices' mean and the largest distance from it (as
+    // rounded to float), to the original and the projected vertices
+    double c[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < nv; k++)
+        for (int i = 0; i < 3; i++) c[i] += v[k][i] / nv;
+    const float cf[3] = {(float)c[0], (float)c[1], (float)c[2]};
+    double r2 = 0.0;
+    auto reach = [&](const double* p) {
+        double d2 = 0.0;
+        for (int i = 0; i < 3; i++) d2 += (p[i] - (double)cf[i]) * (p[i] - (double)cf[i]);
+        r2 = std::max(r2, d2);
+    };
+    for (int k = 0; k < nv; k++) reach(v[k]);
+    reach(v3p);
+    float r2f = (float)(r2 * (1.0 + std::ldexp(1.0, -20)));
+    if (!((double)r2f >= r2)) r2f = std::nextafter(r2f, INFINITY);
+    if (!(std::isfinite(cf[0]) && std::isfinite(cf[1]) && std::isfinite(cf[2]) && std::isfinite(r2f) && r2f > 0.0f)) return false;
+    rec[0] = cf[0];
+    rec[1] = cf[1];
+    rec[2] = cf[2];
+    rec[3] = r2f;
+    rec[4] = h[4];
+    rec[5] = h[5];
+    rec[6] = h[6];
+    std::memcpy(&rec[7], &id, 4);
+    const float b[RT_POLY_LIGHT_FLOATS] = {verts[0].x, verts[0].y, verts[0].z, a0,  verts[1].x, verts[1].y, verts[1].z, a1,
+                                           verts[2].x, verts[2].y, verts[2].z, nl,  (float)v3p[0], (float)v3p[1], (float)v3p[2], 0.0f,
+                                           h[0], h[1], h[2], 0.0f};
+    std::memcpy(blk, b, sizeof b);
+    return true;
+}
+
 // ---- BVH over spheres / triangles / quads (large scenes) -------------------
 // Binned-SAH binary tree, emitted as EIGHT threaded (stackless) node arrays,
 // one per ray-direction octant: in array k the children of every node are
@@ -744,6 +841,18 @@ int rt_compile_scene(const rt_scene& scene, const rt_scene_options& opt, rt_comp
     for (int i = 0; i < nq; i++, id++)
         compile_polygon(h.data() + off_quad + (size_t)i * RT_QUAD_FLOATS, hit + (size_t)id * RT_HIT_FLOATS,
                         s->quads[i].vertices, 4, s->quads[i].mat, scale);
+    // polygon lights behind the sphere lights (rt_set_light_shapes): always built, the mode chooses at a render
+    r.n_sphere_lights = (int)(r.lights.size() / RT_LIGHT_FLOATS);
+    {
+        float rec[RT_LIGHT_FLOATS], blk[RT_POLY_LIGHT_FLOATS];
+        auto light = [&](int pid, const rt_vec3* verts, int nv, const rt_material& m) {
+            if (!polygon_light(hit + (size_t)pid * RT_HIT_FLOATS, verts, nv, m, pid, rec, blk)) return;
+            r.lights.insert(r.lights.end(), rec, rec + RT_LIGHT_FLOATS);
+            r.light_polys.insert(r.light_polys.end(), blk, blk + RT_POLY_LIGHT_FLOATS);
+        };
+        for (int i = 0; i < nt; i++) light(ns + np + i, s->triangles[i].vertices, 3, s->triangles[i].mat);
+        for (int i = 0; i < nq; i++) light(ns + np + nt + i, s->quads[i].vertices, 4, s->quads[i].mat);
+    }
     // overflow bounds of the bounded primitives' tests (rt_layout.h ovf_*;
     // a NaN or inf input makes its bound infinite, so no ray is culled and
     // every BVH ray takes the brute-force loop)

@@ -40,9 +40,13 @@ struct rt_compiled_scene {
     int bvh_order_mask = 7;
     float cull_omax = 0.0f, cull_dmax = -1.0f;          // polygon culling bounds (rt_layout.h)
     float ovf_sc = 0.0f, ovf_nm = 0.0f, ovf_im = 0.0f;  // overflow bounds (rt_layout.h)
-    // light table of next-event estimation (rt_layout.h rt_nee_args): RT_LIGHT_FLOATS per emissive sphere;
-    // not part of `data` (a buffer of its own on the context)
+    // light table of next-event estimation (rt_layout.h rt_nee_args): RT_LIGHT_FLOATS per emissive sphere
+    // (the first n_sphere_lights records), then per admissible emissive triangle and quad, whose sampling
+    // blocks (RT_POLY_LIGHT_FLOATS each) are light_polys; not part of `data` (a buffer of its own on the
+    // context: the records, then the blocks)
     std::vector<float> lights;
+    std::vector<float> light_polys;
+    int n_sphere_lights = 0;
 };
 
 // RT_OK, or RT_ERR_UNSUPPORTED with the reason in err; `out` is written only on

@@ -302,13 +302,40 @@ RT_API int rt_get_light_sampling(const rt_context* ctx);
 typedef enum rt_light_pick { RT_LIGHT_PICK_UNIFORM = 0, RT_LIGHT_PICK_WEIGHTED = 1 } rt_light_pick;
 RT_API int rt_set_light_picking(rt_context* ctx, int mode);
 RT_API int rt_get_light_picking(const rt_context* ctx);
-/* The light table the scene compiler built at rt_set_scene: one record of
- * RT_LIGHT_RECORD_FLOATS floats per sphere with finite emittance > 0 and finite
- * radius > 0, in sphere order: {cx, cy, cz, r*r, emitted.r, emitted.g,
- * emitted.b, primitive id as int32 bits}, emitted = emittance * albedo.  (Other
- * emitters are found by chance as ever.)  Returns the number of records (or a
- * negative error) and copies at most `capacity` of them to `out` (may be null
- * with capacity 0). */
+/* Which emitters next-event estimation samples.
+ * RT_LIGHT_SHAPES_SPHERES (the default): the emissive spheres alone, everything
+ * as before this switch, bit for bit.  RT_LIGHT_SHAPES_ALL: emissive triangles
+ * and quads as well — a point uniform on the polygon's area, weighed by
+ * area * cos / distance^2; polygons emit to both sides, as they are hit from
+ * both.  A triangle is sampled when its emittance is finite and > 0, its
+ * vertices are finite and its normal cross(v1 - v0, v2 - v1) is finite and not
+ * 0; a quad when in addition its projection along that normal into the plane
+ * through v0 (what a ray can hit) is convex with both halves (v0, v1, v2) and
+ * (v0, v2, v3) of positive area.  Every other emitter (planes, non-convex
+ * quads, ...) is found by chance as ever, which is always unbiased.  A scene
+ * without such a polygon renders under ALL what it renders under SPHERES, with
+ * the same kernel.  The paths draw the same numbers under both modes (same RNG
+ * state); both are unbiased for the same image, and frames of both may share
+ * one accumulation.  Combines with both pick modes.
+ * The mode acts only while light sampling is on; with it off the value is
+ * stored and changes nothing, bit for bit.  GPU and CPU contexts agree bit for
+ * bit.  Per context; takes effect at the next render; resets neither the
+ * accumulation, nor the frame counter, nor the RNG streams.  Other values
+ * return RT_ERR_INVALID_ARGUMENT. */
+typedef enum rt_light_shapes { RT_LIGHT_SHAPES_SPHERES = 0, RT_LIGHT_SHAPES_ALL = 1 } rt_light_shapes;
+RT_API int rt_set_light_shapes(rt_context* ctx, int mode);
+RT_API int rt_get_light_shapes(const rt_context* ctx);
+/* The light table the scene compiler built at rt_set_scene, as the current
+ * shapes mode sees it: one record of RT_LIGHT_RECORD_FLOATS floats per sphere
+ * with finite emittance > 0 and finite radius > 0, in sphere order: {cx, cy,
+ * cz, r*r, emitted.r, emitted.g, emitted.b, primitive id as int32 bits},
+ * emitted = emittance * albedo; under RT_LIGHT_SHAPES_ALL followed by one
+ * record per sampled triangle and then per sampled quad, in primitive order
+ * (the ids of the whole table ascend): {centre and squared radius of a sphere
+ * that contains the vertices, emitted, primitive id}.  (Other emitters are
+ * found by chance as ever.)  Returns the number of records (or a negative
+ * error) and copies at most `capacity` of them to `out` (may be null with
+ * capacity 0). */
 #define RT_LIGHT_RECORD_FLOATS 8
 RT_API int rt_get_lights(rt_context* ctx, float* out, int capacity);
 
