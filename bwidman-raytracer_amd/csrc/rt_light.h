@@ -318,11 +318,12 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
     const LightRec l = light_load(N.lights, s.j);
     s.prim = l.prim;
     float omega;
+    f3 wi;  // the sample's direction: s.wi only once the sample stands (no sample: k and wi stay 0)
     [[maybe_unused]] bool poly = false;
     if constexpr (SHAPES == RT_SHAPES_ALL) poly = s.j >= N.n_sphere_lights;
     // (the two kinds meet in one wave: what follows the direction is written once)
     if (poly) {
-        if (!nee_poly_dir(N.poly + RT_POLY_LIGHT_FLOATS * (size_t)(s.j - N.n_sphere_lights), l.prim, P, prim, u1, u2, s.wi, omega))
+        if (!nee_poly_dir(N.poly + RT_POLY_LIGHT_FLOATS * (size_t)(s.j - N.n_sphere_lights), l.prim, P, prim, u1, u2, wi, omega))
             return s;
     } else {
         f3 w;
@@ -331,8 +332,11 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
         const float s2 = rt_div(l.r2, d2);
         const float cm = rt_sqrt(1.0f - s2);
         omega = rt_div(s2, 1.0f + cm);  // 1 - cos(theta_max) without the cancellation
-        const float ct = 1.0f - u1 * omega;
-        const float st = rt_sqrt(fmaxf(0.0f, 1.0f - ct * ct));
+        // cos and sin of the polar angle from t = 1 - cos: 1 - ct * ct would cancel for a small light
+        // (at s2 = 1e-6 it leaves nine distinct sines), t (2 - t) keeps every bit of t; t <= omega <= 1
+        const float t = u1 * omega;
+        const float ct = 1.0f - t;
+        const float st = rt_sqrt(t * (2.0f - t));
         const float phi = 2.0f * RT_PI * u2;
         float sp, cp;
         rt_sincos(phi, sp, cp);
@@ -346,9 +350,9 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
         if (fabsf(a.x) > 0.9f) some = mk(0.0f, 1.0f, 0.0f);
         const f3 t1 = normalize3(cross(a, some));
         const f3 t2 = cross(a, t1);
-        s.wi = mk(dot(mk(t1.x, t2.x, a.x), loc), dot(mk(t1.y, t2.y, a.y), loc), dot(mk(t1.z, t2.z, a.z), loc));
+        wi = mk(dot(mk(t1.x, t2.x, a.x), loc), dot(mk(t1.y, t2.y, a.y), loc), dot(mk(t1.z, t2.z, a.z), loc));
     }
-    const float cs = dot(s.wi, n);
+    const float cs = dot(wi, n);
     if (!(cs > 0.0f)) return s;
     float wc = cs;
     if (kind == 2) {
@@ -366,6 +370,7 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
             return s;
         }
     }
+    s.wi = wi;
     s.trace = true;
     return s;
 }

@@ -189,7 +189,10 @@ def test_light_table(bwrt_lib, make, polys):
         assert np.array_equal(rec["emitted"], e)
 
 
-def test_light_table_exclusions(bwrt_lib):
+def exclusion_scene():
+    """dark_07 with seven emissive triangles and seven emissive quads of which the
+    light table admits the first triangle and the first and fourth quad; returns
+    (scene, the admitted primitive ids)."""
     lit = material((1, 1, 1), 5)
     ok_t = [(0, 3, -4), (1, 3, -4), (0, 3, -3)]
     ok_q = [(0, 5, -4), (1, 5, -4), (1, 5, -3), (0, 5, -3)]
@@ -211,11 +214,16 @@ def test_light_table_exclusions(bwrt_lib):
         quad(ok_q, material((1, 1, 1), float("inf"))),
         quad([(0, 5, -4), (1, 5, -4), (2, 5, -4), (0, 5, -3)], lit),       # first half of zero area
     ]
-    scene = with_polygons(dark_07(), tris, quads)
+    scene = with_polygons(dark_07(), tris, quads, name="exclusions")
     ns, npl, nt, _ = scene.counts
     t0, q0 = ns + npl + nt - len(tris), ns + npl + nt
+    return scene, [t0, q0, q0 + 3]
+
+
+def test_light_table_exclusions(bwrt_lib):
+    scene, admitted = exclusion_scene()
     with cpu(bwrt_lib, scene) as r:
-        assert [int(p) for p in r.lights()["prim"]] == [t0, q0, q0 + 3]
+        assert [int(p) for p in r.lights()["prim"]] == admitted
         r.set_light_shapes("spheres")
         assert len(r.lights()) == 0
 

@@ -48,15 +48,29 @@ static void print(const rt_compiled_scene& c) {
                 bits(c.ovf_im));
 }
 
-// usage: prog scene.txt [BWRT_KNOB=value ...] [--then-fail]
+// --lights: the light table of next-event estimation as tools/nee_probe.hip
+// reads it: {n_lights, n_sphere_lights, n_sph, 0}, the records, the polygon blocks
+static bool dump_lights(const rt_compiled_scene& c, const char* path) {
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return false;
+    const int32_t head[4] = {(int32_t)(c.lights.size() / RT_LIGHT_RECORD_FLOATS), c.n_sphere_lights, c.n_sph, 0};
+    bool ok = std::fwrite(head, 4, 4, f) == 4;
+    ok = ok && std::fwrite(c.lights.data(), 4, c.lights.size(), f) == c.lights.size();
+    ok = ok && std::fwrite(c.light_polys.data(), 4, c.light_polys.size(), f) == c.light_polys.size();
+    return std::fclose(f) == 0 && ok;
+}
+
+// usage: prog scene.txt [BWRT_KNOB=value ...] [--then-fail] [--lights out.bin]
 int main(int argc, char** argv) {
     bwrt::SceneData sd;
     const std::string e = bwrt::load_scene(argv[1], sd);
     if (!e.empty()) return std::fprintf(stderr, "%s\n", e.c_str()), 2;
     rt_scene_options opt;
     bool then_fail = false;
+    const char* lights = nullptr;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--then-fail")) { then_fail = true; continue; }
+        if (!std::strcmp(argv[i], "--lights") && i + 1 < argc) { lights = argv[++i]; continue; }
         char* eq = std::strchr(argv[i], '=');
         if (!eq) return 2;
         *eq = 0;
@@ -67,6 +81,7 @@ int main(int argc, char** argv) {
     int rc = rt_compile_scene(view(sd), opt, out, err);
     if (rc) return std::fprintf(stderr, "%d %s\n", rc, err.c_str()), 1;
     print(out);
+    if (lights && !dump_lights(out, lights)) return std::fprintf(stderr, "cannot write %s\n", lights), 2;
     if (then_fail) {
         // 2^24 spheres, the smallest scene the compiler refuses (it does so
         // after it has compiled every primitive record): `out` must stay
@@ -100,15 +115,22 @@ def cases():
     return out
 
 
-@pytest.fixture(scope="module")
-def prog(tmp_path_factory):
-    d = tmp_path_factory.mktemp("scene_compile")
+def compile_program(d):
+    """The stand-alone program built in directory d (tests/test_nee_reference.py
+    builds it too, for its --lights dump)."""
     src = d / "main.cpp"
     src.write_text(PROGRAM)
     exe = d / "scene_compile"
     subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(PKG, "host"),
                     "-I", os.path.join(PKG, "csrc"), "-I", os.path.join(REPO, "include"), "-o", str(exe), str(src),
                     os.path.join(PKG, "csrc", "rt_scene.cpp")], check=True)
+    return exe
+
+
+@pytest.fixture(scope="module")
+def prog(tmp_path_factory):
+    d = tmp_path_factory.mktemp("scene_compile")
+    exe = compile_program(d)
     files = {}
 
     def run(name, make, knobs, *extra):
