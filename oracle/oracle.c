@@ -452,6 +452,26 @@ static int closest_hit(const ray3* in, const orc_scene* sc, hit_info* closest, h
     return hit;
 }
 
+/* Main.cu:240-258: the scattering of one hit, trace_path's own text (the batch
+ * entry point orc_scatter calls it too).  The brdfChoice draw, then the branch's
+ * draws; returns whether the specular branch was taken. */
+static int scatter_step(vec3 in_dir, const hit_info* closest, uint32_t st[6], vec3* scatter, vec3* brdf) {
+    float choice = rand_range(st, 1.0f);
+    if (choice < SPECULAR_CHANCE) {
+        vec3 m = microfacet_normal(closest->mat.roughness, st);
+        m = base_around_normal(m, closest->normal);
+        *scatter = reflect3(in_dir, m);
+        float f = fresnel(neg3(in_dir), m, 1.0f, closest->mat.refractive_index);
+        float s = specular_weight(neg3(in_dir), *scatter, closest->normal, m,
+                                  closest->mat.roughness);
+        *brdf = scale(s * f / SPECULAR_CHANCE, v3(1, 1, 1));
+        return 1;
+    }
+    *scatter = random_direction(st, closest->normal);
+    *brdf = scale((float)(2.0 / (1 - SPECULAR_CHANCE)), closest->mat.albedo);
+    return 0;
+}
+
 static vec3 trace_path(ray3 in, const orc_scene* sc, uint32_t st[6], int bounces,
                        int max_bounces, unsigned long long* queries) { /* Main.cu:208-272 */
     vec3 out = g_background;                                          /* backgroundColor */
@@ -463,19 +483,7 @@ static vec3 trace_path(ray3 in, const orc_scene* sc, uint32_t st[6], int bounces
     if (hit) {                                                        /* :237-269 */
         vec3 emitted = scale(closest.mat.emittance, closest.mat.albedo);
         vec3 scatter, brdf;
-        float choice = rand_range(st, 1.0f);
-        if (choice < SPECULAR_CHANCE) {
-            vec3 m = microfacet_normal(closest.mat.roughness, st);
-            m = base_around_normal(m, closest.normal);
-            scatter = reflect3(in.direction, m);
-            float f = fresnel(neg3(in.direction), m, 1.0f, closest.mat.refractive_index);
-            float s = specular_weight(neg3(in.direction), scatter, closest.normal, m,
-                                      closest.mat.roughness);
-            brdf = scale(s * f / SPECULAR_CHANCE, v3(1, 1, 1));
-        } else {
-            scatter = random_direction(st, closest.normal);
-            brdf = scale((float)(2.0 / (1 - SPECULAR_CHANCE)), closest.mat.albedo);
-        }
+        scatter_step(in.direction, &closest, st, &scatter, &brdf);
         ray3 next = {closest.intersection, scatter};
         vec3 incoming = trace_path(next, sc, st, bounces + 1, max_bounces, queries);
         float cos_angle = dot(scatter, closest.normal);
@@ -564,6 +572,26 @@ static ray3 primary_ray(const orc_scene* sc, const view3* v, int x, int y, int w
     return cam;
 }
 
+/* Main.cu:291: 0.001 * (windowWidth / 1000), double then float */
+static float jitter_of(int width) {
+#if ORC_MUTANT == 1
+    return (float)(0.001 * (width / 1000.0));
+#else
+    return (float)(0.001 * (width / 1000));
+#endif
+}
+
+/* Main.cu:287-292: the frame's jittered, normalised camera ray of pixel (x, y);
+ * random_direction's draws come from st.  orc_render_rows and orc_camera_rays
+ * both call this. */
+static ray3 camera_ray(const orc_scene* sc, const view3* v, int x, int y, int width, int height,
+                       float jitter, uint32_t st[6]) {
+    ray3 cam = primary_ray(sc, v, x, y, width, height);
+    cam.direction = add(cam.direction, scale(jitter, random_direction(st, cam.direction)));
+    cam.direction = normalize3(cam.direction);                        /* :292 */
+    return cam;
+}
+
 int orc_render_rows(const orc_scene* sc, int width, int height, int row_offset,
                     int row_stride, int rows, unsigned first_frame, int passes,
                     int max_bounces, uint32_t* rng, float* accum, uint8_t* rgba,
@@ -572,12 +600,7 @@ int orc_render_rows(const orc_scene* sc, int width, int height, int row_offset,
         passes < 0 || max_bounces < 0 || !rng || !accum || first_frame == 0)
         return -1;
     const view3 view = camera_view(sc, width);
-    /* Main.cu:291: 0.001 * (windowWidth / 1000), double then float */
-#if ORC_MUTANT == 1
-    const float jitter = (float)(0.001 * (width / 1000.0));
-#else
-    const float jitter = (float)(0.001 * (width / 1000));
-#endif
+    const float jitter = jitter_of(width);
     const size_t plane = (size_t)rows * (size_t)width;
     unsigned long long q_total = 0, p_total = 0;
 #ifdef _OPENMP
@@ -598,10 +621,7 @@ int orc_render_rows(const orc_scene* sc, int width, int height, int row_offset,
             vec3 sum = v3(accum[3 * p], accum[3 * p + 1], accum[3 * p + 2]);
             unsigned frame = first_frame;
             for (int f = 0; f < passes; f++, frame++) {
-                ray3 cam = primary_ray(sc, &view, x, y, width, height);
-                cam.direction = add(cam.direction,
-                                    scale(jitter, random_direction(st, cam.direction)));
-                cam.direction = normalize3(cam.direction);            /* :292 */
+                ray3 cam = camera_ray(sc, &view, x, y, width, height, jitter, st);
                 vec3 val = v3(0, 0, 0);
                 for (int i = 0; i < g_spp; i++)                       /* :296-298: assigns */
                     val = trace_path(cam, sc, st, 0, max_bounces, &q);
@@ -674,6 +694,68 @@ int orc_first_hit_rows(const orc_scene* sc, int width, int height, int row_offse
                 dst[k][3 * p + 2] = out[k].z;
             }
         }
+    }
+    return 0;
+}
+
+/* ---------------------------------------------------------------------- */
+/* Per-step entry points (oracle.h): batch wrappers around camera_ray,
+ * closest_hit and scatter_step, the functions orc_render_rows runs.  No
+ * arithmetic of their own. */
+static void put3(float* dst, size_t i, vec3 v) {
+    dst[3 * i] = v.x;
+    dst[3 * i + 1] = v.y;
+    dst[3 * i + 2] = v.z;
+}
+static vec3 get3(const float* src, size_t i) { return v3(src[3 * i], src[3 * i + 1], src[3 * i + 2]); }
+
+int orc_camera_rays(const orc_scene* sc, int width, int height, int n, const int32_t* x,
+                    const int32_t* y, uint32_t* states, float* origin, float* direction) {
+    if (!sc || width <= 0 || height <= 0 || n < 0 || !x || !y || !states || !origin || !direction)
+        return -1;
+    const view3 view = camera_view(sc, width);
+    const float jitter = jitter_of(width);
+    for (int i = 0; i < n; i++) {
+        const ray3 cam = camera_ray(sc, &view, x[i], y[i], width, height, jitter, states + 6 * (size_t)i);
+        put3(origin, (size_t)i, cam.origin);
+        put3(direction, (size_t)i, cam.direction);
+    }
+    return 0;
+}
+
+int orc_closest_hits(const orc_scene* sc, int n, const float* origin, const float* direction,
+                     int32_t* kind, int32_t* index, float* distance, float* intersection,
+                     float* normal, float* material) {
+    if (!sc || n < 0 || !origin || !direction || !kind || !index || !distance || !intersection ||
+        !normal || !material)
+        return -1;
+    for (int i = 0; i < n; i++) {
+        const ray3 in = {get3(origin, (size_t)i), get3(direction, (size_t)i)};
+        hit_info closest;
+        hit_prim which;
+        closest_hit(&in, sc, &closest, &which);
+        kind[i] = which.kind;
+        index[i] = which.index;
+        distance[i] = closest.distance;
+        put3(intersection, (size_t)i, closest.intersection);
+        put3(normal, (size_t)i, closest.normal);
+        memcpy(material + 6 * (size_t)i, &closest.mat, sizeof closest.mat);
+    }
+    return 0;
+}
+
+int orc_scatter(int n, uint32_t* states, const float* incoming, const float* normal,
+                const float* material, int32_t* specular, float* scatter, float* brdf) {
+    if (n < 0 || !states || !incoming || !normal || !material || !specular || !scatter || !brdf)
+        return -1;
+    for (int i = 0; i < n; i++) {
+        hit_info closest = hit_init();
+        closest.normal = get3(normal, (size_t)i);
+        memcpy(&closest.mat, material + 6 * (size_t)i, sizeof closest.mat);
+        vec3 s, b;
+        specular[i] = scatter_step(get3(incoming, (size_t)i), &closest, states + 6 * (size_t)i, &s, &b);
+        put3(scatter, (size_t)i, s);
+        put3(brdf, (size_t)i, b);
     }
     return 0;
 }

@@ -95,6 +95,33 @@ int orc_first_hit_rows(const orc_scene* scene, int width, int height,
                        float* intersection, float* raw_normal, float* unit_normal,
                        float* albedo);
 
+/* Per-step entry points: the three steps of orc_render_rows' path loop, each
+ * for a batch of n independent items, through the very functions the render
+ * runs (no arithmetic of their own).  A driver that advances paths level by
+ * level (tests/nee_path_ref.py) composes them.  states: n x 6 words
+ * {d, v0 .. v4} per item, advanced in place.  Every array is required.
+ * Return 0, or -1 on bad arguments.
+ *
+ * orc_camera_rays: the frame's jittered, normalised camera ray of pixel
+ *   (x[i], y[i]) (Main.cu:287-292: primary ray, random_direction's draws from
+ *   the item's state, the jitter of the render's width, normalize).
+ * orc_closest_hits: the closest hit of ray (origin, direction) by the loop of
+ *   Main.cu:214-234.  kind / index as orc_first_hit_rows; distance,
+ *   intersection and normal are HitInfo's (the normal trace_path shades with:
+ *   unit for a sphere, the raw cross product otherwise); material: the six
+ *   floats of orc_material.  A miss: kind -1, distance INFINITY, the rest 0.
+ * orc_scatter: Main.cu:240-258 for a hit with this normal and material, the
+ *   incoming ray's direction given: the brdfChoice draw, then the branch's own
+ *   draws.  specular: choice < SPECULAR_CHANCE; scatter: the scattered
+ *   direction; brdf: the vector trace_path multiplies the incoming light by. */
+int orc_camera_rays(const orc_scene* scene, int width, int height, int n, const int32_t* x,
+                    const int32_t* y, uint32_t* states, float* origin, float* direction);
+int orc_closest_hits(const orc_scene* scene, int n, const float* origin, const float* direction,
+                     int32_t* kind, int32_t* index, float* distance, float* intersection,
+                     float* normal, float* material);
+int orc_scatter(int n, uint32_t* states, const float* incoming, const float* normal,
+                const float* material, int32_t* specular, float* scatter, float* brdf);
+
 /* backgroundColor (Main.cu:27; {0,0,0} in the reference build) used by the
  * next orc_render_rows / orc_first_hit_rows calls. */
 void orc_set_background(float r, float g, float b);

@@ -46,6 +46,12 @@ def lib():
         L.orc_render_rows.restype = C.c_int
         L.orc_first_hit_rows.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 7
         L.orc_first_hit_rows.restype = C.c_int
+        L.orc_camera_rays.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5
+        L.orc_camera_rays.restype = C.c_int
+        L.orc_closest_hits.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        L.orc_closest_hits.restype = C.c_int
+        L.orc_scatter.argtypes = [C.c_int] + [C.c_void_p] * 7
+        L.orc_scatter.restype = C.c_int
         L.orc_set_background.argtypes = [C.c_float, C.c_float, C.c_float]
         L.orc_set_background.restype = None
         L.orc_set_samples_per_pixel.argtypes = [C.c_int]
@@ -147,6 +153,64 @@ def first_hit(scene, width, height, row_offset=0, row_stride=1, background=(0.0,
     prim = np.where(kind < 0, np.int32(-1), base[np.maximum(kind, 0)] + index).astype(np.int32)
     return {"albedo": albedo, "normal": unit, "depth": depth, "prim": prim,
             "kind": kind, "index": index, "point": point, "raw_normal": raw}
+
+
+# ---- per-step entry points (tests/nee_path_ref.py) ---------------------------------------
+
+def _in(a, dtype, shape):
+    a = np.ascontiguousarray(a, dtype)
+    if a.shape != shape:
+        raise ValueError(f"expected an array of shape {shape}, got {a.shape}")
+    return a
+
+
+def camera_rays(scene, width, height, x, y, states):
+    """orc_camera_rays: the jittered camera rays of pixels (x[i], y[i]) with RNG
+    states (n, 6) {d, v0 .. v4}: (origin (n, 3), direction (n, 3), the states after)."""
+    n = len(x)
+    x, y = _in(x, np.int32, (n,)), _in(y, np.int32, (n,))
+    st = _in(states, np.uint32, (n, 6)).copy()
+    o, d = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+    rc = lib().orc_camera_rays(C.cast(scene.ptr(), C.c_void_p), width, height, n,
+                               *[a.ctypes.data for a in (x, y, st, o, d)])
+    if rc != 0:
+        raise ValueError("orc_camera_rays: bad arguments")
+    return o, d, st
+
+
+def closest_hits(scene, origin, direction):
+    """orc_closest_hits for n rays: a dict of "kind", "index", "prim" (the
+    product's numbering, -1 on a miss) (n,) int32, "distance" (n,), "point",
+    "normal" (unit for a sphere, raw otherwise) (n, 3) and "material" (n, 6:
+    albedo, emittance, roughness, refractive index) float32."""
+    n = len(origin)
+    o, d = _in(origin, np.float32, (n, 3)), _in(direction, np.float32, (n, 3))
+    kind, index = np.empty(n, np.int32), np.empty(n, np.int32)
+    dist, point, normal = np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+    mat = np.empty((n, 6), np.float32)
+    rc = lib().orc_closest_hits(C.cast(scene.ptr(), C.c_void_p), n,
+                                *[a.ctypes.data for a in (o, d, kind, index, dist, point, normal, mat)])
+    if rc != 0:
+        raise ValueError("orc_closest_hits: bad arguments")
+    ns, npl, nt, _ = scene.counts
+    base = np.array([0, ns, ns + npl, ns + npl + nt], np.int32)
+    prim = np.where(kind < 0, np.int32(-1), base[np.maximum(kind, 0)] + index).astype(np.int32)
+    return {"kind": kind, "index": index, "prim": prim, "distance": dist, "point": point, "normal": normal,
+            "material": mat}
+
+
+def scatter(states, incoming, normal, material):
+    """orc_scatter for n hits: (specular (n,) bool, scattered direction (n, 3),
+    brdf (n, 3), the states after)."""
+    n = len(incoming)
+    st = _in(states, np.uint32, (n, 6)).copy()
+    i, nr, m = _in(incoming, np.float32, (n, 3)), _in(normal, np.float32, (n, 3)), _in(material, np.float32, (n, 6))
+    spec = np.empty(n, np.int32)
+    s, b = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+    rc = lib().orc_scatter(n, *[a.ctypes.data for a in (st, i, nr, m, spec, s, b)])
+    if rc != 0:
+        raise ValueError("orc_scatter: bad arguments")
+    return spec != 0, s, b, st
 
 
 def last_counters():

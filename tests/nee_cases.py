@@ -385,6 +385,66 @@ def fold_cases(words, rows=6, n=N):
     return out
 
 
+def kind_edge_cases():
+    """The exact cases of nee_normal_kind: (sphere flag, n, the kind demanded;
+    None: the reference leaves it undecided, any of 0, 1, 2 passes)"""
+    inf, nan, h = np.inf, np.nan, 0.5
+    e = []
+    for n in ((0, 1, 0), (0, 0, -1), (-1, 0, 0), (0.5, 0.5, np.sqrt(0.5))):  # |n|^2 exactly 1 (the last: within rounding, not exact)
+        e.append((0, n, 1 if n[0] != 0.5 else None))
+    e += [(0, (h, h, 0), 0), (0, (0, -h, h), 0),                      # exactly 1/2: no level
+          (0, (h, h, 2.0 ** -12), 2), (0, (h, 2.0 ** -12, -h), 2),     # 1/2 + 2^-24, the float above 1/2
+          (0, (h, h, 2.0 ** -14), None),                               # 1/2 + 2^-28 is no float (it rounds to 1/2): undecided
+          (0, (1, 2.0 ** -12, 0), None),                               # 1 + 2^-24 is no float (it rounds to 1): undecided
+          (0, (1, 2.0 ** -11, 0), 2),                                  # 1 + 2^-22: a float, exact, kind 2
+          (0, (2, 0, 0), 2), (0, (0, 0.8, 0), 2), (0, (0, 0.7, 0), 0), (0, (0, 0, 0), 0), (0, (1e-30, 0, 0), 0),
+          (0, (inf, 0, 0), 0), (0, (0, -inf, 1), 0), (0, (3e19, 3e19, 0), 0), (0, (1e19, 1e19, 1e19), 2),  # +inf, overflow, 3e38
+          (0, (nan, 0, 1), 0), (0, (0, 1, nan), 0), (0, (nan, nan, nan), 0), (0, (inf, nan, 0), 0)]
+    for n in ((0, 1, 0), (0, 0, 0), (h, h, 0), (7, 0, 0), (inf, 0, 0), (nan, 0, 1), (nan, nan, nan), (0.1, 0.1, 0.1)):
+        e.append((1, n, 1))                                            # the sphere flag, whatever n
+    return e
+
+
+def kind_cases(n=N):
+    """cases of nee_normal_kind: {sphere, n}: directions scaled to |n|^2 around
+    1/2, 1 and far from both, the sphere flag on an eighth, the exact cases last"""
+    rng = np.random.default_rng([SEED, 9, 9])
+    nn = rng.choice([0.25, 0.49, 0.5, 0.51, 0.64, 1.0, 1.25, 2.0, 4.0, 40000.0, 1e-12, 1e30], n) * \
+        np.where(rng.random(n) < 0.5, 1.0, 1.0 + rng.normal(size=n) * 2.0 ** -18)
+    nrm = _unit(rng, n) * np.sqrt(nn)[:, None]
+    axis = rng.random(n) < 0.25  # axis-aligned: |n|^2 is one exact square
+    nrm[axis] = np.eye(3)[rng.integers(0, 3, axis.sum())] * np.sqrt(nn[axis])[:, None]
+    sphere = rng.random(n) < 0.125
+    edge = kind_edge_cases()
+    m = len(edge)
+    sphere[n - m:] = [s for s, _, _ in edge]
+    nrm[n - m:] = [v for _, v, _ in edge]
+    out = np.zeros((n, 4), np.uint32)
+    out[:, 0] = sphere
+    with np.errstate(over="ignore"):
+        out[:, 1:4] = R.f32(nrm).view(np.uint32)
+    return out
+
+
+def check_kind(cases, out):
+    """nee_normal_kind against float64 on |n|^2, wherever that decides; the exact cases by name"""
+    want, dec = R.normal_kind(cases[:, 0] != 0, _f(cases[:, 1:4]))
+    got = out.view(np.int32)
+    assert len(got) == len(cases)
+    edge = kind_edge_cases()
+    m = len(edge)
+    demanded = [k for _, _, k in edge]
+    for i, k in enumerate(demanded):  # stated by hand, and the reference agrees with the hand
+        if k is not None:
+            assert dec[len(cases) - m + i] and want[len(cases) - m + i] == k, (edge[i], want[len(cases) - m + i])
+    # (about 8 % of the random cases sit on 1/2 or 1 within 2^-20 on purpose; each kind is a twentieth at the least)
+    assert dec[:len(cases) - m].mean() > 0.8 and all((want[:len(cases) - m] == k).mean() > 0.05 for k in (0, 1, 2))
+    bad = np.nonzero(dec & (got != want))[0]
+    assert len(bad) == 0, ("kind", bad[:8], got[bad[:8]], want[bad[:8]], _f(cases[bad[:8], 1:4]))
+    assert np.isin(got, (0, 1, 2)).all()
+    return int(dec.sum())
+
+
 # ---- the runs ----------------------------------------------------------------------------
 
 # (table, function id): the nee_sample runs; 0 / 1 uniform / weighted over the spheres, 2 / 3 over all shapes
@@ -395,7 +455,7 @@ SAMPLE_RUNS = [(t, f) for t in ("07", "eight_lights") for f in (0, 1)] + DECADE_
               [("decades", 0), ("grid1", 1), ("grid2", 1), ("grid40", 0), ("grid40", 1), ("grid41", 0), ("grid41", 1),
                ("zero_first", 1), ("zero_mid", 1), ("twins", 1), ("underflow", 1), ("exact_r2", 0), ("origin_quad", 2)]
 DIVERGENT_RUN = ("mixed", 3)  # spheres and polygons, all kinds, 7 lights: the weighted break leaves at every m
-OTHER_RUNS = [("eight_lights", 4), ("exact_r2", 4), ("quad_panel", 5), ("mixed", 6), ("mixed", 7), ("07", 8)]
+OTHER_RUNS = [("eight_lights", 4), ("exact_r2", 4), ("quad_panel", 5), ("mixed", 6), ("mixed", 7), ("07", 8), ("07", 9)]
 
 
 def run_inputs(tables, table, fid):
@@ -408,6 +468,8 @@ def run_inputs(tables, table, fid):
         return w, weight_cases(w), None
     if fid in (6, 7):
         return w, suppressed_cases(w), None
+    if fid == 9:
+        return w, kind_cases(), None
     return fold_table(w)[0], fold_cases(w), None
 
 
@@ -573,5 +635,7 @@ def check_run(tables, table, fid, cases, random, out, ref=None):
         return f"{table}/{fid}: {check_weight_values(wt, dec, extra, out)} decided weights, {int((dec & extra).sum())} more ill-conditioned"
     if fid in (6, 7):
         return f"{table}/{fid}: {check_suppressed(w, fid, cases, out)} decided"
+    if fid == 9:
+        return f"{table}/{fid}: {check_kind(cases, out)} decided kinds of {len(cases)}"
     check_fold(w, cases, out)
     return f"{table}/{fid}: equal bits"

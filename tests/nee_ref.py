@@ -484,6 +484,29 @@ def suppressed(t, shapes, P, prim, ident):
     return out, decided
 
 
+# ---- the kind of a normal ---------------------------------------------------------------
+
+def normal_kind(sphere, n):
+    """Whether a hit with normal n can be an NEE level and how its direct term
+    weighs the cosine (rt_light.h "Non-unit normals"): 1 for a sphere's normal
+    (normalised where it is formed) and for |n|^2 == 1 (cs itself), 2 for any
+    other |n|^2 in (1/2, FLT_MAX] (the stretched form), 0 for |n|^2 <= 1/2, a
+    |n|^2 no float holds, or NaN.  Returns (kind, decided): decided False where
+    a float evaluation of |n|^2 may fall on the other side of 1/2, of 1 or of
+    the largest float — closer than DECIDED to it and not exact."""
+    n = np.asarray(n, np.float64)
+    sphere = np.asarray(sphere, bool)
+    with np.errstate(all="ignore"):
+        nn = _dot(n, n)
+        exact = _d2_exact(n, nn)
+        kind = np.where(nn == 1.0, 1, np.where((nn > 0.5) & (nn <= FLT_MAX), 2, 0))
+        near = np.zeros(nn.shape, bool)
+        for edge in (0.5, 1.0, FLT_MAX):
+            near |= np.abs(nn - edge) <= DECIDED * edge
+        decided = sphere | np.isnan(nn) | exact | ~near
+    return np.where(sphere, 1, kind), decided
+
+
 # ---- the fold (exact: float32, one rounding per operation) ------------------------------
 
 RT_NEE_DROP, RT_NEE_LEVEL, RT_NEE_VISIBLE, RT_NEE_JSHIFT = 1, 2, 4, 3

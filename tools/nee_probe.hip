@@ -23,6 +23,7 @@
 //    6  light_suppressed<spheres>              P[3] prim id                    0 / 1
 //    7  light_suppressed<all>
 //    8  fold_level_nee                         c0 k c aux lx ly lz             lx ly lz
+//    9  nee_normal_kind                        sphere n[3]                     kind
 //
 // Every index a case carries (m; the hit row of c0 and the light of aux) is
 // checked against the table before anything runs; ids 0 .. 3 need a light.
@@ -43,9 +44,9 @@
 #include "rt_light.h"
 
 namespace {
-constexpr int kFunctions = 9;
-constexpr int kIn[kFunctions] = {14, 14, 14, 14, 9, 9, 5, 5, 7};
-constexpr int kOut[kFunctions] = {13, 13, 13, 13, 1, 1, 1, 1, 3};
+constexpr int kFunctions = 10;
+constexpr int kIn[kFunctions] = {14, 14, 14, 14, 9, 9, 5, 5, 7, 4};
+constexpr int kOut[kFunctions] = {13, 13, 13, 13, 1, 1, 1, 1, 3, 1};
 
 struct Table {
     int n_lights, n_sphere_lights, n_sph, n_hit;
@@ -110,6 +111,7 @@ RT_HD void eval(int fid, const Table& T, const unsigned* in, unsigned* out) {
             out[0] = bits_of(lx), out[1] = bits_of(ly), out[2] = bits_of(lz);
             break;
         }
+        case 9: out[0] = (unsigned)nee_normal_kind(in[0] != 0u, mk(float_of(in[1]), float_of(in[2]), float_of(in[3]))); break;
         default: break;
     }
 }
