@@ -308,7 +308,7 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
     c->has_scene = true;
     c->view_changed();
     c->st.end_nonuniform();  // a non-uniform accumulation ends with its scene
-    c->tp_has_hist = c->tp_has_pending = false;  // primitive ids change meaning
+    c->vs.drop_history();  // primitive ids change meaning
     return RT_OK;
 }
 
@@ -526,7 +526,7 @@ int rt_init_rand(rt_context* c, int width, int height, int row_offset, int row_s
     const size_t npix = (size_t)rows * width;
     c->new_view();  // the guides are those of one frame shape
     c->st.end_tracking();  // the moments are those of one shard
-    if (width != c->tp_w || height != c->tp_h) c->tp_has_hist = c->tp_has_pending = false;
+    c->vs.set_shape(width, height);  // the history sets are those of one frame shape
     if (!c->cpu) HIP_TRY(c, hipSetDevice(c->device));
     int rc = quiesce(c);  // a render on a caller's stream may still use the state
     const char* oom = "host state for %zu pixels";

@@ -10,6 +10,7 @@
 //   rt_group.h      over this header: lists of shard contexts, block geometry, the _device preamble
 //   rt_scene.cpp    the scene compiler (rt_scene.h; no HIP, no context)
 //   rt_accum.h      the accumulation's host state and its transition table (no HIP)
+//   rt_view.h       the view-bound host state (view, guides, history roles, assembled record) likewise
 // The render kernels: rt_launch.h declares the launchers of their units
 // (rt_kernels{,_bvh,_fast,_bvh_fast,_shared}.hip); one header per kernel
 // (rt_kernel_simple.h, rt_kernel_sorted.h, rt_kernel_pair.h, rt_kernel_refill.h)
@@ -39,6 +40,7 @@
 #include "rt_layout.h"
 #include "rt_scene.h"
 #include "rt_sky.h"
+#include "rt_view.h"
 
 // ---- kernel launchers (the render units': rt_launch.h) ------------------------
 // scalar C++ CPU fallback (rt_cpu.cpp)
@@ -298,35 +300,28 @@ struct rt_context {
     int max_bounces = RT_DEFAULT_MAX_BOUNCES;
     int spp_inner = 1;  // samplesPerPixel, Main.cu:27
 
+    // the view counter, the guides' validity, the roles of the temporal history
+    // sets and the record of the assembled frame (rt_view.h has the rules)
+    rt_view_state vs;
+
     // denoiser (rt_denoise): the first-hit guides of the current full frame
-    // {n.xyz, prim} / {P.xyz, depth}, valid until the scene, the camera or the
-    // frame shape changes, and two ping-pong colour buffers
+    // {n.xyz, prim} / {P.xyz, depth}, valid for one view (`vs`), and two
+    // ping-pong colour buffers
     Buf guide_a, guide_b, dn_col[2], dn_rgba;
     Buf dn_rs;  // rt_denoise_var: the reciprocal luminance sigma, one float per pixel
     Buf aov_a, aov_b, aov_alb;  // rt_render_aov scratch (any shard; GPU contexts)
-    bool guides_valid = false;
     int dn_kernel = -1;  // BWRT_DENOISE_KERNEL: 0 direct, 1 tiled, -1 = the measured per-level policy
 
-    // temporal reprojection (rt_temporal).  `view` counts views: it goes up
-    // wherever guides_valid is cleared.  Two buffer sets {colour + length,
-    // guide copy, camera}: tp[tp_hist] is the history, tp[tp_hist ^ 1] the
-    // pending result of view tp_pending_view; the first call in a later view
-    // swaps them (tp_hist ^= 1).  Nothing is allocated (events included)
-    // before the first call.  rt_temporal_var shares the sets, the view
-    // counting and the promotion: a set it wrote also holds {s2, dof} per pixel
-    // in `mom` (has_mom; a set rt_temporal wrote has none).  The two planes are
-    // allocated by the first rt_temporal_var call only.
+    // temporal reprojection (rt_temporal, rt_temporal_var): two buffer sets
+    // {colour + length, guide copy, {s2, dof}, camera}; which one is the history
+    // and which holds the pending result is `vs`'s to say.  Nothing is allocated
+    // (events included) before the first call, `mom` by the first
+    // rt_temporal_var call only.
     struct TpSet {
         Buf col, ga, gb, mom;
-        bool has_mom = false;
         float cam_pos[3] = {}, rot[9] = {}, screen_z = 0.0f;
     };
-    unsigned long long view = 1;
     TpSet tp[2];
-    int tp_hist = 0;
-    bool tp_has_hist = false, tp_has_pending = false;
-    unsigned long long tp_pending_view = 0;
-    int tp_w = 0, tp_h = 0;  // frame shape of both sets
 
     // luminance moment tracking (rt_set_moments): a copy of frameSum before
     // the last tracked batch (3 planes) and {M, M2} per shard pixel, updated
@@ -334,31 +329,20 @@ struct rt_context {
     // Nothing is allocated before tracking is on and a render runs.
     Buf mom_prev, mom_m;
 
-    // assembled frame (rt_assemble): a full-frame
-    // snapshot {frameSum, optionally {M, M2}, n, J} de-interleaved from the
-    // ranks' gathered blocks, which the full-frame passes read when the
-    // context's own pixel state is a row shard.  It is current while the view,
-    // the width and the height are those of its assembly.  as_block: this
-    // context's exported block, as_gather: the gathered blocks (staging of the
-    // host forms and of rt_assemble_multi).  Nothing is allocated before the
-    // first call.  A COUNTED assembled frame (rt_assemble_adaptive, section
-    // 19; planes 4 or 7) also has `cnt`, {n_p, J_p} per pixel: the passes then
-    // take every pixel's own counts, and frames / batches are the uniform base
-    // that rt_assembled reports.
+    // assembled frame (rt_assemble*, DESIGN.md sections 17 and 19): a full-frame
+    // snapshot {frameSum, optionally {M, M2}, optionally {n_p, J_p}}
+    // de-interleaved from the ranks' gathered blocks, which the full-frame
+    // passes read when the context's own pixel state is a row shard; its record
+    // and whether it is current are `vs`'s to say.  as_block: this context's
+    // exported block, as_gather: the gathered blocks (staging of the host forms
+    // and of rt_assemble_multi).  Nothing is allocated before the first call.
     struct Assembled {
         Buf sum, mom, cnt;
-        bool made = false;
-        int planes = 0, width = 0, height = 0;
-        unsigned frames = 0, batches = 0;
-        unsigned long long view = 0;
-        bool counted() const { return rt_block_shape_of(planes).counted; }
-        bool has_moments() const { return rt_block_shape_of(planes).moments; }
     };
     Assembled as;
     Buf as_block, as_gather;
-    bool assembled_current() const {
-        return as.made && as.view == view && as.width == width && as.height == height;
-    }
+    bool assembled_current() const { return vs.assembled_current(width, height); }
+    rt_block_shape assembled_shape() const { return rt_block_shape_of(vs.assembled().planes); }  // moments, counts
     bool holds_shard() const { return row_offset != 0 || row_stride > 1; }
 
     // adaptive sampling (rt_render_adaptive, rt_adaptive.h).  While `st` is
@@ -411,10 +395,7 @@ struct rt_context {
     hipEvent_t sky_ev = nullptr;  // behind the last upload (created by the first one)
 
     // a new view (scene, camera, frame shape): the guides are stale
-    void new_view() {
-        guides_valid = false;
-        view++;
-    }
+    void new_view() { vs.new_view(); }
     // the scene or the camera changed: the next render restarts the
     // accumulation (Controls.cuh: any movement sets accumulatedFrames = 1), on
     // another image than the launch order and the sky table were made for

@@ -147,8 +147,8 @@ int assemble_pass(rt_context* c, const float* gathered, int shards, int rows_per
     if (!rc && counted) rc = ensure_buf(c, c->as.cnt, npix * sizeof(uint2), oom, npix);
     if (rc) {
         // a buffer of the earlier frame went in the attempt to grow
-        if (!c->as.sum.p || (c->as.has_moments() && !c->as.mom.p) || (c->as.counted() && !c->as.cnt.p))
-            c->as.made = false;
+        const rt_block_shape B = c->assembled_shape();
+        if (!c->as.sum.p || (B.moments && !c->as.mom.p) || (B.counted && !c->as.cnt.p)) c->vs.assembled_drop();
         return rc;
     }
     rt_asm_args A;
@@ -162,7 +162,7 @@ int assemble_pass(rt_context* c, const float* gathered, int shards, int rows_per
     A.mom = moments ? c->as.mom.as<float2>() : nullptr;
     A.block = const_cast<float*>(gathered);
     A.cnt = counted ? c->as.cnt.as<uint2>() : nullptr;
-    c->as.made = false;  // until the pass is queued: a failure leaves no half-written snapshot behind
+    c->vs.assembled_drop();  // until the pass is queued: a failure leaves no half-written snapshot behind
     if (c->cpu) {
         (void)c->assemble.begin(nullptr, true);
         rt_cpu_assemble(A, c->threads);
@@ -174,13 +174,7 @@ int assemble_pass(rt_context* c, const float* gathered, int shards, int rows_per
         HIP_TRY(c, rt_launch_assemble(A, c->deint_blocks, s));
         HIP_TRY(c, c->assemble.end(s));
     }
-    c->as.made = true;
-    c->as.planes = planes;
-    c->as.width = c->width;
-    c->as.height = c->height;
-    c->as.frames = frames;
-    c->as.batches = moments ? batches : 0u;
-    c->as.view = c->view;
+    c->vs.assembled_done(c->width, c->height, planes, frames, moments ? batches : 0u);
     return RT_OK;
 }
 
@@ -326,17 +320,18 @@ int rt_assemble_adaptive_multi(rt_context* const* ctxs, int n, int planes, int d
 
 int rt_assembled(const rt_context* c, unsigned* frames_out, unsigned* batches_out) {
     if (!c || !c->assembled_current()) return 0;
-    if (frames_out) *frames_out = c->as.frames;
-    if (batches_out) *batches_out = c->as.batches;
+    if (frames_out) *frames_out = c->vs.assembled().frames;
+    if (batches_out) *batches_out = c->vs.assembled().batches;
     return 1;
 }
 
 int rt_get_assembled(rt_context* c, float* accum_rgb, float* moments) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (!c->as.made) return fail(c, RT_ERR_INVALID_ARGUMENT, "no assembled frame (rt_assemble first)");
-    if (moments && !c->as.has_moments())
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "the assembled frame has %d planes: no moments", c->as.planes);
-    const size_t npix = (size_t)c->as.height * c->as.width;
+    const rt_view_state::Assembled& a = c->vs.assembled();
+    if (!a.made) return fail(c, RT_ERR_INVALID_ARGUMENT, "no assembled frame (rt_assemble first)");
+    if (moments && !c->assembled_shape().moments)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "the assembled frame has %d planes: no moments", a.planes);
+    const size_t npix = (size_t)a.height * a.width;
     if (c->cpu) {
         if (accum_rgb) planes_to_rgb(c->as.sum.as<float>(), npix, accum_rgb);
         if (moments) std::memcpy(moments, c->as.mom.p, npix * sizeof(float2));
@@ -354,10 +349,11 @@ int rt_get_assembled(rt_context* c, float* accum_rgb, float* moments) {
 
 int rt_get_assembled_counts(rt_context* c, uint32_t* frames_out, uint32_t* batches_out) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (!c->as.made) return fail(c, RT_ERR_INVALID_ARGUMENT, "no assembled frame (rt_assemble_adaptive first)");
-    if (!c->as.counted())
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "the assembled frame has %d planes: no counts", c->as.planes);
-    const size_t npix = (size_t)c->as.height * c->as.width;
+    const rt_view_state::Assembled& a = c->vs.assembled();
+    if (!a.made) return fail(c, RT_ERR_INVALID_ARGUMENT, "no assembled frame (rt_assemble_adaptive first)");
+    if (!c->assembled_shape().counted)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "the assembled frame has %d planes: no counts", a.planes);
+    const size_t npix = (size_t)a.height * a.width;
     const uint2* cn = c->as.cnt.as<uint2>();
     std::vector<uint2> host;
     if (!c->cpu) {
@@ -375,7 +371,7 @@ int rt_get_assembled_counts(rt_context* c, uint32_t* frames_out, uint32_t* batch
 int rt_assemble_drop(rt_context* c) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     // the record only: passes still queued on the buffers are ordered by the next assembly's stream waits
-    c->as.made = false;
+    c->vs.assembled_drop();
     return RT_OK;
 }
 

@@ -54,7 +54,7 @@ int read_back(rt_context* c, size_t npix, uint8_t* rgba_out, const Buf* color, f
 // stream s for a GPU context: part of the denoise call that needs them).  Always
 // of the full width x height view, whatever rows the context's own state holds.
 int ensure_guides(rt_context* c, hipStream_t s) {
-    if (c->guides_valid) return RT_OK;
+    if (c->vs.guides_valid()) return RT_OK;
     rt_kparams K;
     fill_view(c, c->width, c->height, 0, 1, c->height, K);
     const size_t npix = (size_t)c->height * c->width;
@@ -65,7 +65,7 @@ int ensure_guides(rt_context* c, hipStream_t s) {
         rt_cpu_aov(K, c->threads, ga, gb, nullptr);
     else
         HIP_TRY(c, K.bvh_nodes ? rt_launch_aov_bvh(K, ga, gb, nullptr, s) : rt_launch_aov(K, ga, gb, nullptr, s));
-    c->guides_valid = true;
+    c->vs.guides_computed();
     return RT_OK;
 }
 
@@ -87,9 +87,9 @@ struct FrameSrc {
 bool reads_assembled(const rt_context* c) { return c->holds_shard() && c->assembled_current(); }
 FrameSrc frame_src(const rt_context* c) {
     if (reads_assembled(c)) {
-        const bool mom = c->as.has_moments();
-        return {c->as.sum.as<float>(), mom ? c->as.mom.as<float2>() : nullptr, c->as.frames, mom ? c->as.batches : 0u,
-                mom};
+        const rt_view_state::Assembled& a = c->vs.assembled();  // (batches is 0 without moments)
+        const bool mom = c->assembled_shape().moments;
+        return {c->as.sum.as<float>(), mom ? c->as.mom.as<float2>() : nullptr, a.frames, a.batches, mom};
     }
     return {c->accum.as<float>(), c->mom_m.as<float2>(), c->st.frames(), c->st.batches(), c->st.current()};
 }
@@ -102,7 +102,7 @@ int full_frame_check(rt_context* c, const char* who) {
     if (reads_assembled(c)) {
         // a snapshot with its own n >= 1, whatever state the shard's own accumulation is in; one with
         // counts is a non-uniform frame, which the passes take only behind the same switch
-        if (c->as.counted() && !c->st.filters())
+        if (c->assembled_shape().counted && !c->st.filters())
             return fail(c, RT_ERR_UNSUPPORTED,
                         "the assembled frame is non-uniform (rt_assemble_adaptive): %s takes one frame count for all "
                         "pixels (rt_set_adaptive_filters)", who);
@@ -110,7 +110,7 @@ int full_frame_check(rt_context* c, const char* who) {
     }
     const char* shard = "the context holds a row shard (offset %d, stride %d): %s needs a full frame%s";
     // (a stale assembled frame is reported whatever the shard's own frame counter says)
-    if (c->holds_shard() && c->as.made)
+    if (c->holds_shard() && c->vs.assembled().made)
         return fail(c, RT_ERR_UNSUPPORTED, shard, c->row_offset, c->row_stride, who,
                     " (its assembled frame is stale: the view or the frame shape changed since rt_assemble)");
     if (c->st.frame() < 2u || !c->accum.p)
@@ -133,7 +133,7 @@ const uint2* own_counts(const rt_context* c) { return c->st.nonuniform() ? c->ad
 // An assembled frame brings its own or has none: the shard's counts describe
 // other pixels.
 const uint2* frame_counts(const rt_context* c) {
-    if (reads_assembled(c)) return c->as.counted() ? c->as.cnt.as<uint2>() : nullptr;
+    if (reads_assembled(c)) return c->assembled_shape().counted ? c->as.cnt.as<uint2>() : nullptr;
     return own_counts(c);
 }
 
@@ -356,29 +356,18 @@ int temporal_check(rt_context* c, const rt_temporal_params* tp, const rt_denoise
 }
 
 // The history sets at the start of one rt_temporal or rt_temporal_var call (the
-// two share them): a shape change drops them, the first call of a later view
-// promotes the pending result.  Fills the pass T (zeroed by the caller; all but
-// rgba) and the current view K; returns the set the call writes.
-rt_context::TpSet& temporal_sets(rt_context* c, const rt_temporal_params* tp, rt_tp_uniform& T, rt_kparams& K) {
-    if (c->tp_w != c->width || c->tp_h != c->height) {  // (rt_init_rand dropped them already)
-        c->tp_has_hist = c->tp_has_pending = false;
-        c->tp_w = c->width;
-        c->tp_h = c->height;
-    }
-    // the first call of a later view: the pending result becomes the history.
-    // The swap is of host-side roles only; the stream waits above order this
-    // call's kernel after every earlier reader of the set it now writes.
-    if (c->tp_has_pending && c->tp_pending_view != c->view) {
-        c->tp_hist ^= 1;
-        c->tp_has_hist = true;
-        c->tp_has_pending = false;
-    }
-    const rt_context::TpSet& H = c->tp[c->tp_hist];
-    rt_context::TpSet& P = c->tp[c->tp_hist ^ 1];
+// two share them; rt_view.h has the rules).  Fills the pass T (zeroed by the
+// caller; all but rgba) and the current view K; returns the set the call writes
+// and, through `hist`, the history it reads.
+rt_context::TpSet& temporal_sets(rt_context* c, const rt_temporal_params* tp, rt_tp_uniform& T, rt_kparams& K,
+                                 const rt_context::TpSet** hist = nullptr) {
+    c->vs.temporal_start(c->width, c->height);
+    const rt_context::TpSet& H = c->tp[c->vs.history_set()];
+    rt_context::TpSet& P = c->tp[c->vs.pending_set()];
     fill_view(c, c->width, c->height, 0, 1, c->height, K);
     T.width = c->width;
     T.height = c->height;
-    T.has_history = c->tp_has_hist ? 1 : 0;
+    T.has_history = c->vs.has_history() ? 1 : 0;
     const FrameSrc src = frame_src(c);
     T.n = (float)src.frames;
     T.inv = 1.0f / (float)src.frames;
@@ -397,6 +386,7 @@ rt_context::TpSet& temporal_sets(rt_context* c, const rt_temporal_params* tp, rt
     T.p_col = P.col.as<float4>();
     T.p_ga = P.ga.as<float4>();
     T.p_gb = P.gb.as<float4>();
+    if (hist) *hist = &H;
     return P;
 }
 
@@ -405,9 +395,7 @@ void temporal_stored(rt_context* c, rt_context::TpSet& P, const rt_kparams& K, b
     std::memcpy(P.cam_pos, K.cam_pos, sizeof P.cam_pos);
     std::memcpy(P.rot, K.rot, sizeof P.rot);
     P.screen_z = K.screen_z;
-    P.has_mom = has_mom;
-    c->tp_has_pending = true;
-    c->tp_pending_view = c->view;
+    c->vs.temporal_stored(has_mom);
 }
 
 // One temporal call on stream s: promote, reproject, store the pending result
@@ -474,8 +462,8 @@ int temporal_var_pass(rt_context* c, const rt_temporal_params* tp, const rt_deno
     rt_tv_cnt_args V;
     std::memset(&V, 0, sizeof V);
     rt_kparams K;
-    rt_context::TpSet& P = temporal_sets(c, tp, V.t, K);
-    const rt_context::TpSet& H = c->tp[c->tp_hist];
+    const rt_context::TpSet* H;
+    rt_context::TpSet& P = temporal_sets(c, tp, V.t, K, &H);
     V.t.rgba = filter ? nullptr : rgba;  // the filter's last level writes it otherwise
     const FrameSrc src = frame_src(c);
     V.tracked = src.tracked && src.batches >= 2u;
@@ -489,7 +477,7 @@ int temporal_var_pass(rt_context* c, const rt_temporal_params* tp, const rt_deno
         V.dof_c = 0.0f;
         V.mom = src.tracked ? src.mom : nullptr;
     }
-    V.h_mom = H.has_mom ? H.mom.as<float2>() : nullptr;
+    V.h_mom = c->vs.history_has_moments() ? H->mom.as<float2>() : nullptr;
     V.p_mom = P.mom.as<float2>();
     HIP_TRY(c, c->temporal_var.begin(s, true));
     if (c->cpu)
@@ -690,7 +678,7 @@ int rt_temporal_device(rt_context* c, const rt_temporal_params* tp, const rt_den
 int rt_temporal_reset(rt_context* c) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     // roles only: work still queued on the buffers is ordered by the next call's stream waits
-    c->tp_has_hist = c->tp_has_pending = false;
+    c->vs.drop_history();
     return RT_OK;
 }
 

@@ -255,15 +255,15 @@ int reprojected_check(rt_context* c, const rt_adaptive_reprojected_params* p, in
     if (const int rc = params_check(c, &base, max_bounces, false, 1u)) return rc;
     if (!(p->min_dof >= 0.0f))
         return fail(c, RT_ERR_INVALID_ARGUMENT, "bad adaptive params: min_dof %g (>= 0)", (double)p->min_dof);
-    const rt_context::TpSet& P = c->tp[c->tp_hist ^ 1];
-    if (!c->tp_has_pending || c->tp_pending_view != c->view || c->tp_w != c->width || c->tp_h != c->height)
+    if (!c->vs.pending_current(c->width, c->height))
         return fail(c, RT_ERR_INVALID_ARGUMENT,
                     "rt_render_adaptive_reprojected: no pending temporal set of the current view (call "
                     "rt_temporal_var after the render of this view)");
-    if (!P.has_mom)
+    if (!c->vs.pending_has_moments())
         return fail(c, RT_ERR_INVALID_ARGUMENT,
                     "rt_render_adaptive_reprojected: the pending temporal set was written by rt_temporal and has no "
                     "moments (call rt_temporal_var)");
+    const rt_context::TpSet& P = c->tp[c->vs.pending_set()];
     g = Gathered{};
     g.col = P.col.as<float4>();
     g.mom = P.mom.as<float2>();

@@ -12,6 +12,7 @@ import pytest
 
 from bwrt import Renderer, abi, scenes
 import lifecycle_trace
+import view_trace
 from test_adaptive import DEFAULTS, KS, RESTARTS, START, adaptive_sequence, refused_after_restart, start
 
 pytestmark = pytest.mark.gpu
@@ -290,3 +291,15 @@ def test_lifecycle_trace_equals_cpu(bwrt_lib):
         want = lifecycle_trace.trace(bwrt_lib, seed)
         for i, (a, b) in enumerate(zip(got, want)):
             assert a == b, (seed, i)
+
+
+def test_view_trace_equals_cpu(bwrt_lib):
+    """The seeded call sequences of tests/view_trace.py (views, the temporal
+    history sets, the assembled frame of a shard context) on a GPU context:
+    every record equals the CPU context's of the same library."""
+    for seed in view_trace.SEEDS:
+        got = view_trace.trace(bwrt_lib, seed, gpu=True)
+        want = view_trace.trace(bwrt_lib, seed)
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert a == b, (seed, i)
+        assert len(got) == len(want) == view_trace.STEPS
