@@ -132,6 +132,7 @@ RT_LIGHT_PICK_UNIFORM = 0  # rt_set_light_picking
 RT_LIGHT_PICK_WEIGHTED = 1
 RT_LIGHT_SHAPES_SPHERES = 0  # rt_set_light_shapes
 RT_LIGHT_SHAPES_ALL = 1
+RT_LIGHT_NODE_FLOATS = 8  # rt_get_light_tree
 
 _lib = None
 
@@ -164,6 +165,11 @@ def _proto(lib):
         "rt_set_light_shapes": (C.c_int, [vp, C.c_int]),
         "rt_get_light_shapes": (C.c_int, [vp]),
         "rt_get_lights": (C.c_int, [vp, C.POINTER(C.c_float), C.c_int]),
+        "rt_set_light_hierarchy": (C.c_int, [vp, C.c_int]),
+        "rt_get_light_hierarchy": (C.c_int, [vp]),
+        "rt_get_light_tree": (C.c_int, [vp, C.POINTER(C.c_float), C.c_int]),
+        "rt_light_pick_probabilities": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int,
+                                                  C.POINTER(C.c_float)]),
         "rt_set_samples_per_pixel": (C.c_int, [vp, C.c_int]),
         "rt_get_camera": (C.c_int, [vp, P(Camera)]),
         "rt_apply_controls": (C.c_int, [P(Camera), C.c_uint, C.c_float]),

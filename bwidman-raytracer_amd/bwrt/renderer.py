@@ -158,6 +158,56 @@ class Renderer:
             self._check(got)
         return raw[:n].view(dt).reshape(n)
 
+    def set_light_hierarchy(self, on):
+        """rt_set_light_hierarchy: weighted picking descends a binary tree over
+        the light table (at most ceil(log2 n) + 1 levels per bounce) instead of
+        walking the table twice.  Acts only while light sampling is on, picking
+        is "weighted" and the table holds at least 2 lights; accumulation, frame
+        counter and RNG streams stay."""
+        self._check(self.lib.rt_set_light_hierarchy(self.ctx, int(on)))
+
+    @property
+    def light_hierarchy(self) -> bool:
+        return bool(self.lib.rt_get_light_hierarchy(self.ctx))
+
+    def light_tree(self):
+        """rt_get_light_tree: the light tree of the current shapes mode's table
+        as a structured array with fields centre (3 float32), r2, phi and a, b,
+        parent (int32); 2 n - 1 nodes for n >= 2 lights (the internal ones
+        first, node n - 1 + j the leaf of light j), none below that."""
+        dt = np.dtype([("centre", np.float32, 3), ("r2", np.float32), ("phi", np.float32), ("a", np.int32),
+                       ("b", np.int32), ("parent", np.int32)])
+        n = self.lib.rt_get_light_tree(self.ctx, None, 0)
+        if n < 0:
+            self._check(n)
+        raw = np.zeros((max(n, 1), abi.RT_LIGHT_NODE_FLOATS), np.float32)
+        got = self.lib.rt_get_light_tree(self.ctx, raw.ctypes.data_as(C.POINTER(C.c_float)), n)
+        if got < 0:
+            self._check(got)
+        return raw[:n].view(dt).reshape(n)
+
+    def light_pick_probabilities(self, points, prims) -> np.ndarray:
+        """rt_light_pick_probabilities: where the shadow rays go.  points:
+        (count, 6) float32 {P.xyz, n.xyz} (n the shading normal as the path has
+        it), prims: (count,) int32, the primitive each point lies on (-1: none).
+        Returns (count, n_lights) float32: the probability with which the
+        current pick mode (uniform, weighted, or weighted through the light
+        hierarchy) picks each table light there."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 6)
+        ids = np.ascontiguousarray(prims, np.int32).reshape(-1)
+        if len(ids) != len(pts):
+            raise ValueError(f"{len(pts)} points but {len(ids)} primitive ids")
+        n = self.lib.rt_get_lights(self.ctx, None, 0)
+        if n < 0:
+            self._check(n)
+        out = np.zeros((len(pts), n), np.float32)
+        got = self.lib.rt_light_pick_probabilities(self.ctx, pts.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   ids.ctypes.data_as(C.POINTER(C.c_int)), len(pts),
+                                                   out.ctypes.data_as(C.POINTER(C.c_float)))
+        if got < 0:
+            self._check(got)
+        return out
+
     def set_samples_per_pixel(self, n: int):
         """samplesPerPixel (Main.cu:27, 296-299): n paths per frame from one
         jittered camera ray, the last one kept and scaled by 1/n (default 1)."""

@@ -287,6 +287,9 @@ int rt_set_scene(rt_context* c, const rt_scene* s) {
     // the light table: every record, then the polygon lights' sampling blocks
     std::vector<float> ltab(cs.lights);
     ltab.insert(ltab.end(), cs.light_polys.begin(), cs.light_polys.end());
+    // and the two light trees (rt_set_light_hierarchy; rt_context::table_args has the offsets)
+    ltab.insert(ltab.end(), cs.light_tree_spheres.begin(), cs.light_tree_spheres.end());
+    ltab.insert(ltab.end(), cs.light_tree_all.begin(), cs.light_tree_all.end());
     const size_t lbytes = ltab.size() * sizeof(float);
     if (!rc && lbytes) rc = ensure_buf(c, c->light_buf, lbytes, "host light table of %zu bytes", lbytes);
     if (rc) {
@@ -386,6 +389,55 @@ int rt_get_lights(rt_context* c, float* out, int capacity) {
     const int n = c->n_lights();
     const int k = n < capacity ? n : capacity;
     if (k > 0) std::memcpy(out, c->scene.lights.data(), (size_t)k * RT_LIGHT_FLOATS * sizeof(float));
+    return n;
+}
+
+// Likewise: whether the weighted pick descends the light tree (rt_context::table_args)
+int rt_set_light_hierarchy(rt_context* c, int on) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (on != 0 && on != 1) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_set_light_hierarchy: %d is neither 0 nor 1", on);
+    c->light_hierarchy = on != 0;
+    return RT_OK;
+}
+
+int rt_get_light_hierarchy(const rt_context* c) { return c && c->light_hierarchy ? 1 : 0; }
+
+int rt_get_light_tree(rt_context* c, float* out, int capacity) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    if (capacity < 0 || (capacity > 0 && !out)) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_get_light_tree: bad capacity / null out");
+    const std::vector<float>& t = c->light_tree();
+    const int n = (int)(t.size() / RT_LIGHT_NODE_FLOATS);
+    const int k = n < capacity ? n : capacity;
+    if (k > 0) std::memcpy(out, t.data(), (size_t)k * RT_LIGHT_NODE_FLOATS * sizeof(float));
+    return n;
+}
+
+// An introspection call: its device buffers live for the call (a local Buf
+// frees itself), the light table is only read
+int rt_light_pick_probabilities(rt_context* c, const float* points, const int* prims, int count, float* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_set_scene() not called");
+    if (count < 0 || (count > 0 && (!points || !prims || !out)))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_light_pick_probabilities: bad count / null array");
+    const int n = c->n_lights();
+    if (n == 0 || count == 0) return n;
+    const rt_nee_args N = c->table_args(n);
+    if (c->cpu) {
+        rt_cpu_pick_probabilities(N, c->scene.n_sph, points, prims, count, out, c->threads);
+        return n;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t pb = (size_t)count * 6 * sizeof(float), ib = (size_t)count * sizeof(int), ob = (size_t)count * n * sizeof(float);
+    Buf dp, di, dout;
+    HIP_TRY(c, hipMalloc(&dp.p, pb));
+    HIP_TRY(c, hipMalloc(&di.p, ib));
+    HIP_TRY(c, hipMalloc(&dout.p, ob));
+    HIP_TRY(c, hipMemcpyAsync(dp.p, points, pb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(di.p, prims, ib, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, rt_launch_pick_probabilities(N, c->scene.n_sph, dp.as<const float>(), di.as<const int>(), count, dout.as<float>(), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return n;
 }
 

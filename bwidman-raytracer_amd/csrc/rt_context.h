@@ -46,6 +46,9 @@
 // scalar C++ CPU fallback (rt_cpu.cpp)
 // (N.n_lights > 0: the next-event estimator of rt_light.h, here and in rt_cpu_adaptive_render)
 int rt_cpu_render(const rt_kparams& K, const rt_nee_args& N, int threads);
+// rt_light_pick_probabilities on the host: rt_launch_pick_probabilities' twin (host pointers)
+void rt_cpu_pick_probabilities(const rt_nee_args& N, int n_sph, const float* points, const int* prims, int count, float* out,
+                               int threads);
 // adaptive sampling on the host (rt_adaptive.h): selection into A.list /
 // *A.list_n, the listed pixels' frames, their update, the resolve pass
 void rt_cpu_adaptive_select(const rt_ad_args& A, int threads);
@@ -290,9 +293,28 @@ struct rt_context {
     // empty table and max_bounces 0 are bit-identical to the default, rt_light.h)
     rt_nee_args nee_args(int max_bounces) const {
         const int n = n_lights();
-        if (!light_sampling || n == 0 || max_bounces <= 0) return {nullptr, 0, 0, nullptr, 0};
+        if (!light_sampling || n == 0 || max_bounces <= 0) return {nullptr, 0, 0, nullptr, 0, nullptr};
+        return table_args(n);
+    }
+    // rt_set_light_hierarchy: weighted picking descends the light tree of the table form the render sees
+    // (rt_light.h RT_PICK_TREE) instead of walking the table; acts only where picking is weighted and
+    // that table holds at least 2 records (light_buf: records, sampling blocks, then the two trees)
+    bool light_hierarchy = false;
+    // the table of n = n_lights() > 0 records with the pick mode that acts on it (nee_args, and
+    // rt_light_pick_probabilities, which asks whatever the switch and the depth)
+    rt_nee_args table_args(int n) const {
         const float* tab = light_buf.as<const float>();
-        return {tab, n, light_picking, tab + scene.lights.size(), scene.n_sphere_lights};
+        const float* polys = tab + scene.lights.size();
+        if (light_hierarchy && light_picking == RT_LIGHT_PICK_WEIGHTED && n >= 2) {
+            const float* trees = polys + scene.light_polys.size();
+            const float* tree = n > scene.n_sphere_lights ? trees + scene.light_tree_spheres.size() : trees;
+            return {tab, n, RT_PICK_TREE, polys, scene.n_sphere_lights, tree};
+        }
+        return {tab, n, light_picking, polys, scene.n_sphere_lights, nullptr};
+    }
+    // the tree of the current shapes mode's table (empty: fewer than 2 records)
+    const std::vector<float>& light_tree() const {
+        return n_lights() > scene.n_sphere_lights ? scene.light_tree_all : scene.light_tree_spheres;
     }
     // the frame counter, the moment tracking and the non-uniform state: what
     // frameSum currently holds (rt_accum.h has the rules)

@@ -207,10 +207,13 @@ void render_pixel_as(const rt_kparams& K, const rt_nee_args& N, long npix, long 
     if (K.rgba) K.rgba[p] = tone_map(ax, ay, az, frame - 1u);
 }
 
-// (the estimator is picked once per pixel: rt_set_light_sampling, rt_set_light_picking, rt_set_light_shapes)
+// (the estimator is picked once per pixel: rt_set_light_sampling, rt_set_light_picking, rt_set_light_hierarchy,
+// rt_set_light_shapes)
 template <int SHAPES>
 void render_pixel_nee(const rt_kparams& K, const rt_nee_args& N, long npix, long p, unsigned first) {
-    if (N.pick == RT_PICK_WEIGHTED)
+    if (N.pick == RT_PICK_TREE)
+        render_pixel_as<true, RT_PICK_TREE, SHAPES>(K, N, npix, p, first);
+    else if (N.pick == RT_PICK_WEIGHTED)
         render_pixel_as<true, RT_PICK_WEIGHTED, SHAPES>(K, N, npix, p, first);
     else
         render_pixel_as<true, RT_PICK_UNIFORM, SHAPES>(K, N, npix, p, first);
@@ -293,6 +296,20 @@ void rt_cpu_init_rand(unsigned* rng, int width, int rows, int row_offset, int ro
 int rt_cpu_render(const rt_kparams& K, const rt_nee_args& N, int threads) {
     const long npix = (long)K.rows * K.width;
     return parallel_items(npix, threads, [&](long p) { render_pixel(K, N, npix, p, K.first_frame); });
+}
+
+void rt_cpu_pick_probabilities(const rt_nee_args& N, int n_sph, const float* points, const int* prims, int count, float* out,
+                               int threads) {
+    parallel_items(count, threads, [&](long i) {
+        const float* q = points + 6 * i;
+        const int prim = prims[i];
+        const f3 P = mk(q[0], q[1], q[2]), n = mk(q[3], q[4], q[5]);
+        float* row = out + (size_t)i * N.n_lights;
+        if (N.n_lights > N.n_sphere_lights)
+            nee_pick_probabilities<RT_SHAPES_ALL>(N, P, n, prim, prim >= 0 && prim < n_sph, row);
+        else
+            nee_pick_probabilities<RT_SHAPES_SPHERES>(N, P, n, prim, prim >= 0 && prim < n_sph, row);
+    });
 }
 
 // ---- first-hit features and the a-trous filter on the host -------------------

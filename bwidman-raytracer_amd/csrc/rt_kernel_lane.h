@@ -86,7 +86,9 @@ __device__ __forceinline__ void store_list_pixel(const rt_kparams& K, long npix,
 // The body of a one-path-per-lane kernel of BLOCK lanes.  N is read only with
 // NEE, L only with LIST.  PICK (NEE only): how nee_sample picks its light
 // (rt_light.h); the weighted pick walks the light table with a wave-uniform
-// index, so its records come through the scalar data path.  SHAPES (NEE only):
+// index, so its records come through the scalar data path; the tree pick
+// (RT_PICK_TREE) descends the light tree with a node index of the lane's own,
+// vector loads of a small cached table.  SHAPES (NEE only):
 // RT_SHAPES_ALL where the table holds polygon lights (rt_set_light_shapes); the
 // lanes of a wave then pick lights of both kinds, and what follows the sampled
 // direction (the cs test, wc, k, the shadow ray) is nee_sample's one tail.

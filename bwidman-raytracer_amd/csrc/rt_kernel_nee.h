@@ -6,8 +6,9 @@
 // call's list): the loop, the list helpers and the record layout are the ones
 // the list render takes.  What is this header's own: the entry point with its
 // occupancy target (RT_NEE_WAVES), the launch policy with its 4-dword block-size
-// rule, the kernel's name, and the choice between the uniform and the weighted
-// instantiation (PICK, rt_set_light_picking) and between
+// rule, the kernel's name, and the choice between the uniform, the weighted and
+// the tree instantiation (PICK, rt_set_light_picking and rt_set_light_hierarchy;
+// DESIGN.md sections 24 and 29) and between
 // the sphere-only and the polygon-aware one (SHAPES, rt_set_light_shapes;
 // DESIGN.md section 25).  It shares
 // no text with rt_kernel_simple.h's rt_render_kernel, whose instruction stream
@@ -34,7 +35,8 @@ namespace {
 // Launch: the grid covers every item once, or with grid_mult > 0 (and always
 // for a list, which is usually a fraction of the frame) at most the resident
 // groups per CU x CUs (rt_lane_grid).  No launch-order feedback, no sky table.
-// PICK: N.pick, which the kernel takes at compile time (rt_set_light_picking).
+// PICK: N.pick, which the kernel takes at compile time (rt_set_light_picking;
+// RT_PICK_TREE where rt_set_light_hierarchy acts, rt_context::nee_args).
 // SHAPES: RT_SHAPES_ALL iff the table the render sees holds a polygon record.
 template <int BLOCK, bool HIT_LDS, bool BVH, bool LIST, int PICK, int SHAPES>
 hipError_t launch_nee(const rt_kparams& K0, const rt_nee_args& N, const rt_list_args& L, size_t lds, int grid_mult,
@@ -52,7 +54,7 @@ hipError_t launch_nee(const rt_kparams& K0, const rt_nee_args& N, const rt_list_
                        stream, K, N, L);
     std::snprintf(rt_launched_kernel, sizeof rt_launched_kernel, "rt_render_nee_kernel<%d%s%s%s%s%s>", BLOCK,
                   HIT_LDS ? "" : ",hit_global", BVH ? ",bvh" : "", LIST ? ",list" : "",
-                  PICK == RT_PICK_WEIGHTED ? ",weighted" : "", SHAPES == RT_SHAPES_ALL ? ",polygons" : "");
+                  PICK == RT_PICK_WEIGHTED ? ",weighted" : PICK == RT_PICK_TREE ? ",tree" : "", SHAPES == RT_SHAPES_ALL ? ",polygons" : "");
     return hipGetLastError();
 }
 
@@ -60,6 +62,10 @@ template <int BLOCK, bool HIT_LDS, bool BVH, int SHAPES>
 hipError_t launch_nee_pick(const rt_kparams& K, const rt_nee_args& N, const rt_list_args* L, size_t lds, int grid_mult,
                            int num_cus, hipStream_t s) {
     const rt_list_args none = {nullptr, nullptr, nullptr};
+    if (N.pick == RT_PICK_TREE) {
+        if (L) return launch_nee<BLOCK, HIT_LDS, BVH, true, RT_PICK_TREE, SHAPES>(K, N, *L, lds, grid_mult, num_cus, s);
+        return launch_nee<BLOCK, HIT_LDS, BVH, false, RT_PICK_TREE, SHAPES>(K, N, none, lds, grid_mult, num_cus, s);
+    }
     if (N.pick == RT_PICK_WEIGHTED) {
         if (L) return launch_nee<BLOCK, HIT_LDS, BVH, true, RT_PICK_WEIGHTED, SHAPES>(K, N, *L, lds, grid_mult, num_cus, s);
         return launch_nee<BLOCK, HIT_LDS, BVH, false, RT_PICK_WEIGHTED, SHAPES>(K, N, none, lds, grid_mult, num_cus, s);

@@ -30,6 +30,11 @@ hipError_t rt_launch_render_nee(const rt_kparams& K, const rt_nee_args& N, const
 hipError_t rt_launch_render_nee_bvh(const rt_kparams& K, const rt_nee_args& N, const rt_list_args* L, int block, size_t lds,
                                     int grid_mult, int num_cus, hipStream_t s);
 
+// rt_light_pick_probabilities (rt_light_probs.hip): one point {P.xyz, n.xyz} on primitive prims[i] per lane,
+// out count x N.n_lights; device pointers, count > 0, N.n_lights > 0
+hipError_t rt_launch_pick_probabilities(const rt_nee_args& N, int n_sph, const float* points, const int* prims, int count,
+                                        float* out, hipStream_t s);
+
 // ---- the same in both modes (rt_kernels_shared.hip) -----------------------------
 // launch policy: hit table in LDS, 64-lane groups (very deep paths), pair
 // kernel (pair_req: 1 / 0 forces it on / off, BWRT_SPREAD; -1 the policy)

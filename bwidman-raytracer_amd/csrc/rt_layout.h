@@ -364,6 +364,7 @@ struct rt_list_args {
 // pick modes of nee_sample (rt_light.h; include/rt_abi.h RT_LIGHT_PICK_*)
 #define RT_PICK_UNIFORM 0
 #define RT_PICK_WEIGHTED 1
+#define RT_PICK_TREE 2  // internal: weighted picking through the light tree (rt_set_light_hierarchy)
 // shape modes of nee_sample (rt_light.h; include/rt_abi.h RT_LIGHT_SHAPES_*)
 #define RT_SHAPES_SPHERES 0
 #define RT_SHAPES_ALL 1
@@ -381,6 +382,27 @@ struct rt_list_args {
 // (v0, v2, v3') (a triangle: A1 = 0), n the hit table's normal floats and |n|
 // its float length.
 #define RT_POLY_LIGHT_FLOATS 20
+// The light tree (rt_set_light_hierarchy; rt_light.h has the descent, DESIGN.md
+// section 29; rt_scene.cpp builds it): a binary tree over a table of n >= 2
+// records, 2n - 1 nodes of RT_LIGHT_NODE_FLOATS floats.  Nodes [0, n - 1) are
+// internal, the root first and every parent in front of its children; node
+// n - 1 + j is the leaf of table record j.  So a child reference k is a leaf
+// iff k >= n - 1, and the descent reads a leaf's light record, never its node.
+//   {cx, cy, cz, R*R, phi, a, b, parent}       a, b, parent: int32 bits
+// {c, R*R}: a leaf's is its record's; an internal node's is a sphere that
+// contains both children's, rounded outwards so that
+// sqrt(R*R) >= |c - c_child| + sqrt(R*R_child) holds in exact arithmetic on the
+// stored floats.  phi: a leaf's is pw r*r (sphere light) or (pw area) / pi
+// (polygon light, area = A0 + A1 of its sampling block), pw = |e.x| + |e.y| +
+// |e.z|; an internal node's is phi(a) + phi(b), one float addition.  a, b: an
+// internal node's left and right child; a leaf's are {j, -1}.  parent: -1 for
+// the root.  A record whose centre, R*R or phi is not finite is a leaf with
+// phi = 0 that the bounds above it leave out.  With a centre or R*R that is not
+// finite no pick mode gives it a weight; a phi that overflows (emission near
+// 1e30) can belong to a light the table walk still weighs, and the tree then
+// reaches it only through siblings that have power: such inputs are outside
+// what the hierarchy supports.
+#define RT_LIGHT_NODE_FLOATS 8
 struct rt_nee_args {
     const float* lights;
     int n_lights;            // 0: the estimator is the default one, bit for bit
@@ -390,6 +412,9 @@ struct rt_nee_args {
     const float* poly;       // polygon lights' sampling data; read only where n_lights > n_sphere_lights
     int n_sphere_lights;     // records [0, n_sphere_lights) are spheres, [n_sphere_lights, n_lights) polygons; the
                              // launcher and the CPU twin take the polygon-aware form iff the latter is not empty
+    const float* tree;       // the light tree over records [0, n_lights) (above); read only where pick is
+                             // RT_PICK_TREE, which the host sets only with n_lights >= 2 (behind the existing
+                             // fields: none of them moves)
 };
 
 // One adaptive call (rt_adaptive.h) over the full width x height frame of a

@@ -85,6 +85,66 @@
 // drops the emission.  Weighted picking weighs a polygon by the sphere formula
 // on the record's bounding sphere with s2 = min(1, R^2 / d2): positive wherever
 // the polygon can contribute (a point inside that sphere included).
+//
+// The light hierarchy (rt_set_light_hierarchy; PICK =
+// RT_PICK_TREE below).  Weighted picking through a stochastic descent of the
+// binary tree that rt_scene.cpp builds over the table (rt_layout.h has the
+// node: bounding sphere {c, R2}, power phi, children a and b), O(depth) per
+// level where the table walk is O(n).  The same three draws in the same order.
+// The importance of a child reference k at the level's point P (normal n, nl as
+// above, on primitive `prim`), n_lights = N:
+//   k >= N - 1, the leaf of record j = k - (N - 1):
+//     I = w_j, the weight above (nee_pick_weight, or nee_pick_weight_poly for a
+//     polygon record): an unreachable light has I = 0
+//   else, internal node k with sphere {c, R2} and power phi:
+//     w = c - P, d2 = w . w
+//     s2 = min(1, R2 / d2)
+//     cc = (w . n) / (sqrt(d2) nl)
+//     cb = max(0, cc) + sqrt(s2)            the bound of w_j, on the node's sphere
+//     I = (phi / max(d2, R2)) cb            and 0 unless that is > 0
+// The descent starts with the root's children (a, b), inv = 1 and the pick draw
+// u, and at every level:
+//   S = I_a + I_b;  !(S > 0): no pick (below)
+//   t = u S;  the left child a is taken iff I_a > 0 and (t < I_a or !(I_b > 0)),
+//   else the right child b; I_c the importance of the child taken
+//   u = min(1, t / I_a) (left), min(1, (t - I_a) / I_b) (right): the one draw,
+//       rescaled into the branch taken
+//   inv = inv (S / I_c)
+//   a leaf: j is its record and inv_pick = inv, where the table walk has W / w_j;
+//   else (a, b) = the children of the node taken, and the next level.
+// No pick (!(S > 0) at some level): the direct term is 0 without a shadow ray,
+// the level stays an NEE level (the suppression stays on) and j is the uniform
+// formula's, as with !(W > 0) of the table walk.  Below the root this happens
+// without any underflow: a node has importance wherever its sphere is seen, its
+// leaves only where they are reachable and have power (P on one leaf and inside
+// its sibling; a zero-power sibling).  Every light below such a level has
+// w_j = 0, so the picks that end there are lost to no light that could
+// contribute; the p_j of a point then sum to less than 1.
+// Unbiased: light j is picked with probability p_j = prod (I_c / S) over its
+// levels, 1 / inv up to rounding, and the estimator divides by it; what has to
+// hold is p_j > 0 wherever w_j > 0.  The last factor is w_j itself.  Above it,
+// every ancestor's sphere contains the light's bounding sphere (rt_layout.h: in
+// exact arithmetic on the stored floats), so the cone of its sphere from P
+// contains the light's cone (all directions where P is inside it: s2 = 1): its
+// cb bounds the largest cosine in that cone from above, so it is >= the
+// light's own and > 0 (cb >= sqrt(s2) > 0 for every finite P in any case); its
+// phi is a sum that holds the light's own > 0 (w_j > 0 needs pw > 0), and
+// max(d2, R2) is finite.  So I > 0 on
+// the whole way down, except by underflow of phi / max(d2, R2) or of the
+// product with cb (and a sibling's I overflowing S, which takes phi near
+// FLT_MAX).  Underflow: a child whose I rounds to 0 is not taken while its
+// sibling has I > 0, and both at 0 is the no-pick rule; the lights below lose
+// their direct term there and the suppression still drops their emission, a
+// bias bounded by their share of the light at P, which is below 2^-126 of the
+// sibling's by the definition of underflow.
+// Resolution: u is a multiple of 2^-24, and a branch of probability p keeps
+// 24 + log2(p) bits of it, so after the whole descent u S of the last level
+// still resolves 2^-24 / p_j of the leaf: a light is reached by
+// about p_j 2^24 values of u, as in the table walk's u W, whatever the depth
+// (at most ceil(log2 N) + 1); lights with p_j < 2^-24 are reached by u = 0 at
+// most.  Each rescaling division adds half an ulp to u, d ulps over d levels.
+// Everything behind the pick is the table walk's: the cone or area sample, wc,
+// the overflow guard, the record and the fold.
 #pragma once
 #include "rt_path.h"
 
@@ -241,6 +301,117 @@ RT_HD float nee_weight_of(const rt_nee_args& N, int m, f3 P, f3 n, float nl, int
     return nee_pick_weight(l, P, n, nl, prim);
 }
 
+// A child of the light tree as the descent sees it (see the head of this file):
+// its importance at the level's point, > 0 or exactly 0, and an internal node's
+// own children (a leaf: a = its record, b = -1)
+struct TreeChild {
+    float imp;
+    int a, b;
+};
+
+// Child reference k differs from lane to lane: vector loads of a small table
+template <int SHAPES>
+RT_HD TreeChild tree_child(const rt_nee_args& N, int k, f3 P, f3 n, float nl, int prim) {
+    TreeChild c;
+    const int j = k - (N.n_lights - 1);
+    if (j >= 0) {
+        const LightRec l = light_load(N.lights, j);
+        [[maybe_unused]] bool poly = false;
+        if constexpr (SHAPES == RT_SHAPES_ALL) poly = j >= N.n_sphere_lights;
+        c.imp = poly ? nee_pick_weight_poly(l, P, n, nl, prim) : nee_pick_weight(l, P, n, nl, prim);
+        c.a = j;
+        c.b = -1;
+        return c;
+    }
+    const float4 s = *reinterpret_cast<const float4*>(N.tree + RT_LIGHT_NODE_FLOATS * (size_t)k);
+    const float4 q = *reinterpret_cast<const float4*>(N.tree + RT_LIGHT_NODE_FLOATS * (size_t)k + 4);
+    const f3 w = sub(mk(s.x, s.y, s.z), P);
+    const float d2 = dot(w, w);
+    const float s2 = fminf(1.0f, rt_div(s.w, d2));
+    const float cc = rt_div(dot(w, n), rt_sqrt(d2) * nl);
+    const float cb = fmaxf(0.0f, cc) + rt_sqrt(s2);
+    const float imp = rt_div(q.x, fmaxf(d2, s.w)) * cb;
+    c.imp = imp > 0.0f ? imp : 0.0f;
+    c.a = rt_f2i(q.y);
+    c.b = rt_f2i(q.z);
+    return c;
+}
+
+// The descent (see the head of this file): true with the leaf's record j and
+// inv = 1 / (the probability of ending there), false where some level has no
+// importance (j and inv are then not to be used).  FORCED, for
+// nee_pick_probabilities: no draw; bit i of `path` takes the right child at
+// level i, and a child of importance 0 on the way is no pick either.  One loop
+// with one live node; the children of the node taken come with its importance.
+template <int SHAPES, bool FORCED = false>
+RT_HD bool tree_descend(const rt_nee_args& N, f3 P, f3 n, float nl, int prim, float u, unsigned long long path, int& j,
+                        float& inv) {
+    const float4 root = *reinterpret_cast<const float4*>(N.tree + 4);
+    int a = rt_f2i(root.y), b = rt_f2i(root.z);
+    inv = 1.0f;
+    while (true) {
+        const TreeChild l = tree_child<SHAPES>(N, a, P, n, nl, prim);
+        const TreeChild r = tree_child<SHAPES>(N, b, P, n, nl, prim);
+        const float S = l.imp + r.imp;
+        if (!(S > 0.0f)) return false;
+        const float t = u * S;
+        bool left = l.imp > 0.0f && (t < l.imp || !(r.imp > 0.0f));
+        if constexpr (FORCED) {
+            left = !(path & 1ull);
+            path >>= 1;
+        }
+        const float ic = left ? l.imp : r.imp;
+        if constexpr (FORCED)
+            if (!(ic > 0.0f)) return false;
+        u = fminf(1.0f, rt_div(left ? t : t - l.imp, ic));
+        inv = inv * rt_div(S, ic);
+        const int k = left ? a : b;
+        if (k >= N.n_lights - 1) {
+            j = k - (N.n_lights - 1);
+            return true;
+        }
+        a = left ? l.a : r.a;
+        b = left ? l.b : r.b;
+    }
+}
+
+// rt_light_pick_probabilities: the probability with which an NEE level at P
+// (normal n, on primitive `prim`, a sphere's or not) picks each table light
+// under N.pick, out[0 .. n_lights), from the functions nee_sample picks with:
+// 1 / n (uniform), w_j / W (weighted), 1 / inv of the descent forced to light
+// j's leaf (tree).  All 0 where the pick rule gives no direct term (!(W > 0),
+// no pick), and where a hit with this normal is no NEE level.
+template <int SHAPES>
+RT_HD void nee_pick_probabilities(const rt_nee_args& N, f3 P, f3 n, int prim, bool sphere, float* out) {
+    const int kind = nee_normal_kind(sphere, n);
+    const float nl = kind == 2 ? rt_sqrt(dot(n, n)) : 1.0f;
+    float W = 0.0f;
+    if (kind && N.pick == RT_PICK_WEIGHTED)
+        for (int m = 0; m < N.n_lights; m++) W = W + nee_weight_of<SHAPES>(N, m, P, n, nl, prim);
+    for (int m = 0; m < N.n_lights; m++) {
+        float p = 0.0f;
+        if (!kind) {
+        } else if (N.pick == RT_PICK_TREE) {
+            // the way to leaf m, read upwards: bit 0 ends as the root's branch
+            unsigned long long path = 0ull;
+            int k = N.n_lights - 1 + m;
+            for (int up = rt_f2i(N.tree[RT_LIGHT_NODE_FLOATS * (size_t)k + 7]); up >= 0;
+                 up = rt_f2i(N.tree[RT_LIGHT_NODE_FLOATS * (size_t)k + 7])) {
+                path = (path << 1) | (rt_f2i(N.tree[RT_LIGHT_NODE_FLOATS * (size_t)up + 6]) == k ? 1ull : 0ull);
+                k = up;
+            }
+            int j;
+            float inv;
+            if (tree_descend<SHAPES, true>(N, P, n, nl, prim, 0.0f, path, j, inv)) p = rt_div(1.0f, inv);
+        } else if (N.pick == RT_PICK_WEIGHTED) {
+            if (W > 0.0f) p = rt_div(nee_weight_of<SHAPES>(N, m, P, n, nl, prim), W);
+        } else {
+            p = rt_div(1.0f, (float)N.n_lights);
+        }
+        out[m] = p;
+    }
+}
+
 // The direction towards a polygon light's area sample (see the head of this
 // file; q: the light's sampling block): wi and the sample's measure omega;
 // false: not reachable, or the sample cannot contribute (d2 or cos_l not > 0)
@@ -314,6 +485,15 @@ RT_HD NeeSample nee_sample(Xorwow& rs, const rt_nee_args& N, f3 P, f3 n, int pri
             }
         }
         inv_pick = rt_div(W, wj);
+    }
+    if constexpr (PICK == RT_PICK_TREE) {
+        const float nl = kind == 2 ? rt_sqrt(dot(n, n)) : 1.0f;
+        int jt;
+        if (!tree_descend<SHAPES>(N, P, n, nl, prim, u, 0ull, jt, inv_pick)) {
+            s.prim = -1;
+            return s;
+        }
+        s.j = jt;
     }
     const LightRec l = light_load(N.lights, s.j);
     s.prim = l.prim;

@@ -234,6 +234,170 @@ bool polygon_light(const float* h, const rt_vec3* verts, int nv, const rt_materi
     return true;
 }
 
+// ---- the light tree (rt_layout.h RT_LIGHT_NODE_FLOATS; rt_set_light_hierarchy) ----
+// A binary tree over records [0, n) of the light table, n >= 2.  A node's
+// records are sorted along each axis by their centres (ties and non-finite
+// centres by table index, so the build is deterministic) and split where
+//   phi_left area_left + phi_right area_right
+// is smallest over the three axes and the admissible positions: phi the summed
+// leaf power of a side, area the surface of the box around its spheres — what
+// Conty Estevez and Kulla's heuristic keeps of the surface-area heuristic when
+// emitters have no orientation.  Admissible: both sides fit the depth that is
+// left, 2^(budget - 1) records each, the root's budget being
+// ceil(log2 n) + 1 levels; so no leaf lies deeper than that.  Internal nodes
+// are numbered in preorder, the root 0; the bounds are merged on the way back
+// up, in double on the children's stored floats, and rounded outwards.
+struct LightTreeBuild {
+    const float* lights;
+    int n;
+    float* out;  // (2n - 1) * RT_LIGHT_NODE_FLOATS, the leaves filled in
+    int next = 0;
+    std::vector<char> ok;  // the node's sphere is finite
+};
+
+void light_tree_put_int(float* slot, int v) { std::memcpy(slot, &v, 4); }
+
+struct LightBox {
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, phi = 0.0;
+    void add(const float* node) {  // a leaf node with a finite sphere
+        const double r = std::sqrt((double)node[3]);
+        for (int a = 0; a < 3; a++) {
+            lo[a] = std::min(lo[a], node[a] - r);
+            hi[a] = std::max(hi[a], node[a] + r);
+        }
+        phi += node[4];
+    }
+    double cost() const {
+        if (!(hi[0] >= lo[0])) return 0.0;  // empty
+        const double x = hi[0] - lo[0], y = hi[1] - lo[1], z = hi[2] - lo[2];
+        return phi * (2.0 * (x * y + y * z + z * x));
+    }
+};
+
+int light_tree_node(LightTreeBuild& B, int* idx, int count, int parent, int budget) {
+    if (count == 1) {
+        const int k = B.n - 1 + idx[0];
+        light_tree_put_int(B.out + (size_t)RT_LIGHT_NODE_FLOATS * k + 7, parent);
+        return k;
+    }
+    const int k = B.next++;
+    auto leaf = [&](int j) { return B.out + (size_t)RT_LIGHT_NODE_FLOATS * ((size_t)B.n - 1 + j); };
+    const long cap = 1L << (budget - 1);  // records a side may hold
+    const int first = (int)std::max(1L, (long)count - cap), last = (int)std::min((long)count - 1, cap);
+    std::vector<int> order(idx, idx + count);
+    std::vector<double> right((size_t)count + 1);
+    // (key, table index) is a total order: sorting again along an axis gives the same sequence
+    auto sort_along = [&](int axis) {
+        auto key = [&](int j) { return B.ok[(size_t)B.n - 1 + j] ? leaf(j)[axis] : INFINITY; };
+        std::sort(order.begin(), order.end(), [&](int p, int q) {
+            const float kp = key(p), kq = key(q);
+            return kp < kq || (kp == kq && p < q);
+        });
+    };
+    int half = (count + 1) / 2, best_axis = -1;  // (no finite cost anywhere: the median in table order)
+    double best = INFINITY;
+    for (int axis = 0; axis < 3; axis++) {
+        sort_along(axis);
+        LightBox r;
+        right[(size_t)count] = 0.0;
+        for (int i = count - 1; i >= 1; i--) {
+            if (B.ok[(size_t)B.n - 1 + order[i]]) r.add(leaf(order[i]));
+            right[(size_t)i] = r.cost();
+        }
+        LightBox l;
+        for (int i = 1; i <= last; i++) {  // i records on the left
+            if (B.ok[(size_t)B.n - 1 + order[i - 1]]) l.add(leaf(order[i - 1]));
+            const double c = l.cost() + right[(size_t)i];
+            if (i >= first && c < best) {
+                best = c;
+                half = i;
+                best_axis = axis;
+            }
+        }
+    }
+    if (best_axis >= 0) {
+        sort_along(best_axis);
+        std::copy(order.begin(), order.end(), idx);
+    }
+    const int a = light_tree_node(B, idx, half, k, budget - 1);
+    const int b = light_tree_node(B, idx + half, count - half, k, budget - 1);
+    float* nd = B.out + (size_t)RT_LIGHT_NODE_FLOATS * k;
+    const float* na = B.out + (size_t)RT_LIGHT_NODE_FLOATS * a;
+    const float* nb = B.out + (size_t)RT_LIGHT_NODE_FLOATS * b;
+    float sph[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    bool ok = B.ok[a] || B.ok[b];
+    if (B.ok[a] && B.ok[b]) {
+        // the smallest sphere around both, its centre rounded to float; then the
+        // radius that reaches both children from that centre
+        double ca[3], cb[3], d2 = 0.0;
+        for (int i = 0; i < 3; i++) {
+            ca[i] = na[i];
+            cb[i] = nb[i];
+            d2 += (cb[i] - ca[i]) * (cb[i] - ca[i]);
+        }
+        const double d = std::sqrt(d2), ra = std::sqrt((double)na[3]), rb = std::sqrt((double)nb[3]);
+        double t = 0.0;  // the centre at ca + t (cb - ca)
+        if (d + rb <= ra)
+            t = 0.0;
+        else if (d + ra <= rb)
+            t = 1.0;
+        else
+            t = (0.5 * (d + ra + rb) - ra) / d;
+        double da2 = 0.0, db2 = 0.0;
+        for (int i = 0; i < 3; i++) {
+            sph[i] = (float)(ca[i] + t * (cb[i] - ca[i]));
+            da2 += ((double)sph[i] - ca[i]) * ((double)sph[i] - ca[i]);
+            db2 += ((double)sph[i] - cb[i]) * ((double)sph[i] - cb[i]);
+        }
+        const double R = std::max(std::sqrt(da2) + ra, std::sqrt(db2) + rb);
+        const double R2 = R * R * (1.0 + std::ldexp(1.0, -20));
+        float r2f = (float)R2;
+        if (!((double)r2f >= R2)) r2f = std::nextafter(r2f, INFINITY);
+        sph[3] = std::isfinite(r2f) ? r2f : 3.4028234663852886e38f;  // (coordinates beyond float's square root)
+    } else if (ok) {
+        std::memcpy(sph, B.ok[a] ? na : nb, sizeof sph);
+    }
+    B.ok[k] = ok;
+    std::memcpy(nd, sph, sizeof sph);
+    nd[4] = na[4] + nb[4];
+    light_tree_put_int(nd + 5, a);
+    light_tree_put_int(nd + 6, b);
+    light_tree_put_int(nd + 7, parent);
+    return k;
+}
+
+// polys: the sampling blocks of records [n_sphere_lights, ...)
+void build_light_tree(const float* lights, const float* polys, int n_sphere_lights, int n, std::vector<float>& out) {
+    out.clear();
+    if (n < 2) return;
+    out.assign((size_t)(2 * n - 1) * RT_LIGHT_NODE_FLOATS, 0.0f);
+    LightTreeBuild B{lights, n, out.data()};
+    B.ok.assign((size_t)2 * n - 1, 0);
+    std::vector<int> idx((size_t)n);
+    for (int j = 0; j < n; j++) {
+        idx[j] = j;
+        const float* l = lights + (size_t)RT_LIGHT_FLOATS * j;
+        float* nd = out.data() + (size_t)RT_LIGHT_NODE_FLOATS * (n - 1 + j);
+        std::memcpy(nd, l, 4 * sizeof(float));
+        const float pw = std::fabs(l[4]) + std::fabs(l[5]) + std::fabs(l[6]);
+        float phi;
+        if (j < n_sphere_lights) {
+            phi = pw * l[3];
+        } else {
+            const float* q = polys + (size_t)RT_POLY_LIGHT_FLOATS * (j - n_sphere_lights);
+            phi = (pw * (q[3] + q[7])) / RT_PI;
+        }
+        const bool ok = std::isfinite(l[0]) && std::isfinite(l[1]) && std::isfinite(l[2]) && std::isfinite(l[3]) && std::isfinite(phi);
+        B.ok[(size_t)n - 1 + j] = ok;
+        nd[4] = ok ? phi : 0.0f;
+        light_tree_put_int(nd + 5, j);
+        light_tree_put_int(nd + 6, -1);
+    }
+    int budget = 1;  // ceil(log2 n) + 1
+    while ((1L << (budget - 1)) < n) budget++;
+    light_tree_node(B, idx.data(), n, -1, budget);
+}
+
 // ---- BVH over spheres / triangles / quads (large scenes) -------------------
 // Binned-SAH binary tree, emitted as EIGHT threaded (stackless) node arrays,
 // one per ray-direction octant: in array k the children of every node are
@@ -852,6 +1016,13 @@ int rt_compile_scene(const rt_scene& scene, const rt_scene_options& opt, rt_comp
         };
         for (int i = 0; i < nt; i++) light(ns + np + i, s->triangles[i].vertices, 3, s->triangles[i].mat);
         for (int i = 0; i < nq; i++) light(ns + np + nt + i, s->quads[i].vertices, 4, s->quads[i].mat);
+    }
+    // the light trees of the two table forms (rt_set_light_hierarchy): likewise always built
+    {
+        const int n_all = (int)(r.lights.size() / RT_LIGHT_FLOATS);
+        build_light_tree(r.lights.data(), r.light_polys.data(), r.n_sphere_lights, r.n_sphere_lights, r.light_tree_spheres);
+        if (n_all > r.n_sphere_lights)
+            build_light_tree(r.lights.data(), r.light_polys.data(), r.n_sphere_lights, n_all, r.light_tree_all);
     }
     // overflow bounds of the bounded primitives' tests (rt_layout.h ovf_*;
     // a NaN or inf input makes its bound infinite, so no ray is culled and

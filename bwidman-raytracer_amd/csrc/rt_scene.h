@@ -47,6 +47,10 @@ struct rt_compiled_scene {
     std::vector<float> lights;
     std::vector<float> light_polys;
     int n_sphere_lights = 0;
+    // light trees (rt_layout.h RT_LIGHT_NODE_FLOATS; rt_set_light_hierarchy): one over the sphere prefix
+    // and one over the whole table, each empty where its form has fewer than 2 records (the second also
+    // where the table holds no polygon record: it would be the first again)
+    std::vector<float> light_tree_spheres, light_tree_all;
 };
 
 // RT_OK, or RT_ERR_UNSUPPORTED with the reason in err; `out` is written only on

@@ -39,6 +39,8 @@
 // diffuse bounces; it combines with every other flag but --precision fast.
 // --light-picking uniform|weighted (rt_set_light_picking) chooses how such a
 // bounce picks its light; it needs --light-sampling.
+// --light-hierarchy (rt_set_light_hierarchy) lets the weighted pick descend the
+// light tree instead of walking the table; it needs --light-picking weighted.
 // --light-shapes spheres|all (rt_set_light_shapes) chooses whether emissive
 // triangles and quads are sampled as well; it needs --light-sampling.
 // --denoise [N] filters the final frame with rt_denoise (N a-trous levels,
@@ -120,7 +122,8 @@ static const char* kUsage =
     "                   [--width 1920] [--height 1080] [--frames 8] [--frames-per-call 1]\n"
     "                   [--max-bounces 5] [--background r,g,b] [--spp 1] [--device 0] [--gpus 1]\n"
     "                   [--cpu [THREADS]] [--precision exact|fast]\n"
-    "                   [--light-sampling [--light-picking uniform|weighted] [--light-shapes spheres|all]]\n"
+    "                   [--light-sampling [--light-picking uniform|weighted [--light-hierarchy]]\n"
+    "                    [--light-shapes spheres|all]]\n"
     "                   [--keys \"W*10,W+LEFT*5,*3\"]\n"
     "                   [--dt SECONDS] [--out image.png|image.ppm] [--dump-scene file.bin]\n"
     "                   [--denoise [N]] [--sigma-color S] [--sigma-normal S] [--sigma-plane S]\n"
@@ -191,6 +194,7 @@ int main(int argc, char** argv) {
     bool light_sampling = false;
     int light_picking = -1;  // -1: not given
     int light_shapes = -1;
+    bool light_hierarchy = false;
     float bg[3] = {0.0f, 0.0f, 0.0f};
     double fixed_dt = -1.0;
     bool denoise = false;
@@ -252,6 +256,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (!std::strcmp(argv[i], "--light-hierarchy")) light_hierarchy = true;
         else if (!std::strcmp(argv[i], "--light-shapes")) {
             const char* v = next();
             if (!std::strcmp(v, "spheres")) light_shapes = RT_LIGHT_SHAPES_SPHERES;
@@ -324,6 +329,10 @@ int main(int argc, char** argv) {
     }
     if (light_picking >= 0 && !light_sampling) {
         std::fprintf(stderr, "--light-picking needs --light-sampling: it chooses how light sampling picks its light\n");
+        return 2;
+    }
+    if (light_hierarchy && light_picking != RT_LIGHT_PICK_WEIGHTED) {
+        std::fprintf(stderr, "--light-hierarchy needs --light-picking weighted: it is the weighted pick through a light tree\n");
         return 2;
     }
     if (light_shapes >= 0 && !light_sampling) {
@@ -421,6 +430,7 @@ int main(int argc, char** argv) {
         if ((rc = rt_set_precision(ctxs[g], precision))) return die(ctxs[g], rc, "rt_set_precision");
         if ((rc = rt_set_light_sampling(ctxs[g], light_sampling ? 1 : 0))) return die(ctxs[g], rc, "rt_set_light_sampling");
         if (light_picking >= 0 && (rc = rt_set_light_picking(ctxs[g], light_picking))) return die(ctxs[g], rc, "rt_set_light_picking");
+        if (light_hierarchy && (rc = rt_set_light_hierarchy(ctxs[g], 1))) return die(ctxs[g], rc, "rt_set_light_hierarchy");
         if (light_shapes >= 0 && (rc = rt_set_light_shapes(ctxs[g], light_shapes))) return die(ctxs[g], rc, "rt_set_light_shapes");
         if ((rc = rt_set_samples_per_pixel(ctxs[g], spp))) return die(ctxs[g], rc, "rt_set_samples_per_pixel");
         if ((rc = rt_set_scene(ctxs[g], &view))) return die(ctxs[g], rc, "rt_set_scene");

@@ -338,6 +338,61 @@ RT_API int rt_get_light_shapes(const rt_context* ctx);
  * capacity 0). */
 #define RT_LIGHT_RECORD_FLOATS 8
 RT_API int rt_get_lights(rt_context* ctx, float* out, int capacity);
+/* A light hierarchy for weighted picking.  With the
+ * switch on (1; 0 the default), RT_LIGHT_PICK_WEIGHTED picks its light by a
+ * stochastic descent of a binary tree that rt_set_scene builds over the light
+ * table — at every node one of the two children, with a probability
+ * proportional to a bound of what the lights below it can contribute at the
+ * shading point (summed power over squared distance, times the largest cosine
+ * towards the node's bounding sphere; a child that is a single light takes
+ * that light's own weight) — instead of walking the whole table twice: the
+ * cost per diffuse bounce is the depth of the tree, at most
+ * ceil(log2 n) + 1 levels, where the walk's is linear in n.  The pick
+ * probabilities approximate the walk's, they do not equal them; both are
+ * unbiased for the same image, and the path itself does not change (same
+ * draws, same rays, same RNG state), so frames of every pick mode may share one
+ * accumulation.
+ * The value is stored independently of the other switches and acts only while
+ * light sampling is on, picking is weighted and the table the render sees
+ * (rt_set_light_shapes) holds at least 2 records; everywhere else a render is
+ * bit for bit what it is without the switch.  GPU and CPU contexts agree bit
+ * for bit.  Per context; takes effect at the next render; resets neither the
+ * accumulation, nor the frame counter, nor the RNG streams.  Values other than
+ * 0 / 1 return RT_ERR_INVALID_ARGUMENT. */
+RT_API int rt_set_light_hierarchy(rt_context* ctx, int on);
+RT_API int rt_get_light_hierarchy(const rt_context* ctx);
+/* The light tree of the table that the current shapes mode sees, as
+ * rt_get_lights returns that table: 2 n - 1 nodes of RT_LIGHT_NODE_FLOATS
+ * floats for a table of n >= 2 records, none for a smaller one.  Nodes
+ * [0, n - 1) are internal, the root first and every parent in front of its
+ * children; node n - 1 + j is the leaf of table record j.
+ *   {cx, cy, cz, R*R, phi, a, b, parent}      (a, b, parent: int32 bits)
+ * {c, R*R}: a bounding sphere — a leaf's is its record's, an internal node's
+ * contains both children's, in exact arithmetic on the stored floats.  phi:
+ * the power term, a leaf's (|e.r| + |e.g| + |e.b|) r*r for a sphere and
+ * (|e.r| + |e.g| + |e.b|) area / pi for a polygon, an internal node's the float
+ * sum phi(a) + phi(b).  a, b: the children's node indices; a leaf has
+ * {j, -1}.  parent: -1 for the root.  Returns the number of nodes (or a
+ * negative error) and copies at most `capacity` of them to `out` (may be null
+ * with capacity 0).  The tree is built whether or not the switch is on. */
+#define RT_LIGHT_NODE_FLOATS 8
+RT_API int rt_get_light_tree(rt_context* ctx, float* out, int capacity);
+/* Where the shadow rays go: the probability with which next-event estimation,
+ * under the context's current pick mode (rt_set_light_picking,
+ * rt_set_light_hierarchy) and shapes mode, picks each table light at `count`
+ * shading points.  Point i is points[6 i ..] = {P.xyz, n.xyz}, n the shading
+ * normal as the path has it (a sphere's is of unit length, a plane's or
+ * polygon's is its unnormalised one), on primitive prims[i] (-1: on none).
+ * out takes count x n floats, n the number of table lights (the return value;
+ * 0: nothing is written): row i holds 1 / n under uniform picking, w_j / W
+ * under weighted picking and, with the hierarchy, the product of the branch
+ * probabilities down to light j's leaf — computed by the functions the sampler
+ * itself picks with, whether or not light sampling is on.  A row is all 0
+ * where the pick rule gives no direct term (no light has a positive weight
+ * there) or where a hit with that normal takes no light sample.  A GPU context
+ * computes it on the device, a CPU context on the host; they agree bit for
+ * bit.  Returns n or a negative error. */
+RT_API int rt_light_pick_probabilities(rt_context* ctx, const float* points, const int* prims, int count, float* out);
 
 /* samplesPerPixel (Main.cu:27, a compile-time constant 1 there): each
  * progressive frame traces n paths from the frame's one jittered camera ray
